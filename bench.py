@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X (contract: one JSON line on stdout from rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the
+line (metric, value, unit, ms_per_step, dtype, abmil_fwd_ms, model_tflops, config).  Everything after the timed region
+listed below runs only with --full.
 
 ``python bench.py --gpus N`` with N > 1 and no torchrun environment starts the N ranks ITSELF (a child
 ``python -m torch.distributed.run ...`` started before this process has touched the GPU; its output is relayed and its
@@ -18,7 +22,8 @@ region:
 value = regions/s over ALL ranks (K steps per rank, max-over-ranks wall time between barriers); ``abmil_fwd_ms`` is the
 HIP-event time of the CLAM_SB call inside the same timed steps (weak scaling: per-GPU work is fixed).
 
-After the timed region:
+After the timed region (--full):
+  * board power and sclk over the timed steps, and the MFMA rate bare loops sustain (rank 0, N = 1);
   * ``config5`` (every N): BASELINE configs[4] -- 64 synthetic slides sharded slide i -> rank i mod N, per slide a stated
     SAMPLE of its ~8 192 regions through HIPT_4K (resident pixels), the slide's bag through CLAM_SB, ONE all-gather of all
     logits and ragged attention logits (``hipt_abmil_atec23_amd/pipeline.py``); slides/s extrapolated from the sample;
@@ -71,7 +76,19 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearsal of the multi-rank leg without a GPU: gloo backend, CPU tensors, stand-in models -- the same spawn / "
                          "init / barrier / timed loop / config 5 / gather / rank-0 JSON code path (tests/test_pipeline.py runs it with --gpus 2)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: power and sustained-MFMA readings, config 5, the per-kernel roofline "
+                         "leg, the reference's call patterns, the CPU baseline and the selfcheck (the options above that steer those legs "
+                         "apply only here).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32): "
+                         "features [R,192], logits, y_prob, y_hat, a_raw; rank r > 0 adds the suffix _rank<r>")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the result line is the time of the timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -114,7 +131,7 @@ def dry_models():
     return model, clam, clam
 
 
-def build_models(dev, dtype):
+def build_models(dev, dtype, slide_aggregator=True):
     from hipt_abmil_atec23_amd import CLAM_SB, HIPT_4K, synth
     m = HIPT_4K(None, None, dev, dev)
     m.model256.load_state_dict(synth.make_state_dict(synth.vit_param_specs("vit256"), 256))
@@ -123,6 +140,8 @@ def build_models(dev, dtype):
     c = CLAM_SB(size_arg="hipt_384")
     c.load_state_dict(synth.make_state_dict(synth.clam_param_specs((384, 128, 64)), 384))
     c = c.eval().to(dev).set_compute_dtype(dtype)
+    if not slide_aggregator:  # (only config 5 uses it)
+        return m, c, None
     c192 = CLAM_SB(size_arg="hipt_big")  # the slide aggregator over HIPT_4K's 192-d region features (docs/README.md:69)
     c192.load_state_dict(synth.make_state_dict(synth.clam_param_specs((192, 128, 64)), 192))
     c192 = c192.eval().to(dev).set_compute_dtype(dtype)
@@ -331,6 +350,19 @@ def emit_json_line(out) -> None:
 
 _REAL_STDOUT: list = []
 
+DUMP_NAMES = ("features", "logits", "a_raw", "y_prob", "y_hat")  # the order step() returns them in
+
+
+def dump_outputs(dirname, last, rank) -> None:
+    """--dump-outputs: what the last timed step handed its caller -- HIPT_4K's [R,192] features and CLAM_SB's logits, A_raw,
+    Y_prob, Y_hat -- as DIR/<name>.npy in float32 (bf16 widens exactly; the class index is exact), 0.5 MB at the default sizes.
+    Inputs and weights are seeded, so two builds run with the same arguments can be compared array by array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, t in zip(DUMP_NAMES, last):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), t.detach().float().cpu().numpy())
+
 
 def main():
     args = parse_args()
@@ -370,7 +402,7 @@ def main():
         dev = torch.device("cuda", local)
         torch.cuda.set_device(dev)
         N.lib()  # fail loudly before doing anything if the native library is missing
-        model, clam, clam192 = build_models(dev, args.dtype)
+        model, clam, clam192 = build_models(dev, args.dtype, slide_aggregator=args.full and args.slides > 0)
         REGION_PX, n_bag = REGION, BAG_N
     model.streams = args.streams
     model.chunk = args.chunk
@@ -397,10 +429,10 @@ def main():
         if timed:
             ev[i][0].record()
         with torch.no_grad():
-            logits, _, _, a_raw, _ = clam(bags[i % n_bags])
+            logits, y_prob, y_hat, a_raw, _ = clam(bags[i % n_bags])
         if timed:
             ev[i][1].record()
-        return f, logits, a_raw
+        return f, logits, a_raw, y_prob, y_hat
 
     def barrier():
         if grp[0]:
@@ -413,7 +445,7 @@ def main():
     # board power / shader clock over the timed steps: a thread of THIS process reading the card's hwmon node (tools/telemetry.py; sysfs only --
     # no GPU call, no child process), rank 0 only
     sampler = None
-    if not dry and rank == 0 and os.environ.get("HIPT_BENCH_NO_POWER", "0") in ("", "0"):
+    if args.full and not dry and rank == 0 and os.environ.get("HIPT_BENCH_NO_POWER", "0") in ("", "0"):
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             from telemetry import PowerSampler, pci_bus_id_of
@@ -435,10 +467,12 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
     abmil_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if args.steps else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
 
     # ---- config 5 (BASELINE configs[4]): slides sharded over the ranks, one all-gather ----
     cfg5 = None
-    if args.slides > 0:
+    if args.full and args.slides > 0:
         slides = PL.synthetic_slides(args.slides, args.slide_regions)
         ns = min(args.slide_sample, R)
         calls = [0]
@@ -495,7 +529,7 @@ def main():
     # launches, no event record per launch.  Rotating bags (5 x 77 MB > Infinity Cache).
     abmil_graph = None
     # (single-process runs only: with a process group alive, RCCL's watchdog thread may touch the runtime while a capture is open)
-    if not dry and args.steps and world == 1 and not args.no_extras:
+    if args.full and not dry and args.steps and world == 1 and not args.no_extras:
         try:
             KG, REP = 20, 5
             gs = torch.cuda.Stream()
@@ -570,6 +604,13 @@ def main():
         # the process group the timed gather and config 5 ran over (backend "nccl" = RCCL on ROCm), as the group itself reports it
         out["rccl_ranks" if group_info["backend"] == "nccl" else "group_ranks"] = group_info["ranks"]
         out["collective_backend"] = group_info["backend"]
+    if not args.full:
+        # a plain run ends here: the headline figure of the timed steps (every leg below is --full's)
+        emit_json_line(out)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
 
     if power_timed is not None:
         # what the board drew and the shader clock it held over the timed steps (hwmon power1_input / freq1_input, 10 ms samples)

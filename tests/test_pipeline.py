@@ -117,7 +117,7 @@ def test_bench_dry_run_two_ranks(launcher):
     import json
     import subprocess
     bench = os.path.join(ROOT, "bench.py")
-    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"]
+    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run", "--full"]
     if launcher == "self":
         cmd = [sys.executable, bench] + tail
     else:
@@ -138,6 +138,37 @@ def test_bench_dry_run_two_ranks(launcher):
     assert bad.returncode != 0 and not any(l.startswith("{") for l in bad.stdout.splitlines())
 
 
+@pytest.mark.timeout(300)
+def test_bench_dry_run_plain_line_and_dump_outputs(tmp_path):
+    """Without --full a run is the timed steps and the headline line only (no config 5 or other legs); --dump-outputs writes
+    the last timed step's outputs of every rank as float32 .npy, and the same arguments give the same arrays run after run."""
+    import json
+    import subprocess
+
+    import numpy as np
+    bench = os.path.join(ROOT, "bench.py")
+    dumps = []
+    for k in range(2):
+        d_out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "4", "--warmup", "1", "--dry-run", "--dump-outputs", str(d_out)],
+                           capture_output=True, text=True, timeout=280, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert not {"config5", "kernels", "roofline", "extras", "cpu_baseline", "selfcheck", "power"} & set(d)
+        dumps.append({f: np.load(d_out / f) for f in sorted(os.listdir(d_out))})
+    names = ("features", "logits", "a_raw", "y_prob", "y_hat")
+    assert sorted(dumps[0]) == sorted([f"{n}.npy" for n in names] + [f"{n}_rank1.npy" for n in names])
+    assert dumps[0]["features.npy"].shape == (24, 192) and dumps[0]["a_raw.npy"].shape == (1, 2000)
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][f]), f
+    assert not np.array_equal(dumps[0]["features.npy"], dumps[0]["features_rank1.npy"])  # each rank its own inputs
+    bad = subprocess.run([sys.executable, bench, "--dry-run", "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert bad.returncode != 0 and not any(l.startswith("{") for l in bad.stdout.splitlines())
+
+
 def test_bench_dry_run_eight_ranks_and_fewer_slides_than_ranks():
     """The driver's 8-rank launch form rehearsed on CPU / gloo: (i) 8 ranks over the default 64 slides, (ii) 8 ranks over 5
     slides -- three ranks have NO slide: they must contribute an empty (all -1) block to the gather and still reach every barrier,
@@ -148,7 +179,7 @@ def test_bench_dry_run_eight_ranks_and_fewer_slides_than_ranks():
     bench = os.path.join(ROOT, "bench.py")
     for slides in (64, 5):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), bench, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run", "--slides", str(slides)]
+               "--master-port", str(_free_port()), bench, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run", "--full", "--slides", str(slides)]
         env = dict(os.environ, OMP_NUM_THREADS="1", MKL_NUM_THREADS="1")  # 8 ranks on the container's 8 cores
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=560, cwd=ROOT, env=env)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -307,7 +338,7 @@ def test_bench_one_rank_through_the_launcher_reports_rccl_ranks():
     over RCCL."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port",
            str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--regions", "3", "--profile-steps", "0",
-           "--no-cpu-baseline", "--no-extras", "--slides", "4", "--slide-sample", "2"]
+           "--full", "--no-cpu-baseline", "--no-extras", "--slides", "4", "--slide-sample", "2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
