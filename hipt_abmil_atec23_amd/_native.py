@@ -117,6 +117,8 @@ SIGNATURES = {
     "hipt_clam_train_forward": (_i, [_TW, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "hipt_clam_train_backward": (_i, [_TW, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _TG, _p, _sz, _p]),
     "hipt_topk_rows": (_i, [_p, _i, _i, _i, _p, _p]),
+    "hipt_augment_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hipt_augment_regions": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

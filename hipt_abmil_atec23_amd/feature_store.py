@@ -146,6 +146,9 @@ class _HostFeed:
         if self.buf[s] is None or self.buf[s].shape != shape or self.buf[s].dtype != like.dtype:
             self.buf[s] = torch.empty(shape, dtype=like.dtype, device=self.device)
             self.stage[s] = None
+            # the block comes from the compute stream's pool: it may be one that work still enqueued there has just freed (the
+            # augmented copy of the previous call, which is exactly this size); the copy stream writes it only after that work
+            self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))
         if self.free[s] is not None:
             self.copy_stream.wait_event(self.free[s])  # the compute that read this buffer two calls ago
         self.fill = 0
@@ -206,6 +209,44 @@ def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], f
     and the features of call k are read back (on a stream of their own) only after call k + 1 has been enqueued -- the link, the GPU and the host loop overlap.  Same
     gathered tensor, same kernels, same bits as with resident batches."""
     w = FeatureWriter(feat_dir, slide_id)
+    return _extract(model, batches, [w], lambda regions, first: [model(regions)], coalesce)[0]
+
+
+def extract_slide_augmented(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], feat_dir: str, slide_id: str, policy: str,
+                            n_augs: int, seed: int = 0, include_original: bool = True, coalesce: int = 8) -> list:
+    """``extract_features_fp.py --use_transforms <policy>`` run ``n_augs`` times, plus the plain run, in ONE pass over the loader:
+    every (gathered) call of ``extract_slide`` goes through ``model`` as it is -> ``pt_files/{slide}.pt`` (bit for bit what
+    ``extract_slide`` writes; skipped when ``include_original`` is False) and then, for k = 1..n_augs, augmented on the device
+    (``augment.RegionAugment(policy, seed)``: region i of the slide gets the parameters seeded by (seed, slide_id, k, i)) and
+    through ``model`` again -> ``pt_files/{slide}aug{k}.pt``, the files ``Generic_MIL_Dataset(use_augs=True)`` reads
+    (datasets/dataset_generic.py:497-507).  Each file has its coords sidecar.  Regions must be raw uint8 RGB (the reference
+    augments before eval_transforms): float regions raise ``ValueError``.  Returns the written ``.pt`` paths, original first."""
+    from .augment import POLICIES, RegionAugment
+
+    if policy not in POLICIES:
+        raise ValueError(f"unknown augmentation policy {policy!r}; known: {sorted(POLICIES)}")
+    if n_augs < 0 or (n_augs == 0 and not include_original):
+        raise ValueError(f"n_augs={n_augs}, include_original={include_original}: nothing to write")
+    aug = RegionAugment(policy, seed)
+    writers = ([FeatureWriter(feat_dir, slide_id)] if include_original else []) + \
+              [FeatureWriter(feat_dir, f"{slide_id}aug{k}") for k in range(1, n_augs + 1)]
+
+    def run(regions, first):
+        if regions.dtype != torch.uint8:
+            raise ValueError(f"extract_slide_augmented: regions must be raw uint8 RGB (got {regions.dtype}); the reference augments "
+                             f"before eval_transforms")
+        out = [model(regions)] if include_original else []
+        for k in range(1, n_augs + 1):
+            out.append(model(aug(regions, slide_id, k, first)))
+        return out
+
+    return _extract(model, batches, writers, run, coalesce)
+
+
+def _extract(model, batches, writers, run, coalesce: int) -> list:
+    """the loop of ``extract_slide``; ``run(regions, first)`` -> one feature tensor per writer for a call whose regions are
+    regions ``first, first+1, ...`` of the slide (in loader order)"""
+    done_regions = [0]
     held: list = []  # (regions or None when already staged into the host feed's gather buffer, coords, count) waiting for company
     shape_key = [None]
     ncalls = [0]
@@ -215,13 +256,14 @@ def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], f
     feed = [None]        # _HostFeed, made when the first host batch for a HIP model arrives
     pending: list = []   # [(features on the device, counts, coords)]: read back one call late
 
-    def append_call(feats, counts, coords, done=None):
-        if done is not None:
-            feats = feed[0].read_back(feats, done)
-        o = 0
-        for n, c in zip(counts, coords):  # one append per loader batch, as the reference's loop does
-            w.append(feats[o:o + n], c)
-            o += n
+    def append_call(outs, counts, coords, done=None):
+        for w, feats in zip(writers, outs):
+            if done is not None:
+                feats = feed[0].read_back(feats, done)
+            o = 0
+            for n, c in zip(counts, coords):  # one append per loader batch, as the reference's loop does
+                w.append(feats[o:o + n], c)
+                o += n
 
     def drain():
         while pending:
@@ -251,7 +293,8 @@ def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], f
         held.clear()
         shape_key[0] = None
         ncalls[0] += 1
-        feats = model(regions)
+        feats = run(regions, done_regions[0])
+        done_regions[0] += sum(counts)
         if slot is not None:
             feed[0].release(slot)
         del regions
@@ -304,13 +347,26 @@ def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], f
                 flush()
         flush()
         drain()
-    return w.close()
+    return [w.close() for w in writers]
 
 
-def load_bag(data_dir: str, slide_id: str, max_patches_per_slide: Optional[int] = None, rng=None) -> torch.Tensor:
-    """``datasets/dataset_generic.py:512-520``: the slide's ``[n, d]`` features, sub-sampled WITH replacement to
+def load_bag(data_dir: str, slide_id: str, max_patches_per_slide: Optional[int] = None, rng=None, number_of_augs: int = 0,
+             perturb_variance: Optional[float] = None) -> torch.Tensor:
+    """``datasets/dataset_generic.py:497-526``: the slide's ``[n, d]`` features, sub-sampled WITH replacement to
     ``max_patches_per_slide`` rows when it has more (``rng``: a ``numpy.random.Generator`` / ``RandomState`` for
-    reproducible draws; default ``np.random`` as the reference)."""
+    reproducible draws; default ``np.random`` as the reference).
+
+    ``number_of_augs > 0`` (``use_augs``): first draws k uniformly in ``[0, number_of_augs]`` (``rng`` or, by default, Python's
+    ``random.randint`` as the reference) and reads ``{slide}aug{k}.pt`` for k > 0, the plain file for k = 0.
+    ``perturb_variance`` (``use_perturbs``): adds ``torch.randn_like(features) * perturb_variance`` after the sub-sampling."""
+    if number_of_augs > 0:
+        if rng is None:
+            import random
+            k = random.randint(0, number_of_augs)
+        else:
+            k = int(rng.integers(0, number_of_augs + 1)) if hasattr(rng, "integers") else int(rng.randint(0, number_of_augs + 1))
+        if k > 0:
+            slide_id = f"{slide_id}aug{k}"
     path = os.path.join(data_dir, "pt_files", f"{slide_id}.pt")
     try:
         features = torch.load(path)
@@ -319,4 +375,6 @@ def load_bag(data_dir: str, slide_id: str, max_patches_per_slide: Optional[int] 
     if max_patches_per_slide is not None and max_patches_per_slide < len(features):
         idx = (rng if rng is not None else np.random).choice(len(features), max_patches_per_slide)
         features = features[torch.as_tensor(np.asarray(idx), dtype=torch.int64)]
+    if perturb_variance is not None:
+        features = features + torch.randn_like(features) * perturb_variance
     return features

@@ -425,6 +425,32 @@ int hipt_clam_train_backward(const hipt_clam_train_weights* w, const float* bag,
  * ids int64 [rows, 2, k], descending / ascending by value, ties -> lowest index first. */
 int hipt_topk_rows(const float* A, int rows, int N, int k, int64_t* ids, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Region augmentation (extract_features_fp.py:89-136, --use_transforms HIPT_*): uint8 RGB in, uint8 out, one parameter
+ * record per region drawn by the caller.  Reproduces torchvision's PIL path: HFlip / VFlip, RandomAffine (Pillow AFFINE,
+ * NEAREST, fill 0), ColorJitter (Pillow ImageEnhance blends, HSV hue shift) and GaussianBlur((1,3)).
+ * ---------------------------------------------------------------------------------- */
+enum { HIPT_AUG_HFLIP = 1, HIPT_AUG_VFLIP = 2, HIPT_AUG_AFFINE = 4, HIPT_AUG_BLUR = 8 };
+enum { HIPT_AUG_BRIGHTNESS = 0, HIPT_AUG_CONTRAST = 1, HIPT_AUG_SATURATION = 2, HIPT_AUG_HUE = 3 };
+
+typedef struct hipt_augment_params {
+    double  affine[6];   /* Pillow AFFINE data (output pixel -> input pixel, width = cols), read when flags & HIPT_AUG_AFFINE */
+    float   factor[3];   /* blend factors of brightness, contrast, saturation                                              */
+    float   blur_w[3];   /* vertical 3-tap weights (row above, row, row below), read when flags & HIPT_AUG_BLUR              */
+    int32_t flags;       /* HIPT_AUG_*; flips apply first (to the source), then the affine; BLUR is alone (the rest ignored)  */
+    int32_t hue_shift;   /* added to Pillow's HSV hue modulo 256                                                             */
+    int32_t n_ops;       /* colour ops applied, 0..4                                                                         */
+    int32_t ops[4];      /* HIPT_AUG_BRIGHTNESS.. in application order                                                       */
+    int32_t reserved;
+} hipt_augment_params;
+
+/* workspace of hipt_augment_regions: a uint64 luminance sum and two sampling tables per region */
+size_t hipt_augment_workspace_bytes(int n, int rows, int cols);
+/* src / dst uint8 [n,3,rows,cols] (interleaved = 0) or [n,rows,cols,3] (interleaved = 1), any rows x cols; params: n DEVICE
+ * records; src and dst must not overlap.  A record that is the identity copies the bytes. */
+int hipt_augment_regions(const uint8_t* src, int interleaved, int n, int rows, int cols, const hipt_augment_params* params,
+                         uint8_t* dst, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
