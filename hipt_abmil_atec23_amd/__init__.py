@@ -1,6 +1,7 @@
 """hipt_abmil_atec23_amd — MI355X-native (gfx950) implementation of the one data-parallel hot path of
 scjjb/HIPT_ABMIL_ATEC23: HIPT_4K feature extraction (ViT-256 -> ViT-4K) and the CLAM_SB / ABMIL
-gated-attention pooling, behind the reference's own Python call surface.
+gated-attention pooling, behind the reference's own Python call surface; also the reference's ResNet-50 baseline
+extractor (``resnet50_baseline``, the ResNet-ABMIL route).
 
     from hipt_abmil_atec23_amd import HIPT_4K, CLAM_SB, Attn_Net_Gated
     import hipt_abmil_atec23_amd as amd; amd.install()   # make the reference scripts import these classes
@@ -19,6 +20,8 @@ _LAZY = {
     "Attn_Net": ("model_clam", "Attn_Net"), "Attn_Net_Gated": ("model_clam", "Attn_Net_Gated"),
     "VisionTransformer": ("vision_transformer", "VisionTransformer"), "vit_small": ("vision_transformer", "vit_small"),
     "VisionTransformer4K": ("vision_transformer4k", "VisionTransformer4K"), "vit4k_xs": ("vision_transformer4k", "vit4k_xs"),
+    "ResNet_Baseline": ("resnet_custom", "ResNet_Baseline"), "Bottleneck_Baseline": ("resnet_custom", "Bottleneck_Baseline"),
+    "resnet50_baseline": ("resnet_custom", "resnet50_baseline"),
     "install": ("dropin", "install"), "build_native": ("_native", "build"),
     "FeatureWriter": ("feature_store", "FeatureWriter"), "extract_slide": ("feature_store", "extract_slide"),
     "load_bag": ("feature_store", "load_bag"), "load_coords": ("feature_store", "load_coords"),

@@ -61,8 +61,21 @@ class ClamTrainGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dw1", "db1", "dwa", "dba", "dwb", "dbb", "dwc", "dbc", "dwcls", "dbcls", "dbag")]
 
 
+class ConvBN(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("weight", "bn_weight", "bn_bias", "bn_mean", "bn_var")] + [
+        ("cout", C.c_int32), ("cin", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32), ("bn_eps", C.c_float), ("reserved", C.c_int32)]
+
+
+class ResnetWeights(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("layers", C.c_int32 * 3), ("convs", C.POINTER(ConvBN)), ("n_convs", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+RESNET_IN_F32, RESNET_IN_U8, RESNET_IN_U8_HWC = 0, 1, 2
+
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
+_CB, _RW = C.POINTER(ConvBN), C.POINTER(ResnetWeights)
 _i, _i64, _p, _sz, _f = C.c_int, C.c_int64, C.c_void_p, C.c_size_t, C.c_float
 
 # name -> (restype, argtypes); mirrors include/hipt_abmil.h one to one
@@ -119,6 +132,15 @@ SIGNATURES = {
     "hipt_topk_rows": (_i, [_p, _i, _i, _i, _p, _p]),
     "hipt_augment_workspace_bytes": (_sz, [_i, _i, _i]),
     "hipt_augment_regions": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "hipt_resnet_packed_bytes": (_sz, [_RW]),
+    "hipt_resnet_pack_weights": (_i, [_RW, _p, _p]),
+    "hipt_resnet_workspace_bytes": (_sz, [_RW, _i, _i, _i]),
+    "hipt_resnet_forward": (_i, [_RW, _p, _p, _i, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "hipt_conv_bn_packed_bytes": (_sz, [_CB, _i]),
+    "hipt_conv_bn_pack": (_i, [_CB, _i, _p, _p, _p]),
+    "hipt_conv2d": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
+    "hipt_resnet_maxpool": (_i, [_p, _i, _i, _i, _i, _p, _i, _p]),
+    "hipt_resnet_avgpool": (_i, [_p, _i, _i, _i, _p, _i, _p]),
 }
 
 _lib = None

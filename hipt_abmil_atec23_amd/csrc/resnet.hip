@@ -1,0 +1,607 @@
+// ResNet-50 baseline feature extractor (reference models/resnet_custom.py:ResNet_Baseline): stem conv 7x7/2 + BN + ReLU,
+// maxpool 3x3/2, layer1..layer3 of Bottleneck_Baseline, global average pool -> [n, 1024] fp32.
+//
+// Activations are NHWC in the compute dtype T (fp32 or bf16); eval-mode BatchNorm is folded into the conv weights and a
+// fp32 bias at pack time.  Every convolution is ONE implicit-GEMM kernel: M = output pixels, N = Cout, K = kh*kw*Cin in
+// (ky, kx, ci) order, so that for Cin % KB == 0 (every conv but the stem) one 128-byte K slab of a row lies inside ONE
+// filter tap and is a contiguous 128-byte run of the input pixel's channels (or zeros for a padding tap).  The stem
+// (Cin = 3, K = 147) takes the element-gather form of the same loader, K zero-padded to the slab.
+//
+// Tile: 128 output pixels x BN (128 or 64) output channels per 256-thread workgroup (4 waves as 2(M) x 2(N)).  Operands are
+// staged global -> registers -> LDS (two buffers, one barrier per slab), with the same 16-byte-chunk XOR swizzle as
+// gemm.hip; weights are the MFMA A operand so each lane ends with 4 consecutive output channels of one pixel (8/16-byte
+// stores).  The epilogue is bias, optional residual add, optional ReLU, store.  No split-K and no atomics: every output
+// row is computed by the same instruction sequence whatever the batch, so features do not depend on the batch.
+// There are no hand-counted waits in this file (plain C++ loads and stores; the compiler places every s_waitcnt).
+#include "common.h"
+
+namespace {
+
+constexpr int RN_BM = 128;
+constexpr int RN_THREADS = 256;
+
+struct ConvArgs {
+    const void* x;      // [n, h, w, cin] T
+    const void* wt;     // [cout, kp] T (BN folded, K zero-padded to kp)
+    const float* bias;  // [cout]
+    const void* resid;  // [M, cout] T or null
+    void* out;          // [M, cout] T
+    int n, h, w, cin, oh, ow, cout, kh, kw, stride, pad, K, kp, M, relu;
+};
+
+template <typename T, int BN, bool GATHER>
+__global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
+    constexpr int EPC = Tr<T>::EPC, KB = Tr<T>::KB;
+    constexpr int WQ = BN / 32;       // weight chunks per thread per slab
+    constexpr int NFR = BN / 32;      // 16-column fragments per wave (a wave owns BN / 2 columns)
+    constexpr int A_BYTES = RN_BM * 128, STAGE = A_BYTES + BN * 128;
+    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int li = lane & 15, g = lane >> 4;
+    const int tiles_n = p.cout / BN;
+    const int tile = xcd_remap(blockIdx.x, gridDim.x);
+    const int m0 = (tile / tiles_n) * RN_BM, n0 = (tile % tiles_n) * BN;
+
+    // ---- staging slots: row (tid >> 3) + 32 q, 16-byte chunk (tid & 7) ----
+    const int c = tid & 7;
+    const int ohw = p.oh * p.ow;
+    int iy0[4], ix0[4];
+    int64_t pix0[4];  // element offset of image b's pixel (0, 0)
+    bool mok[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int m = m0 + (tid >> 3) + 32 * q;
+        mok[q] = m < p.M;
+        const int mm = mok[q] ? m : 0;
+        const int b = mm / ohw, r = mm - b * ohw, oy = r / p.ow, ox = r - oy * p.ow;
+        iy0[q] = oy * p.stride - p.pad;
+        ix0[q] = ox * p.stride - p.pad;
+        pix0[q] = (int64_t)b * p.h * p.w * p.cin;
+    }
+    const T* X = (const T*)p.x;
+    const T* wrow[WQ];
+#pragma unroll
+    for (int q = 0; q < WQ; ++q) wrow[q] = (const T*)p.wt + (int64_t)(n0 + (tid >> 3) + 32 * q) * p.kp + c * EPC;
+
+    u32x4 ra[4], rw[WQ];
+    auto load = [&](int kt) {
+        const int k0 = kt * KB;
+        if constexpr (GATHER) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                T v[EPC];
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    const int k = k0 + c * EPC + e;
+                    const int tap = k / p.cin, ci = k - tap * p.cin, ky = tap / p.kw, kx = tap - ky * p.kw;
+                    const int iy = iy0[q] + ky, ix = ix0[q] + kx;
+                    const bool ok = mok[q] && k < p.K && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
+                    v[e] = ok ? X[pix0[q] + ((int64_t)iy * p.w + ix) * p.cin + ci] : Tr<T>::from_f(0.0f);
+                }
+                ra[q] = *(const u32x4*)v;
+            }
+        } else {
+            const int tap = k0 / p.cin, ci0 = k0 - tap * p.cin, ky = tap / p.kw, kx = tap - ky * p.kw;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int iy = iy0[q] + ky, ix = ix0[q] + kx;
+                const bool ok = mok[q] && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
+                ra[q] = ok ? *(const u32x4*)(X + pix0[q] + ((int64_t)iy * p.w + ix) * p.cin + ci0 + c * EPC) : u32x4{0u, 0u, 0u, 0u};
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < WQ; ++q) rw[q] = *(const u32x4*)(wrow[q] + k0);
+    };
+    auto store = [&](int s) {
+        char* sa = smem + s * STAGE;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = (tid >> 3) + 32 * q;
+            *(u32x4*)(sa + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = ra[q];
+        }
+#pragma unroll
+        for (int q = 0; q < WQ; ++q) {
+            const int r = (tid >> 3) + 32 * q;
+            *(u32x4*)(sa + A_BYTES + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = rw[q];
+        }
+    };
+
+    int foff[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) foff[ks] = li * 128 + (((g + 4 * ks) ^ ((li >> 1) & 7)) << 4);
+
+    f32x4 acc[4][NFR];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = p.kp / KB;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) load(kt + 1);
+        const char* sa = smem + (kt & 1) * STAGE + wm * 64 * 128;
+        const char* sw = smem + (kt & 1) * STAGE + A_BYTES + wn * (BN / 2) * 128;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            u32x4 wf[NFR], af[4];
+#pragma unroll
+            for (int j = 0; j < NFR; ++j) wf[j] = *(const u32x4*)(sw + j * 16 * 128 + foff[ks]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) af[i] = *(const u32x4*)(sa + i * 16 * 128 + foff[ks]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < NFR; ++j) Tr<T>::mma16(acc[i][j], wf[j], af[i]);
+        }
+        if (kt + 1 < nk) store((kt + 1) & 1);
+        __syncthreads();
+    }
+
+    // ---- epilogue: lane holds C[pixel m0 + wm*64 + 16 i + li][channel n0 + wn*BN/2 + 16 j + 4 g + 0..3] ----
+    const T* R = (const T*)p.resid;
+    T* O = (T*)p.out;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m0 + wm * 64 + i * 16 + li;
+        if (m >= p.M) continue;
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) {
+            const int n = n0 + wn * (BN / 2) + j * 16 + 4 * g;
+            f32x4 v = acc[i][j] + *(const f32x4*)(p.bias + n);
+            const int64_t o = (int64_t)m * p.cout + n;
+            if (R) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += Tr<T>::to_f(R[o + e]);
+            }
+            if (p.relu) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+            }
+            store4<T>(O + o, v);
+        }
+    }
+}
+
+// BN fold + repack of one conv: w [cout, cin, kh, kw] fp32 -> [cout, kp] T in (ky, kx, ci) order, zero beyond K; bias fp32.
+template <typename T>
+__global__ void rn_pack_kernel(hipt_conv_bn c, int K, int kp, T* wout, float* bout) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)c.cout * kp) return;
+    const int n = (int)(i / kp), k = (int)(i - (int64_t)n * kp);
+    const double scale = (double)c.bn_weight[n] / sqrt((double)c.bn_var[n] + (double)c.bn_eps);
+    float v = 0.0f;
+    if (k < K) {
+        const int tap = k / c.cin, ci = k - tap * c.cin, ky = tap / c.kw, kx = tap - ky * c.kw;
+        v = (float)((double)c.weight[(((int64_t)n * c.cin + ci) * c.kh + ky) * c.kw + kx] * scale);
+    }
+    wout[i] = Tr<T>::from_f(v);
+    if (k == 0) bout[n] = (float)((double)c.bn_bias[n] - (double)c.bn_mean[n] * scale);
+}
+
+// input -> NHWC T.  KIND 0: fp32 planar, already normalised (copied / rounded as is); 1: uint8 planar; 2: uint8 [n,h,w,3].
+// uint8: ToTensor + Normalize, (float(x) / 255 - mean_c) / std_c, each operation rounded on its own (file built with
+// -ffp-contract=off, IEEE division), which is what torch computes for the same bytes.
+// The layout is a template parameter on purpose: with a runtime `kind` switched per channel, hipcc (ROCm 7.2, gfx950) lowered
+// the interleaved case of channels 1 and 2 to a ubyte load from an address register the path never set (an illegal access).
+// One straight-line kernel per layout leaves no such control flow.
+struct NormArgs {
+    float mean[3], std[3];
+};
+template <typename T, int KIND>
+__global__ void rn_input_kernel(const void* x, int64_t npx, int64_t plane, NormArgs nm, T* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npx) return;
+    const int64_t b = i / plane, r = i - b * plane;
+    float v[3];
+    if constexpr (KIND == HIPT_RESNET_IN_F32) {
+        const float* s = (const float*)x + b * 3 * plane + r;
+        v[0] = s[0], v[1] = s[plane], v[2] = s[2 * plane];
+    } else {
+        uint8_t u[3];
+        if constexpr (KIND == HIPT_RESNET_IN_U8) {
+            const uint8_t* s = (const uint8_t*)x + b * 3 * plane + r;
+            u[0] = s[0], u[1] = s[plane], u[2] = s[2 * plane];
+        } else {
+            const uint8_t* s = (const uint8_t*)x + i * 3;
+            u[0] = s[0], u[1] = s[1], u[2] = s[2];
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            float f = (float)u[ch] / 255.0f;
+            f = f - nm.mean[ch];
+            v[ch] = f / nm.std[ch];
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[i * 3 + ch] = Tr<T>::from_f(v[ch]);
+}
+
+template <typename T>
+int launch_input(const void* x, int kind, int64_t npx, int64_t plane, const NormArgs& nm, T* out, hipStream_t st) {
+    const unsigned blocks = (unsigned)((npx + 255) / 256);
+    if (kind == HIPT_RESNET_IN_F32)
+        hipLaunchKernelGGL((rn_input_kernel<T, HIPT_RESNET_IN_F32>), dim3(blocks), dim3(256), 0, st, x, npx, plane, nm, out);
+    else if (kind == HIPT_RESNET_IN_U8)
+        hipLaunchKernelGGL((rn_input_kernel<T, HIPT_RESNET_IN_U8>), dim3(blocks), dim3(256), 0, st, x, npx, plane, nm, out);
+    else
+        hipLaunchKernelGGL((rn_input_kernel<T, HIPT_RESNET_IN_U8_HWC>), dim3(blocks), dim3(256), 0, st, x, npx, plane, nm, out);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
+}
+
+// MaxPool2d(3, 2, 1) on NHWC: one thread per (output pixel, 16-byte channel chunk).  Padding taps never win (-inf).
+template <typename T>
+__global__ void rn_maxpool_kernel(const T* x, int n, int h, int w, int C, int oh, int ow, T* out) {
+    constexpr int EPC = Tr<T>::EPC;
+    const int cpp = C / EPC;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n * oh * ow * cpp) return;
+    const int cc = (int)(i % cpp);
+    const int64_t px = i / cpp;
+    const int ox = (int)(px % ow), oy = (int)((px / ow) % oh), b = (int)(px / ((int64_t)ow * oh));
+    float m[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) m[e] = -INFINITY;
+    for (int dy = 0; dy < 3; ++dy) {
+        const int iy = oy * 2 - 1 + dy;
+        if (iy < 0 || iy >= h) continue;
+        for (int dx = 0; dx < 3; ++dx) {
+            const int ix = ox * 2 - 1 + dx;
+            if (ix < 0 || ix >= w) continue;
+            const u32x4 raw = *(const u32x4*)(x + (((int64_t)b * h + iy) * w + ix) * C + cc * EPC);
+            T v[EPC];
+            *(u32x4*)v = raw;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) m[e] = fmaxf(m[e], Tr<T>::to_f(v[e]));
+        }
+    }
+    T o[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) o[e] = Tr<T>::from_f(m[e]);
+    *(u32x4*)(out + px * C + cc * EPC) = *(const u32x4*)o;
+}
+
+// AdaptiveAvgPool2d(1): out[b, c] = (sum over the hw pixels in pixel order, fp32) / hw.  One thread per (b, c).
+template <typename T>
+__global__ void rn_avgpool_kernel(const T* x, int n, int hw, int C, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n * C) return;
+    const int64_t b = i / C, ch = i - b * C;
+    const T* p = x + b * hw * C + ch;
+    float s = 0.0f;
+    for (int k = 0; k < hw; ++k) s += Tr<T>::to_f(p[(int64_t)k * C]);
+    out[i] = s / (float)hw;
+}
+
+inline int esize(int dtype) { return dtype == HIPT_BF16 ? 2 : 4; }
+inline int kslab(int dtype) { return dtype == HIPT_BF16 ? 64 : 32; }
+inline int conv_out(int x, int k, int s, int pad) { return (x + 2 * pad - k) / s + 1; }
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int conv_kp(int cin, int kh, int kw, int dtype) {
+    const int K = cin * kh * kw, kb = kslab(dtype);
+    return (K + kb - 1) / kb * kb;
+}
+
+template <typename T, int BN>
+int launch_conv_bn(const ConvArgs& a, hipStream_t st) {
+    const int tiles = ((a.M + RN_BM - 1) / RN_BM) * (a.cout / BN);
+    if (a.cin % Tr<T>::KB == 0)
+        hipLaunchKernelGGL((rn_conv_kernel<T, BN, false>), dim3(tiles), dim3(RN_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((rn_conv_kernel<T, BN, true>), dim3(tiles), dim3(RN_THREADS), 0, st, a);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
+}
+
+template <typename T>
+int launch_conv(const ConvArgs& a, hipStream_t st) {
+    return a.cout % 128 == 0 ? launch_conv_bn<T, 128>(a, st) : launch_conv_bn<T, 64>(a, st);
+}
+
+// shape checks of one conv; fills the derived fields
+int conv_setup(ConvArgs& a, int dtype) {
+    HIPT_CHECK_ARG(dtype == HIPT_F32 || dtype == HIPT_BF16, "conv2d: bad dtype %d", dtype);
+    HIPT_CHECK_ARG(a.n > 0 && a.h > 0 && a.w > 0 && a.cin > 0 && a.cout > 0 && a.kh > 0 && a.kw > 0 && a.stride > 0 && a.pad >= 0,
+                   "conv2d: empty or negative shape");
+    HIPT_CHECK_ARG(a.cout % 64 == 0, "conv2d: cout=%d must be a multiple of 64", a.cout);
+    HIPT_CHECK_ARG(a.cin % kslab(dtype) == 0 || a.cin * a.kh * a.kw <= 1024,
+                   "conv2d: cin=%d is neither a multiple of %d nor a small (K <= 1024) gathered input", a.cin, kslab(dtype));
+    a.oh = conv_out(a.h, a.kh, a.stride, a.pad);
+    a.ow = conv_out(a.w, a.kw, a.stride, a.pad);
+    HIPT_CHECK_ARG(a.oh > 0 && a.ow > 0, "conv2d: empty output");
+    const int64_t M = (int64_t)a.n * a.oh * a.ow;
+    HIPT_CHECK_ARG(M < ((int64_t)1 << 31) / 2 && (int64_t)a.n * a.h * a.w * a.cin < ((int64_t)1 << 40), "conv2d: problem too large");
+    a.M = (int)M;
+    a.K = a.cin * a.kh * a.kw;
+    a.kp = conv_kp(a.cin, a.kh, a.kw, dtype);
+    HIPT_CHECK_ARG(a.x && a.wt && a.bias && a.out, "conv2d: null pointer");
+    HIPT_CHECK_ARG(((uintptr_t)a.x % 16) == 0 && ((uintptr_t)a.wt % 16) == 0 && ((uintptr_t)a.out % 16) == 0 &&
+                       ((uintptr_t)a.bias % 16) == 0 && ((uintptr_t)a.resid % 16) == 0,
+                   "conv2d: pointers must be 16-byte aligned");
+    return HIPT_OK;
+}
+
+int run_conv(ConvArgs& a, int dtype, hipStream_t st) {
+    const int rc = conv_setup(a, dtype);
+    if (rc != HIPT_OK) return rc;
+    return dtype == HIPT_BF16 ? launch_conv<bf16_t>(a, st) : launch_conv<float>(a, st);
+}
+
+int run_maxpool(const void* x, int n, int h, int w, int C, void* out, int dtype, hipStream_t st) {
+    const int oh = conv_out(h, 3, 2, 1), ow = conv_out(w, 3, 2, 1);
+    const int64_t tot = (int64_t)n * oh * ow * (C / (16 / esize(dtype)));
+    const unsigned blocks = (unsigned)((tot + 255) / 256);
+    if (dtype == HIPT_BF16)
+        hipLaunchKernelGGL(rn_maxpool_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, n, h, w, C, oh, ow, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(rn_maxpool_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)x, n, h, w, C, oh, ow, (float*)out);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
+}
+
+int run_avgpool(const void* x, int n, int hw, int C, float* out, int dtype, hipStream_t st) {
+    const unsigned blocks = (unsigned)(((int64_t)n * C + 255) / 256);
+    if (dtype == HIPT_BF16)
+        hipLaunchKernelGGL(rn_avgpool_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, n, hw, C, out);
+    else
+        hipLaunchKernelGGL(rn_avgpool_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)x, n, hw, C, out);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
+}
+
+// ---- the network ------------------------------------------------------------------------------------------------------
+// conv order of hipt_resnet_weights.convs: stem, then per block conv1, conv2, conv3 and (first block of a layer where the
+// shape changes) downsample -- the order of the reference's state dict.
+struct NetConv {
+    int cin, cout, k, stride, pad;
+};
+constexpr int RN_MAX_CONVS = 1 + 3 * 4 * 64;
+
+int net_convs(const hipt_resnet_weights* w, NetConv* out) {
+    int nc = 0, inplanes = 64;
+    out[nc++] = {3, 64, 7, 2, 3};
+    for (int L = 0; L < 3; ++L) {
+        const int planes = 64 << L, stride = L ? 2 : 1;
+        for (int b = 0; b < w->layers[L]; ++b) {
+            const int s = b ? 1 : stride;
+            out[nc++] = {inplanes, planes, 1, 1, 0};
+            out[nc++] = {planes, planes, 3, s, 1};
+            out[nc++] = {planes, planes * 4, 1, 1, 0};
+            if (b == 0 && (s != 1 || inplanes != planes * 4)) out[nc++] = {inplanes, planes * 4, 1, s, 0};
+            inplanes = planes * 4;
+        }
+    }
+    return nc;
+}
+
+int check_weights(const hipt_resnet_weights* w, NetConv* nc, int* count) {
+    HIPT_CHECK_ARG(w != nullptr, "resnet: null weights");
+    HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "resnet: bad dtype %d", w->dtype);
+    for (int L = 0; L < 3; ++L)
+        HIPT_CHECK_ARG(w->layers[L] >= 1 && w->layers[L] <= 64, "resnet: layers[%d]=%d outside [1, 64]", L, w->layers[L]);
+    *count = net_convs(w, nc);
+    HIPT_CHECK_ARG(w->n_convs == *count && w->convs != nullptr, "resnet: %d convs given, the layer counts need %d", w->n_convs, *count);
+    for (int i = 0; i < *count; ++i) {
+        const hipt_conv_bn& c = w->convs[i];
+        HIPT_CHECK_ARG(c.cin == nc[i].cin && c.cout == nc[i].cout && c.kh == nc[i].k && c.kw == nc[i].k,
+                       "resnet: conv %d is %dx%dx%dx%d, expected %dx%dx%dx%d", i, c.cout, c.cin, c.kh, c.kw, nc[i].cout, nc[i].cin,
+                       nc[i].k, nc[i].k);
+        HIPT_CHECK_ARG(c.weight && c.bn_weight && c.bn_bias && c.bn_mean && c.bn_var, "resnet: conv %d has a null tensor", i);
+    }
+    return HIPT_OK;
+}
+
+size_t conv_w_bytes(int cout, int cin, int k, int dtype) { return align256((size_t)cout * conv_kp(cin, k, k, dtype) * esize(dtype)); }
+size_t conv_b_bytes(int cout) { return align256((size_t)cout * 4); }
+
+// workspace: five NHWC activation buffers (A, B: block input / output, T1, T2: bottleneck interior, D: downsample), each
+// as large as the largest tensor it ever holds; T1 also holds the NHWC copy of the input.
+struct NetPlan {
+    size_t sz[5];
+};
+NetPlan plan(const hipt_resnet_weights* w, int n, int h, int wd) {
+    NetPlan pl = {};
+    const size_t es = esize(w->dtype);
+    auto upd = [&](int i, size_t elems) { pl.sz[i] = pl.sz[i] > elems * es ? pl.sz[i] : elems * es; };
+    const size_t N = (size_t)n;
+    upd(2, N * h * wd * 3);
+    int hh = conv_out(h, 7, 2, 3), ww = conv_out(wd, 7, 2, 3);
+    upd(0, N * hh * ww * 64);
+    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
+    upd(1, N * hh * ww * 64);
+    int inplanes = 64;
+    for (int L = 0; L < 3; ++L) {
+        const int planes = 64 << L;
+        for (int b = 0; b < w->layers[L]; ++b) {
+            const int s = b ? 1 : (L ? 2 : 1);
+            upd(2, N * hh * ww * planes);
+            const int h2 = conv_out(hh, 3, s, 1), w2 = conv_out(ww, 3, s, 1);
+            upd(3, N * h2 * w2 * planes);
+            upd(4, N * h2 * w2 * planes * 4);
+            upd(0, N * h2 * w2 * planes * 4);
+            upd(1, N * h2 * w2 * planes * 4);
+            hh = h2, ww = w2, inplanes = planes * 4;
+        }
+    }
+    (void)inplanes;
+    for (auto& s : pl.sz) s = align256(s);
+    return pl;
+}
+
+int check_shape(int n, int h, int w) {
+    HIPT_CHECK_ARG(n >= 1 && h > 0 && w > 0, "resnet: empty input n=%d h=%d w=%d", n, h, w);
+    if (h % 16 || w % 16 || h < 32 || w < 32) {
+        hipt_set_error("resnet: %d x %d input outside the envelope (height and width multiples of 16, at least 32)", h, w);
+        return HIPT_E_UNSUPPORTED;
+    }
+    if ((int64_t)n * (h / 2) * (w / 2) >= ((int64_t)1 << 30)) {
+        hipt_set_error("resnet: batch of %d images of %d x %d too large for one call", n, h, w);
+        return HIPT_E_UNSUPPORTED;
+    }
+    return HIPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hipt_conv_bn_packed_bytes(const hipt_conv_bn* c, int dtype) {
+    if (!c || c->cout <= 0 || c->cin <= 0 || c->kh <= 0 || c->kw <= 0 || (dtype != HIPT_F32 && dtype != HIPT_BF16)) return 0;
+    return (size_t)c->cout * conv_kp(c->cin, c->kh, c->kw, dtype) * esize(dtype);
+}
+
+int hipt_conv_bn_pack(const hipt_conv_bn* c, int dtype, void* w_out, float* bias_out, void* stream) {
+    HIPT_CHECK_ARG(hipt_conv_bn_packed_bytes(c, dtype) > 0, "conv_bn_pack: bad conv shape or dtype");
+    HIPT_CHECK_ARG(c->weight && c->bn_weight && c->bn_bias && c->bn_mean && c->bn_var && w_out && bias_out,
+                   "conv_bn_pack: null pointer");
+    const int K = c->cin * c->kh * c->kw, kp = conv_kp(c->cin, c->kh, c->kw, dtype);
+    const int64_t tot = (int64_t)c->cout * kp;
+    const unsigned blocks = (unsigned)((tot + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == HIPT_BF16)
+        hipLaunchKernelGGL(rn_pack_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, *c, K, kp, (bf16_t*)w_out, bias_out);
+    else
+        hipLaunchKernelGGL(rn_pack_kernel<float>, dim3(blocks), dim3(256), 0, st, *c, K, kp, (float*)w_out, bias_out);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
+}
+
+int hipt_conv2d(const void* x, int n, int h, int w, int cin, const void* w_packed, const float* bias, int cout, int kh, int kw,
+                int stride, int pad, const void* resid, int relu, void* out, int dtype, void* stream) {
+    ConvArgs a = {};
+    a.x = x, a.wt = w_packed, a.bias = bias, a.resid = resid, a.out = out;
+    a.n = n, a.h = h, a.w = w, a.cin = cin, a.cout = cout, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.relu = relu ? 1 : 0;
+    return run_conv(a, dtype, (hipStream_t)stream);
+}
+
+int hipt_resnet_maxpool(const void* x, int n, int h, int w, int c, void* out, int dtype, void* stream) {
+    HIPT_CHECK_ARG(x && out && n > 0 && h > 0 && w > 0 && c > 0 && (dtype == HIPT_F32 || dtype == HIPT_BF16), "resnet_maxpool: bad argument");
+    HIPT_CHECK_ARG(c % (16 / esize(dtype)) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0,
+                   "resnet_maxpool: channels must fill 16-byte chunks, pointers 16-byte aligned");
+    return run_maxpool(x, n, h, w, c, out, dtype, (hipStream_t)stream);
+}
+
+int hipt_resnet_avgpool(const void* x, int n, int hw, int c, float* out, int dtype, void* stream) {
+    HIPT_CHECK_ARG(x && out && n > 0 && hw > 0 && c > 0 && (dtype == HIPT_F32 || dtype == HIPT_BF16), "resnet_avgpool: bad argument");
+    return run_avgpool(x, n, hw, c, out, dtype, (hipStream_t)stream);
+}
+
+size_t hipt_resnet_packed_bytes(const hipt_resnet_weights* w) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    if (check_weights(w, nc, &count) != HIPT_OK) return 0;
+    size_t tot = 0;
+    for (int i = 0; i < count; ++i) tot += conv_w_bytes(nc[i].cout, nc[i].cin, nc[i].k, w->dtype) + conv_b_bytes(nc[i].cout);
+    return tot;
+}
+
+int hipt_resnet_pack_weights(const hipt_resnet_weights* w, void* packed, void* stream) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    const int rc = check_weights(w, nc, &count);
+    if (rc != HIPT_OK) return rc;
+    HIPT_CHECK_ARG(packed && ((uintptr_t)packed % 256) == 0, "resnet_pack_weights: packed image must be 256-byte aligned");
+    char* p = (char*)packed;
+    for (int i = 0; i < count; ++i) {
+        const size_t wb = conv_w_bytes(nc[i].cout, nc[i].cin, nc[i].k, w->dtype);
+        const int r = hipt_conv_bn_pack(&w->convs[i], w->dtype, p, (float*)(p + wb), stream);
+        if (r != HIPT_OK) return r;
+        p += wb + conv_b_bytes(nc[i].cout);
+    }
+    return HIPT_OK;
+}
+
+size_t hipt_resnet_workspace_bytes(const hipt_resnet_weights* w, int n, int h, int wd) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    if (check_weights(w, nc, &count) != HIPT_OK || n < 1 || h < 1 || wd < 1) return 0;
+    const NetPlan pl = plan(w, n, h, wd);
+    return pl.sz[0] + pl.sz[1] + pl.sz[2] + pl.sz[3] + pl.sz[4];
+}
+
+int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
+                        int n, int h, int wd, float* out, void* workspace, size_t ws_bytes, void* stream) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    int rc = check_weights(w, nc, &count);
+    if (rc != HIPT_OK) return rc;
+    rc = check_shape(n, h, wd);
+    if (rc != HIPT_OK) return rc;
+    HIPT_CHECK_ARG(input_kind == HIPT_RESNET_IN_F32 || input_kind == HIPT_RESNET_IN_U8 || input_kind == HIPT_RESNET_IN_U8_HWC,
+                   "resnet: bad input kind %d", input_kind);
+    HIPT_CHECK_ARG(packed && x && out && workspace && ((uintptr_t)packed % 256) == 0 && ((uintptr_t)workspace % 256) == 0 &&
+                       ((uintptr_t)out % 16) == 0,
+                   "resnet: null pointer, or packed / workspace not 256-byte aligned");
+    const NetPlan pl = plan(w, n, h, wd);
+    const size_t need = pl.sz[0] + pl.sz[1] + pl.sz[2] + pl.sz[3] + pl.sz[4];
+    if (ws_bytes < need) {
+        hipt_set_error("resnet: workspace %zu B too small (need %zu)", ws_bytes, need);
+        return HIPT_E_WORKSPACE;
+    }
+    const int dt = w->dtype;
+    hipStream_t st = (hipStream_t)stream;
+    char* buf[5];
+    buf[0] = (char*)workspace;
+    for (int i = 1; i < 5; ++i) buf[i] = buf[i - 1] + pl.sz[i - 1];
+    char *A = buf[0], *B = buf[1], *T1 = buf[2], *T2 = buf[3], *D = buf[4];
+
+    // input -> NHWC T in T1
+    NormArgs nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
+    if (norm)
+        for (int c = 0; c < 3; ++c) nm.mean[c] = norm[c], nm.std[c] = norm[3 + c];
+    {
+        const int64_t npx = (int64_t)n * h * wd;
+        rc = dt == HIPT_BF16 ? launch_input<bf16_t>(x, input_kind, npx, (int64_t)h * wd, nm, (bf16_t*)T1, st)
+                             : launch_input<float>(x, input_kind, npx, (int64_t)h * wd, nm, (float*)T1, st);
+        if (rc != HIPT_OK) return rc;
+    }
+    // byte offset of every conv's packed weight (its fp32 bias follows it)
+    size_t off[RN_MAX_CONVS], o = 0;
+    for (int i = 0; i < count; ++i) {
+        off[i] = o;
+        o += conv_w_bytes(nc[i].cout, nc[i].cin, nc[i].k, dt) + conv_b_bytes(nc[i].cout);
+    }
+    auto conv = [&](int i, const void* in, int hh, int ww, const void* resid, int relu, void* o, int* oh, int* ow) -> int {
+        const NetConv& c = nc[i];
+        const char* pw = (const char*)packed + off[i];
+        ConvArgs a = {};
+        a.x = in, a.wt = pw, a.bias = (const float*)(pw + conv_w_bytes(c.cout, c.cin, c.k, dt)), a.resid = resid, a.out = o;
+        a.n = n, a.h = hh, a.w = ww, a.cin = c.cin, a.cout = c.cout, a.kh = c.k, a.kw = c.k, a.stride = c.stride, a.pad = c.pad;
+        a.relu = relu;
+        const int r = run_conv(a, dt, st);
+        *oh = a.oh, *ow = a.ow;
+        return r;
+    };
+    int hh, ww;
+    if ((rc = conv(0, T1, h, wd, nullptr, 1, A, &hh, &ww)) != HIPT_OK) return rc;
+    if ((rc = run_maxpool(A, n, hh, ww, 64, B, dt, st)) != HIPT_OK) return rc;
+    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
+    char *cur = B, *nxt = A;
+    int ci = 1, C = 64;
+    for (int L = 0; L < 3; ++L) {
+        const int planes = 64 << L;
+        for (int b = 0; b < w->layers[L]; ++b) {
+            const int s = b ? 1 : (L ? 2 : 1);
+            const bool ds = b == 0 && (s != 1 || C != planes * 4);  // the rule of net_convs / _make_layer
+            int h1, w1, h2, w2, h3, w3;
+            if ((rc = conv(ci, cur, hh, ww, nullptr, 1, T1, &h1, &w1)) != HIPT_OK) return rc;
+            if ((rc = conv(ci + 1, T1, h1, w1, nullptr, 1, T2, &h2, &w2)) != HIPT_OK) return rc;
+            if (ds && (rc = conv(ci + 3, cur, hh, ww, nullptr, 0, D, &h3, &w3)) != HIPT_OK) return rc;
+            if ((rc = conv(ci + 2, T2, h2, w2, ds ? (const void*)D : (const void*)cur, 1, nxt, &h3, &w3)) != HIPT_OK) return rc;
+            ci += ds ? 4 : 3;
+            C = planes * 4, hh = h3, ww = w3;
+            char* t = cur;
+            cur = nxt, nxt = t;
+        }
+    }
+    return run_avgpool(cur, n, hh * ww, C, out, dt, st);
+}
+
+}  // extern "C"

@@ -7,7 +7,8 @@ The reference imports the hot-path classes by module path:
   utils/eval_utils.py:6).  ``install()`` registers this package's modules in ``sys.modules`` under
   exactly those names BEFORE the reference scripts import them; the reference's ``models`` package
   (which also holds model_mil.py / resnet_custom.py) is left alone — only the ``model_clam``
-  sub-module is replaced.  The alternative is the overlay files under ``shims/``.
+  sub-module is replaced.  ``install(resnet=True)`` also replaces ``models.resnet_custom`` (the ResNet-50 baseline route,
+  extract_features_fp.py:19,210-211).  The alternative is the overlay files under ``shims/``.
 """
 from __future__ import annotations
 
@@ -25,11 +26,17 @@ _MAP = {
 }
 
 
-def install(verbose: bool = False):
-    """Register the HIP-backed modules under the reference's import paths. Returns the mapping."""
+# opt-in (install(resnet=True)): the reference's ResNet-50 baseline extractor (extract_features_fp.py:19,210-211)
+_RESNET_MAP = {"models.resnet_custom": "resnet_custom"}
+_saved = {}  # ref name -> the module it replaced (restored by uninstall())
+
+
+def install(verbose: bool = False, resnet: bool = False):
+    """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
+    ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone."""
     done = {}
     pkg = __name__.rsplit(".", 1)[0]
-    for ref_name, ours in _MAP.items():
+    for ref_name, ours in list(_MAP.items()) + (list(_RESNET_MAP.items()) if resnet else []):
         mod = importlib.import_module(f"{pkg}.{ours}")
         parent_name = ref_name.split(".")[0]
         if parent_name not in sys.modules:
@@ -49,6 +56,8 @@ def install(verbose: bool = False):
                 parent.__path__ = []
                 parent.__hipt_amd_stub__ = True
                 sys.modules[parent_name] = parent
+        if ref_name in _RESNET_MAP and ref_name not in _saved:
+            _saved[ref_name] = sys.modules.get(ref_name)
         sys.modules[ref_name] = mod
         parent = sys.modules.get(parent_name)
         if parent is not None:
@@ -62,6 +71,19 @@ def install(verbose: bool = False):
 def uninstall():
     for ref_name in _MAP:
         sys.modules.pop(ref_name, None)
+    for ref_name in _RESNET_MAP:
+        if ref_name not in _saved:
+            continue
+        prev = _saved.pop(ref_name)
+        parent = sys.modules.get(ref_name.split(".")[0])
+        if prev is None:
+            sys.modules.pop(ref_name, None)
+            if parent is not None and hasattr(parent, ref_name.split(".")[1]):
+                delattr(parent, ref_name.split(".")[1])
+        else:
+            sys.modules[ref_name] = prev
+            if parent is not None:
+                setattr(parent, ref_name.split(".")[1], prev)
     for parent in ("HIPT_4K", "models"):
         if getattr(sys.modules.get(parent), "__hipt_amd_stub__", False):
             sys.modules.pop(parent, None)

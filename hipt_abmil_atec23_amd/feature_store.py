@@ -207,7 +207,11 @@ def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], f
     extract_features_fp.py:162-166): when ``model`` is a ``HIPT_4K`` on a HIP device and a loader batch is not there, the batch
     is copied host -> device AS IT ARRIVES, on a copy stream, into one of two gather buffers while the previous call computes (``_HostFeed``),
     and the features of call k are read back (on a stream of their own) only after call k + 1 has been enqueued -- the link, the GPU and the host loop overlap.  Same
-    gathered tensor, same kernels, same bits as with resident batches."""
+    gathered tensor, same kernels, same bits as with resident batches.
+
+    ``model`` may also be a ``ResNet_Baseline`` (``--model_type resnet50``: patches ``[B, 3, H, W]``, features ``[B, 1024]``): host
+    batches take the same copy-stream path (keyed on the model's ``weight_device``), and loader batches of any patch size are gathered
+    up to ``coalesce`` patches per call -- bit-exact, since every output row depends on its own patch only."""
     w = FeatureWriter(feat_dir, slide_id)
     return _extract(model, batches, [w], lambda regions, first: [model(regions)], coalesce)[0]
 
@@ -243,6 +247,11 @@ def extract_slide_augmented(model, batches: Iterable[Tuple[torch.Tensor, torch.T
     return _extract(model, batches, writers, run, coalesce)
 
 
+def _is_resnet(model) -> bool:
+    from .resnet_custom import ResNet_Baseline
+    return isinstance(model, ResNet_Baseline)
+
+
 def _extract(model, batches, writers, run, coalesce: int) -> list:
     """the loop of ``extract_slide``; ``run(regions, first)`` -> one feature tensor per writer for a call whose regions are
     regions ``first, first+1, ...`` of the slide (in loader order)"""
@@ -252,6 +261,9 @@ def _extract(model, batches, writers, run, coalesce: int) -> list:
     ncalls = [0]
     m256 = getattr(model, "model256", None)  # HIPT_4K: where its first-level ViT's weights live NOW (.to() may have moved it since construction)
     dev = getattr(m256, "weight_device", None) if m256 is not None else None
+    resnet = _is_resnet(model)
+    if resnet:
+        dev = model.weight_device
     dev = torch.device(dev) if dev is not None else None
     feed = [None]        # _HostFeed, made when the first host batch for a HIP model arrives
     pending: list = []   # [(features on the device, counts, coords)]: read back one call late
@@ -325,6 +337,8 @@ def _extract(model, batches, writers, run, coalesce: int) -> list:
     def gathers_bit_exactly(regions) -> bool:
         # whole 16-row fragments in every call (patch count a multiple of 16): the gathered call and the one-by-one call take the
         # same kernels and write the same bits; other region sizes are NOT gathered (they would agree to the bf16 bar only)
+        if resnet:
+            return True  # every output row of hipt_resnet_forward depends on its own patch only, whatever the batch
         if regions.dim() != 4:
             return False
         hw = regions.shape[2:] if regions.shape[1] == 3 else regions.shape[1:3]  # planar [R,3,W,H] or interleaved [R,W,H,3]

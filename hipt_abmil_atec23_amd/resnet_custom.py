@@ -1,0 +1,348 @@
+"""ResNet-50 baseline extractor: the reference's ``models/resnet_custom.py`` call surface on top of the gfx950 library.
+
+``ResNet_Baseline`` / ``Bottleneck_Baseline`` / ``resnet50_baseline`` / ``load_pretrained_weights`` keep the reference's
+constructor arguments, module names and state-dict keys (``conv1``, ``bn1``, ``layer{1,2,3}.{i}.{conv,bn}{1,2,3}``,
+``layer{1,2,3}.0.downsample.{0,1}``, ``num_batches_tracked`` included), so a torchvision ``resnet50`` checkpoint loads with
+``strict=False`` exactly as there (``layer4.*`` / ``fc.*`` unexpected, nothing missing).  The modules only HOLD
+parameters: ``forward`` runs the whole truncated network -- stem, maxpool, layer1..layer3, average pool -- as HIP kernels
+through ``libhipt_abmil.so`` (``hipt_resnet_forward``), eval-mode BatchNorm folded into the conv weights.  There is no
+CPU path and no train-mode path (BatchNorm would need batch statistics).
+
+Input: ``[B, 3, H, W]`` float, already normalised (the reference's ``eval_transforms``), or raw uint8 RGB, planar
+``[B, 3, H, W]`` or interleaved ``[B, H, W, 3]``, normalised on the device with :meth:`ResNet_Baseline.set_input_normalization`
+(ImageNet by default; ``(0.5, 0.5)`` for ``--use_transforms HIPT`` runs).  H and W: multiples of 16, at least 32.
+
+``compute_dtype``: ``'fp32'`` (exact-fp32 MFMA) or ``'bf16'`` (bf16 operands and stored activations, fp32 accumulate);
+``set_compute_dtype`` or the ``HIPT_AMD_DTYPE`` environment variable.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from urllib.parse import urlparse
+
+import torch
+import torch.nn as nn
+
+from . import _native as N
+from . import functional as Fn
+
+__all__ = ['ResNet_Baseline', 'Bottleneck_Baseline', 'resnet18_baseline', 'resnet50_baseline', 'load_pretrained_weights']
+
+model_urls = {
+    'resnet18': 'https://download.pytorch.org/models/resnet18-5c106cde.pth',
+    'resnet34': 'https://download.pytorch.org/models/resnet34-333f7ec4.pth',
+    'resnet50': 'https://download.pytorch.org/models/resnet50-19c8e357.pth',
+    'resnet50_histo': 'https://dox.uliege.be/index.php/s/kvABLtVuMxW8iJy/download',
+    'resnet101': 'https://download.pytorch.org/models/resnet101-5d3b4d8f.pth',
+    'resnet152': 'https://download.pytorch.org/models/resnet152-b121ed2d.pth',
+}
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def _default_dtype() -> str:
+    return os.environ.get("HIPT_AMD_DTYPE", "fp32")
+
+
+def _conv_bn_struct(conv: nn.Conv2d, bn: nn.BatchNorm2d, keep: list) -> N.ConvBN:
+    def f(t):
+        t = t.detach().float().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+
+    c = N.ConvBN()
+    c.weight, c.bn_weight, c.bn_bias = f(conv.weight), f(bn.weight), f(bn.bias)
+    c.bn_mean, c.bn_var = f(bn.running_mean), f(bn.running_var)
+    c.cout, c.cin, c.kh, c.kw = conv.weight.shape
+    c.bn_eps = float(bn.eps)
+    return c
+
+
+# ---- fine-grained units (NHWC tensors on a HIP device) -----------------------------------------------------------------
+def pack_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: int = N.HIPT_F32):
+    """(weight [cout, kp] in the compute dtype, bias [cout] fp32): ``bn(conv(.))`` in eval mode folded into one conv."""
+    dev = conv.weight.device
+    N.require_cuda(conv.weight, "pack_conv_bn")
+    keep = []
+    c = _conv_bn_struct(conv, bn, keep)
+    nbytes = N.lib().hipt_conv_bn_packed_bytes(C.byref(c), dtype)
+    if not nbytes:
+        raise ValueError(f"pack_conv_bn: unsupported conv {tuple(conv.weight.shape)}")
+    w = torch.empty(nbytes // (2 if dtype == N.HIPT_BF16 else 4), dtype=Fn.torch_dtype(dtype), device=dev).view(c.cout, -1)
+    b = torch.empty(c.cout, dtype=torch.float32, device=dev)
+    N.call("hipt_conv_bn_pack", C.byref(c), dtype, N.ptr(w), N.ptr(b), N.stream_ptr(dev))
+    return w, b
+
+
+def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, kernel_size: int, stride: int = 1, padding: int = 0,
+                resid: torch.Tensor = None, relu: bool = False, dtype: int = N.HIPT_F32) -> torch.Tensor:
+    """``relu?(conv2d(x) + bias (+ resid))`` on NHWC ``x [n, h, w, cin]`` with a packed weight (:func:`pack_conv_bn`); returns
+    ``[n, oh, ow, cout]`` in the compute dtype."""
+    N.require_cuda(x, "conv2d_nhwc")
+    x = x.detach().to(Fn.torch_dtype(dtype)).contiguous()
+    n, h, w, cin = x.shape
+    cout = w_packed.shape[0]
+    oh, ow = (h + 2 * padding - kernel_size) // stride + 1, (w + 2 * padding - kernel_size) // stride + 1
+    out = torch.empty((n, oh, ow, cout), dtype=x.dtype, device=x.device)
+    r = None if resid is None else resid.detach().to(x.dtype).contiguous()
+    if r is not None and tuple(r.shape) != tuple(out.shape):
+        raise ValueError(f"conv2d_nhwc: residual {tuple(r.shape)} does not match the output {tuple(out.shape)}")
+    N.call("hipt_conv2d", N.ptr(x), n, h, w, cin, N.ptr(w_packed), N.ptr(bias), cout, kernel_size, kernel_size, stride, padding,
+           N.ptr(r), int(relu), N.ptr(out), dtype, N.stream_ptr(x.device))
+    return out
+
+
+def maxpool_nhwc(x: torch.Tensor, dtype: int = N.HIPT_F32) -> torch.Tensor:
+    """``MaxPool2d(3, 2, 1)`` on NHWC ``x``."""
+    N.require_cuda(x, "maxpool_nhwc")
+    x = x.detach().to(Fn.torch_dtype(dtype)).contiguous()
+    n, h, w, c = x.shape
+    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=x.dtype, device=x.device)
+    N.call("hipt_resnet_maxpool", N.ptr(x), n, h, w, c, N.ptr(out), dtype, N.stream_ptr(x.device))
+    return out
+
+
+def avgpool_nhwc(x: torch.Tensor, dtype: int = N.HIPT_F32) -> torch.Tensor:
+    """``AdaptiveAvgPool2d(1)`` on NHWC ``x [n, h, w, c]`` -> ``[n, c]`` fp32."""
+    N.require_cuda(x, "avgpool_nhwc")
+    x = x.detach().to(Fn.torch_dtype(dtype)).contiguous()
+    n, h, w, c = x.shape
+    out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    N.call("hipt_resnet_avgpool", N.ptr(x), n, h * w, c, N.ptr(out), dtype, N.stream_ptr(x.device))
+    return out
+
+
+class Bottleneck_Baseline(nn.Module):
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super(Bottleneck_Baseline, self).__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * self.expansion, kernel_size=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        """One block on NCHW ``x`` (eval mode), unit by unit through ``hipt_conv2d`` in fp32; the network forward does not
+        come through here (it is one library call)."""
+        if self.training:
+            raise RuntimeError("Bottleneck_Baseline: BatchNorm in train() mode needs batch statistics (not implemented); call .eval()")
+        N.require_cuda(x, "Bottleneck_Baseline")
+        xh = x.detach().float().permute(0, 2, 3, 1).contiguous()
+        w1, b1 = pack_conv_bn(self.conv1, self.bn1)
+        w2, b2 = pack_conv_bn(self.conv2, self.bn2)
+        w3, b3 = pack_conv_bn(self.conv3, self.bn3)
+        t = conv2d_nhwc(xh, w1, b1, 1, relu=True)
+        t = conv2d_nhwc(t, w2, b2, 3, self.stride, 1, relu=True)
+        r = xh
+        if self.downsample is not None:
+            wd, bd = pack_conv_bn(self.downsample[0], self.downsample[1])
+            r = conv2d_nhwc(xh, wd, bd, 1, self.downsample[0].stride[0])
+        return conv2d_nhwc(t, w3, b3, 1, resid=r, relu=True).permute(0, 3, 1, 2)
+
+
+class _PackedResnet:
+    """Device-side image of one ResNet_Baseline for one compute dtype: BN-folded weights (``hipt_resnet_pack_weights``) plus
+    the ctypes structs that describe them.  Rebuilt when a parameter or running statistic changes."""
+
+    def __init__(self, model, code: int, dev):
+        keep = []
+        convs = [(model.conv1, model.bn1)]
+        for layer in (model.layer1, model.layer2, model.layer3):
+            for blk in layer:
+                convs += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)]
+                if blk.downsample is not None:
+                    convs.append((blk.downsample[0], blk.downsample[1]))
+        self.convs = (N.ConvBN * len(convs))(*[_conv_bn_struct(c, b, keep) for c, b in convs])
+        w = N.ResnetWeights()
+        w.dtype = code
+        for i, layer in enumerate((model.layer1, model.layer2, model.layer3)):
+            w.layers[i] = len(layer)
+        w.convs = C.cast(self.convs, C.POINTER(N.ConvBN))
+        w.n_convs = len(convs)
+        self.w = w
+        nbytes = N.lib().hipt_resnet_packed_bytes(C.byref(w))
+        if not nbytes:
+            raise ValueError("ResNet_Baseline: this layer configuration is outside the library's network "
+                             f"({N.lib().hipt_last_error().decode(errors='replace')})")
+        self.image = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        N.call("hipt_resnet_pack_weights", C.byref(w), N.ptr(self.image), N.stream_ptr(dev))
+        self.keep = keep  # the fp32 sources stay alive until the packing kernels (enqueued above) have read them
+
+    @property
+    def ref(self):
+        return C.byref(self.w)
+
+
+class ResNet_Baseline(nn.Module):
+
+    def __init__(self, block, layers):
+        self.inplanes = 64
+        super(ResNet_Baseline, self).__init__()
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._make_layer(block, 64, layers[0])
+        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        self._compute_dtype = _default_dtype()
+        self._norm = IMAGENET_MEAN + IMAGENET_STD
+        self._packed = {}  # device -> (key, _PackedResnet): one image per device (nn.DataParallel replicas share this dict)
+        self._warned_grad = False
+
+    def _make_layer(self, block, planes, blocks, stride=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(
+                nn.Conv2d(self.inplanes, planes * block.expansion, kernel_size=1, stride=stride, bias=False),
+                nn.BatchNorm2d(planes * block.expansion),
+            )
+        layers = [block(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes * block.expansion
+        for _ in range(1, blocks):
+            layers.append(block(self.inplanes, planes))
+        return nn.Sequential(*layers)
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_packed"] = {}
+        return d
+
+    # ---- settings ---------------------------------------------------------------------------------------------------
+    def set_compute_dtype(self, name: str):
+        N.dtype_code(name)
+        self._compute_dtype = "bf16" if name in ("bf16", "bfloat16") else "fp32"
+        return self
+
+    @property
+    def compute_dtype(self) -> str:
+        return self._compute_dtype
+
+    def set_input_normalization(self, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        """Per-channel ``Normalize(mean, std)`` applied on the device to uint8 input (after ``/ 255``); fp32 input is taken as
+        already normalised.  A scalar applies to all three channels (``--use_transforms HIPT``: ``0.5, 0.5``)."""
+        mean = tuple(float(v) for v in (mean if hasattr(mean, "__len__") else (mean,) * 3))
+        std = tuple(float(v) for v in (std if hasattr(std, "__len__") else (std,) * 3))
+        if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
+            raise ValueError(f"set_input_normalization: need 3 means and 3 non-zero stds, got {mean}, {std}")
+        self._norm = mean + std
+        return self
+
+    # ---- weights ------------------------------------------------------------------------------------------------------
+    @property
+    def weight_device(self):
+        """Device the weights live on; survives DataParallel replication (``next(self.parameters())`` does not)."""
+        return self.conv1.weight.device
+
+    def _tensors(self):
+        """Parameters and BN running statistics (both enter the folded image).  A ``nn.DataParallel`` replica keeps its
+        parameters in ``_former_parameters`` (torch/nn/parallel/replicate.py; extract_features_fp.py:217-218 wraps the model)."""
+        ps = list(self.parameters())
+        if not ps:
+            ps = [t for m in self.modules() for t in getattr(m, "_former_parameters", {}).values() if t is not None]
+        return ps + [b for b in self.buffers() if b.is_floating_point()]
+
+    def _version_key(self):
+        return tuple((t.data_ptr(), t._version) for t in self._tensors())
+
+    def _check_inference_only(self):
+        if self.training:
+            raise RuntimeError("ResNet_Baseline HIP forward: BatchNorm in train() mode needs batch statistics (inference kernels "
+                               "only); call .eval()")
+        if torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
+            import warnings
+            warnings.warn("HIP ResNet_Baseline forward returns tensors without grad_fn: no gradient flows into the extractor "
+                          "weights (the reference uses it as a frozen feature extractor)", stacklevel=3)
+            self._warned_grad = True
+
+    def _packed_for(self, dev) -> _PackedResnet:
+        self._check_inference_only()
+        code = N.dtype_code(self._compute_dtype)
+        key = (code, self._version_key())
+        pk = self._packed.get(dev)
+        if pk is None or pk[0] != key:
+            N.same_device(type(self).__name__, dev, *self._tensors())
+            pk = (key, _PackedResnet(self, code, dev))
+            self._packed[dev] = pk
+        return pk[1]
+
+    # ---- forward ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _input_kind(x: torch.Tensor) -> int:
+        if x.dtype == torch.uint8:
+            return N.RESNET_IN_U8_HWC if (x.dim() == 4 and x.shape[-1] == 3 and x.shape[1] != 3) else N.RESNET_IN_U8
+        return N.RESNET_IN_F32
+
+    def forward(self, x):
+        """``[B, 1024]`` fp32 features of ``[B, 3, H, W]`` float (normalised) or uint8 (``[B, 3, H, W]`` / ``[B, H, W, 3]``)."""
+        N.require_cuda(x, type(self).__name__)
+        kind = self._input_kind(x)
+        if x.dim() != 4 or (x.shape[-1] if kind == N.RESNET_IN_U8_HWC else x.shape[1]) != 3:
+            raise ValueError(f"ResNet_Baseline: expected [B,3,H,W] (or uint8 [B,H,W,3]) images, got {tuple(x.shape)}")
+        dev = x.device
+        N.same_device(type(self).__name__, self.weight_device, x)
+        pk = self._packed_for(dev)
+        x = x.detach().contiguous() if kind != N.RESNET_IN_F32 else x.detach().float().contiguous()
+        B = x.shape[0]
+        H, W = (x.shape[1], x.shape[2]) if kind == N.RESNET_IN_U8_HWC else (x.shape[2], x.shape[3])
+        out = torch.empty((B, 4 * 256), dtype=torch.float32, device=dev)
+        need = N.lib().hipt_resnet_workspace_bytes(pk.ref, B, H, W)
+        # one scratch per stream: two streams driving the model at once never share activations
+        ws = Fn.workspace(dev, need, slot=("resnet", torch.cuda.current_stream(dev).cuda_stream))
+        norm = (C.c_float * 6)(*self._norm)
+        N.call("hipt_resnet_forward", pk.ref, N.ptr(pk.image), N.ptr(x), kind, C.cast(norm, C.c_void_p), B, H, W, N.ptr(out),
+               N.ptr(ws), ws.numel(), N.stream_ptr(dev))
+        return out
+
+
+def resnet18_baseline(pretrained=False, dataset='ImageNet'):
+    """The reference builds torchvision's ResNet-18 here (models/resnet_custom.py:resnet18_baseline); that network is not
+    part of this library."""
+    raise NotImplementedError("resnet18_baseline: torchvision's ResNet-18 is not implemented by hipt_abmil_atec23_amd; "
+                              "use resnet50_baseline (or --model_type resnet50 / HIPT_4K)")
+
+
+def resnet50_baseline(pretrained=False, dataset='ImageNet'):
+    """Constructs a Modified ResNet-50 model.
+    Args:
+        pretrained (bool): If True, loads the ImageNet (or 'Histo') checkpoint from the local torch hub cache
+    """
+    model = ResNet_Baseline(Bottleneck_Baseline, [3, 4, 6, 3])
+    if pretrained:
+        if dataset == 'ImageNet':
+            model = load_pretrained_weights(model, 'resnet50')
+        elif dataset == 'Histo':
+            model = load_pretrained_weights(model, 'resnet50_histo')
+    return model
+
+
+def cached_checkpoint_path(name: str) -> str:
+    """Where ``torch.utils.model_zoo.load_url(model_urls[name])`` keeps its download: ``<torch.hub.get_dir()>/checkpoints/<file>``."""
+    return os.path.join(torch.hub.get_dir(), "checkpoints", os.path.basename(urlparse(model_urls[name]).path))
+
+
+def load_pretrained_weights(model, name):
+    """The reference downloads through ``model_zoo.load_url``; this reads the file that call would have cached and never
+    touches the network.  Missing file: ``FileNotFoundError`` naming the path to put it at."""
+    path = cached_checkpoint_path(name)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"pretrained '{name}' weights not found at {path}; this package never downloads: place the "
+                                f"checkpoint of {model_urls[name]} there (or load a state dict with model.load_state_dict(sd, strict=False))")
+    pretrained_dict = torch.load(path, map_location="cpu")
+    model.load_state_dict(pretrained_dict, strict=False)
+    return model

@@ -149,6 +149,41 @@ def clam_param_specs(size=(384, 128, 64), n_classes: int = 2, dropout: bool = Fa
     return sp
 
 
+def resnet_conv_bn_names(layers=(3, 4, 6)):
+    """``[(conv, bn, cout, cin, k)]`` of ResNet_Baseline (models/resnet_custom.py) in state-dict order: stem, then per block
+    conv1..conv3 and (first block of a layer whose shape changes) downsample."""
+    out = [("conv1", "bn1", 64, 3, 7)]
+    inplanes = 64
+    for L, nb in enumerate(layers):
+        planes = 64 << L
+        for b in range(nb):
+            p = f"layer{L + 1}.{b}."
+            out += [(p + "conv1", p + "bn1", planes, inplanes, 1), (p + "conv2", p + "bn2", planes, planes, 3),
+                    (p + "conv3", p + "bn3", planes * 4, planes, 1)]
+            if b == 0 and (L > 0 or inplanes != planes * 4):
+                out.append((p + "downsample.0", p + "downsample.1", planes * 4, inplanes, 1))
+            inplanes = planes * 4
+    return out
+
+
+def resnet_param_specs(layers=(3, 4, 6)):
+    """``name -> (shape, scale, offset)`` of the LEARNABLE tensors of ResNet_Baseline: conv weights uniform with the spread
+    of kaiming_normal_(mode='fan_out', nonlinearity='relu') (models/resnet_custom.py:ResNet_Baseline.__init__), BatchNorm
+    affine terms around (1, 0).  The running statistics are data (tests/golden/resnet50_baseline.npz), not a spec."""
+    sp = OrderedDict()
+    for conv, bn, cout, cin, k in resnet_conv_bn_names(layers):
+        sp[conv + ".weight"] = ((cout, cin, k, k), math.sqrt(6.0 / (cout * k * k)), 0.0)
+        sp[bn + ".weight"] = ((cout,), 0.1, 1.0)
+        sp[bn + ".bias"] = ((cout,), 0.05, 0.0)
+    return sp
+
+
+def hash_u8_np(shape, seed: int) -> np.ndarray:
+    """uint8 array (the top byte of the hash): synthetic RGB pixels."""
+    n = int(np.prod(shape)) if len(shape) else 1
+    return (hash_u32_np(n, seed) >> np.uint32(24)).astype(np.uint8).reshape(shape)
+
+
 def make_params_np(specs, base_seed: int = 0):
     """Materialise a spec dict as fp32 numpy arrays."""
     return OrderedDict((k, hash_uniform_np(shape, name_seed(k, base_seed), sc, off))

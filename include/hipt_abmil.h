@@ -451,6 +451,66 @@ size_t hipt_augment_workspace_bytes(int n, int rows, int cols);
 int hipt_augment_regions(const uint8_t* src, int interleaved, int n, int rows, int cols, const hipt_augment_params* params,
                          uint8_t* dst, void* workspace, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * ResNet-50 baseline feature extractor (models/resnet_custom.py:ResNet_Baseline, resnet50_baseline; the default route of
+ * extract_features_fp.py:187,210-211): stem conv 7x7/2 + BN + ReLU, maxpool 3x3/2, layer1..layer3 of Bottleneck_Baseline
+ * (stride on conv2), AdaptiveAvgPool2d(1) -> [n, 1024] fp32.  Eval-mode BatchNorm only (running statistics), folded into
+ * the conv weights at pack time.  Activations between layers are NHWC in the compute dtype.
+ * ---------------------------------------------------------------------------------- */
+enum { HIPT_RESNET_IN_F32 = 0, HIPT_RESNET_IN_U8 = 1, HIPT_RESNET_IN_U8_HWC = 2 };
+
+/* One Conv2d(bias=False) + BatchNorm2d pair: device fp32 tensors of torch's layouts (weight [cout, cin, kh, kw]). */
+typedef struct hipt_conv_bn {
+    const float* weight;
+    const float* bn_weight;
+    const float* bn_bias;
+    const float* bn_mean;   /* running_mean */
+    const float* bn_var;    /* running_var  */
+    int32_t cout, cin, kh, kw;
+    float   bn_eps;
+    int32_t reserved;
+} hipt_conv_bn;
+
+/* The network: `convs` is a HOST array of n_convs records in state-dict order -- conv1/bn1, then per block conv1/bn1,
+ * conv2/bn2, conv3/bn3 and, in the first block of a layer whose shape changes, downsample.0/downsample.1.
+ * layers[]: blocks of layer1..layer3 (ResNet_Baseline's layers[0..2]; layers[3] is never built by the reference). */
+typedef struct hipt_resnet_weights {
+    int32_t dtype;          /* HIPT_F32 / HIPT_BF16: GEMM operands and stored activations */
+    int32_t layers[3];
+    const hipt_conv_bn* convs;
+    int32_t n_convs;
+    int32_t reserved;
+} hipt_resnet_weights;
+
+/* Bytes of the packed image (every conv's BN-folded weight in the compute dtype plus its fp32 bias); 0 if w is invalid. */
+size_t hipt_resnet_packed_bytes(const hipt_resnet_weights* w);
+/* Fill `packed` (256-byte aligned, hipt_resnet_packed_bytes) from w's tensors; enqueued on stream. */
+int hipt_resnet_pack_weights(const hipt_resnet_weights* w, void* packed, void* stream);
+size_t hipt_resnet_workspace_bytes(const hipt_resnet_weights* w, int n, int h, int wd);
+/* out[n, 1024] fp32 = ResNet_Baseline.forward(x) for n images of h x wd pixels (h, wd multiples of 16, >= 32; else
+ * HIPT_E_UNSUPPORTED).  input_kind HIPT_RESNET_IN_F32: x fp32 [n, 3, h, wd], already normalised (the reference's input);
+ * HIPT_RESNET_IN_U8 / _U8_HWC: raw RGB bytes [n, 3, h, wd] / [n, h, wd, 3], normalised on the device as ToTensor +
+ * Normalize, (x / 255 - mean_c) / std_c in fp32 (bit-identical to feeding the fp32 tensor torch computes from the same
+ * bytes).  norm: HOST array {mean[3], std[3]}, NULL = ImageNet (0.485, 0.456, 0.406) / (0.229, 0.224, 0.225).
+ * packed and workspace 256-byte aligned.  Every output row depends on its own image only (no cross-image reduction). */
+int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
+                        int n, int h, int wd, float* out, void* workspace, size_t ws_bytes, void* stream);
+
+/* The units, for tests and composition.  hipt_conv_bn_pack: one conv's BN fold into w_out [cout, kp] (compute dtype,
+ * (ky, kx, ci) order, K = cin*kh*kw zero-padded to kp = multiple of 64 (bf16) / 32 (fp32); hipt_conv_bn_packed_bytes
+ * gives cout*kp*element size) and bias_out [cout] fp32. */
+size_t hipt_conv_bn_packed_bytes(const hipt_conv_bn* c, int dtype);
+int hipt_conv_bn_pack(const hipt_conv_bn* c, int dtype, void* w_out, float* bias_out, void* stream);
+/* out[n, oh, ow, cout] = relu?(conv(x[n, h, w, cin], w_packed) + bias (+ resid[n, oh, ow, cout])), NHWC, all tensors in
+ * dtype except the fp32 bias; cout a multiple of 64; cin a multiple of 64 (bf16) / 32 (fp32), or cin*kh*kw <= 1024
+ * (gathered, the stem's Cin = 3).  Padding taps read zeros.  16-byte aligned pointers. */
+int hipt_conv2d(const void* x, int n, int h, int w, int cin, const void* w_packed, const float* bias, int cout, int kh, int kw,
+                int stride, int pad, const void* resid, int relu, void* out, int dtype, void* stream);
+/* MaxPool2d(3, 2, 1) on NHWC x[n, h, w, c] -> out[n, (h+1)/2, (w+1)/2, c]; c a multiple of 8 (bf16) / 4 (fp32). */
+int hipt_resnet_maxpool(const void* x, int n, int h, int w, int c, void* out, int dtype, void* stream);
+/* AdaptiveAvgPool2d(1) on NHWC x[n, hw, c] -> out[n, c] fp32, each sum in pixel order. */
+int hipt_resnet_avgpool(const void* x, int n, int hw, int c, float* out, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
