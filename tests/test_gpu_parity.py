@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import vit_bf16_ref as R
 from conftest import golden
 from hipt_abmil_atec23_amd import _native as N
 from hipt_abmil_atec23_amd import functional as Fn
@@ -568,15 +569,50 @@ def test_vit256_embedding_emits_first_block_operands(vit256, hipt, monkeypatch):
         hipt.set_compute_dtype("fp32")
 
 
-def _to_image(x):
-    """[M, 384] row-major -> activation image (include/hipt_abmil.h, hipt_vit_attention_unit): fragment F, column chunk c, lane 16 g + i, 8 elements"""
-    m = x.shape[0]
-    return x.view(m // 16, 16, 12, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(m, 384)
+# hipt_vit_attention_unit against tests/vit_bf16_ref.py's emulation (q | k | v, the unnormalised probabilities and the output rounded to
+# bf16 where the kernels round them): rel-L2 of the rows other than [CLS], and of the [CLS] rows, which the fused kernel computes by
+# another route (the side GEMM's q and the per-wave partial softmax merge: its probabilities are rounded to bf16 relative to each wave's
+# own maximum, not the row's, an independent rounding of every P element).  2 x the largest measurement over the cases (printed with -s):
+# rows 1.77e-4 (outlier weights 2.28e-4); [CLS] fused 1.96e-3 (1.12e-3), two kernels 1.82e-4 (8.6e-5).
+ATT_BARS = {"rows": 3.5e-4, "cls": {1: 3.9e-3, 0: 3.6e-4}}
+ATT_BARS_OUTLIER = {"rows": 4.5e-4, "cls": {1: 2.2e-3, 0: 1.7e-4}}
 
 
-def _from_image(img):
-    m = img.shape[0]
-    return img.view(m // 16, 12, 4, 16, 8).permute(0, 3, 1, 2, 4).contiguous().view(m, 384)
+def _attention_unit_run(pk, blk, x, nseq, fused, ws):
+    """one hipt_vit_attention_unit launch on bf16 rows x into a buffer with 32 rows of NaN behind it (which must stay NaN) -> row-major fp32"""
+    M = nseq * 257
+    o = torch.full((M + 32, 384), float("nan"), dtype=torch.bfloat16, device=DEV)
+    before = N.calls
+    N.call("hipt_vit_attention_unit", pk.ref, blk, N.ptr(R.to_image(x)), nseq, N.ptr(o), fused, N.ptr(ws), ws.numel(), N.stream_ptr(torch.device(DEV)))
+    torch.cuda.synchronize()
+    assert N.calls == before + 1
+    assert torch.equal(o[M:].view(torch.int16), torch.full_like(o[M:], float("nan")).view(torch.int16)), "write past row M"
+    return R.from_image(o[:M]).float()
+
+
+def _attention_unit_vs_emulation(tag, m, pk, blk, x, nseq, outs, ws, bars):
+    M = nseq * 257
+    p = R.block_params(m, blk)
+    emu = R.attention_unit(x.double(), p, nseq)
+    cls = torch.zeros(M, dtype=torch.bool, device=DEV)
+    cls[::257] = True
+    for fused, name, o in zip((1, 0), ("fused", "two kernels"), outs):
+        e_rows, e_cls = R.errors(o[~cls], emu[~cls]), R.errors(o[cls], emu[cls])
+        print(f"{tag}, {name} vs bf16 emulation: rows rel-L2 {e_rows['rel']:.2e} (bar {bars['rows']:.1e}) max {e_rows['max']:.2e}; "
+              f"[CLS] rel-L2 {e_cls['rel']:.2e} (bar {bars['cls'][fused]:.1e}) max {e_cls['max']:.2e}")
+        assert e_rows["rel"] < bars["rows"] and e_cls["rel"] < bars["cls"][fused], name
+    # sensitivity: the scale applied twice, one key tile masked -- each >= 3 x beyond the bars (rows and [CLS] rows)
+    for v in ("scale2", "mask_tile"):
+        d = R.attention_unit(x.double(), p, nseq, variant=v)
+        worst = min(R.errors(d[~cls], emu[~cls])["rel"] / bars["rows"], R.errors(d[cls], emu[cls])["rel"] / max(bars["cls"].values()))
+        print(f"   variant {v}: {worst:.1f} x the bar")
+        assert worst >= 3.0, v
+    # a patch's bits do not depend on the call: the first 16 patches again in front of all nseq (another nseq, other positions)
+    x2 = torch.cat([x[:16 * 257], x])
+    for fused, o in zip((1, 0), outs):
+        o2 = _attention_unit_run(pk, blk, x2, nseq + 16, fused, ws if ws.numel() >= N.lib().hipt_vit_workspace_bytes(pk.ref, nseq + 16)
+                                 else torch.empty(N.lib().hipt_vit_workspace_bytes(pk.ref, nseq + 16), dtype=torch.uint8, device=DEV))
+        assert torch.equal(o2[:16 * 257], o[:16 * 257]) and torch.equal(o2[16 * 257:], o), fused
 
 
 @pytest.mark.parametrize("nseq", [16, 48, 144, 528])  # (>= 128 patches: the one-wave-per-SIMD kernel; 528: two or three patches per workgroup)
@@ -593,20 +629,15 @@ def test_attention_unit_fused_kernel_vs_torch_and_two_kernels(vit256, nseq):
         blk = 3
         M = nseq * 257
         x = (synth.hash_uniform_torch((M, 384), 57 + nseq, device=DEV) * 2.0).bfloat16()  # (scores of std ~2: a peaky softmax, sensitive to any mis-ordered operand)
-        xi = _to_image(x)
         need = N.lib().hipt_vit_workspace_bytes(pk.ref, nseq)
         ws = Fn.workspace(torch.device(DEV), need)
-        outs = []
-        for fused in (1, 0):
-            o = torch.full((M, 384), float("nan"), dtype=torch.bfloat16, device=DEV)
-            N.call("hipt_vit_attention_unit", pk.ref, blk, N.ptr(xi), nseq, N.ptr(o), fused, N.ptr(ws), ws.numel(), N.stream_ptr(torch.device(DEV)))
-            torch.cuda.synchronize()
-            outs.append(_from_image(o).float())
+        outs = [_attention_unit_run(pk, blk, x, nseq, fused, ws) for fused in (1, 0)]
         att = vit256.blocks[blk].attn
         wq = att.qkv.weight.detach().bfloat16().float()
         qkv = (x.float() @ wq.t() + att.qkv.bias.detach().float()).bfloat16().float().view(nseq, 257, 3, 6, 64).permute(2, 0, 3, 1, 4)
         pr = torch.softmax((qkv[0] @ qkv[1].transpose(-1, -2)) * att.scale, dim=-1)
         ref = (pr @ qkv[2]).transpose(1, 2).reshape(M, 384)
+        _attention_unit_vs_emulation(f"attention unit, {nseq} patches", vit256, pk, blk, x, nseq, outs, ws, ATT_BARS)
     finally:
         vit256.set_compute_dtype("fp32")
     rmax = float(ref.abs().max())
@@ -1267,19 +1298,14 @@ def test_attention_unit_outlier_weights_large_logits(vit256_outlier, blk):
         big = torch.from_numpy(synth.hash_u32_np(384, 5).astype(np.int64) % 50 == 0).to(DEV)
         x[:, big] *= 12.0
         x = x.bfloat16()
-        xi = _to_image(x)
         ws = Fn.workspace(torch.device(DEV), N.lib().hipt_vit_workspace_bytes(pk.ref, nseq))
-        outs = []
-        for fused in (1, 0):
-            o = torch.full((M, 384), float("nan"), dtype=torch.bfloat16, device=DEV)
-            N.call("hipt_vit_attention_unit", pk.ref, blk, N.ptr(xi), nseq, N.ptr(o), fused, N.ptr(ws), ws.numel(), N.stream_ptr(torch.device(DEV)))
-            torch.cuda.synchronize()
-            outs.append(_from_image(o).float())
+        outs = [_attention_unit_run(pk, blk, x, nseq, fused, ws) for fused in (1, 0)]
         att = m.blocks[blk].attn
         wq = att.qkv.weight.detach().bfloat16().float()
         qkv = (x.float() @ wq.t() + att.qkv.bias.detach().float()).bfloat16().float().view(nseq, 257, 3, 6, 64).permute(2, 0, 3, 1, 4)
         lg = (qkv[0] @ qkv[1].transpose(-1, -2)) * att.scale
         ref = (torch.softmax(lg, dim=-1) @ qkv[2]).transpose(1, 2).reshape(M, 384)
+        _attention_unit_vs_emulation(f"attention unit, outlier block {blk}", m, pk, blk, x, nseq, outs, ws, ATT_BARS_OUTLIER)
     finally:
         m.set_compute_dtype("fp32")
     rmax = float(ref.abs().max())
