@@ -25,6 +25,10 @@ _LAZY = {
     "install": ("dropin", "install"), "build_native": ("_native", "build"),
     "FeatureWriter": ("feature_store", "FeatureWriter"), "extract_slide": ("feature_store", "extract_slide"),
     "load_bag": ("feature_store", "load_bag"), "load_coords": ("feature_store", "load_coords"),
+    # DRAS-MIL attention-guided sampling inference (eval.py --sampling)
+    "SamplingConfig": ("sampling", "SamplingConfig"), "dras_eval_slide": ("sampling", "dras_eval_slide"),
+    "knn": ("sampling", "knn"), "update_sampling_weights": ("sampling", "update_sampling_weights"),
+    "generate_sample_idxs": ("sampling", "generate_sample_idxs"), "resnet_patch_features": ("sampling", "resnet_patch_features"),
 }
 
 

@@ -72,6 +72,8 @@ class ResnetWeights(C.Structure):
 
 
 RESNET_IN_F32, RESNET_IN_U8, RESNET_IN_U8_HWC = 0, 1, 2
+KNN_SPATIAL, KNN_TEXTURAL = 0, 1
+SAMPLING_MAX, SAMPLING_NEWEST, SAMPLING_AVERAGE = 0, 1, 2
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -141,6 +143,10 @@ SIGNATURES = {
     "hipt_conv2d": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
     "hipt_resnet_maxpool": (_i, [_p, _i, _i, _i, _i, _p, _i, _p]),
     "hipt_resnet_avgpool": (_i, [_p, _i, _i, _i, _p, _i, _p]),
+    "hipt_knn_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hipt_knn": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "hipt_sampling_update_workspace_bytes": (_sz, [_i]),
+    "hipt_sampling_update": (_i, [_p, _i, _p, _i, _p, _i, _i, _p, _i, C.c_double, _i, _p, _p, _sz, _p]),
 }
 
 _lib = None

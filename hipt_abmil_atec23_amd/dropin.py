@@ -8,7 +8,10 @@ The reference imports the hot-path classes by module path:
   exactly those names BEFORE the reference scripts import them; the reference's ``models`` package
   (which also holds model_mil.py / resnet_custom.py) is left alone — only the ``model_clam``
   sub-module is replaced.  ``install(resnet=True)`` also replaces ``models.resnet_custom`` (the ResNet-50 baseline route,
-  extract_features_fp.py:19,210-211).  The alternative is the overlay files under ``shims/``.
+  extract_features_fp.py:19,210-211).  ``install(sampling=True)`` makes ``utils.sampling_utils.generate_sample_idxs`` and
+  ``update_sampling_weights`` (what ``summary_sampling`` calls, utils/eval_utils.py:18,298-467) this package's: where the
+  reference's module imports, the two names are rebound ON it (eval_utils.py takes its plotting helpers from the same module);
+  where it does not, a module is registered whose plotting names raise.  The alternative is the overlay files under ``shims/``.
 """
 from __future__ import annotations
 
@@ -31,10 +34,78 @@ _RESNET_MAP = {"models.resnet_custom": "resnet_custom"}
 _saved = {}  # ref name -> the module it replaced (restored by uninstall())
 
 
-def install(verbose: bool = False, resnet: bool = False):
+_SAMPLING_MOD = "utils.sampling_utils"
+_SAMPLING_NAMES = {"generate_sample_idxs": "generate_sample_idxs", "update_sampling_weights": "update_sampling_weights_np"}
+_PLOTTING = ("plot_sampling", "plot_sampling_gif", "plot_weighting", "plot_weighting_gif", "generate_features_array")
+
+
+def _install_sampling(verbose: bool):
+    """Bind the two sampling functions under ``utils.sampling_utils`` (opt-in)."""
+    from . import sampling
+    if _SAMPLING_MOD in _saved:
+        return
+    mod = None
+    try:
+        if importlib.util.find_spec(_SAMPLING_MOD) is not None:
+            mod = importlib.import_module(_SAMPLING_MOD)   # needs openslide / matplotlib, as the reference does
+    except Exception:   # no reference checkout on sys.path, or one of its imports is missing
+        mod = None
+    if mod is not None and not getattr(mod, "__hipt_amd_stub__", False):
+        _saved[_SAMPLING_MOD] = ("rebound", {n: getattr(mod, n) for n in _SAMPLING_NAMES})
+    else:
+        _saved[_SAMPLING_MOD] = ("stub", sys.modules.get(_SAMPLING_MOD))
+        mod = types.ModuleType(_SAMPLING_MOD)
+        mod.__hipt_amd_stub__ = True
+
+        def _absent(name):
+            def fn(*a, **k):
+                raise RuntimeError(f"utils.sampling_utils.{name}: the reference's module is not importable here (no checkout on "
+                                   f"sys.path, or openslide / matplotlib missing); hipt_abmil_atec23_amd provides the sampling functions only")
+            return fn
+        for name in _PLOTTING:
+            setattr(mod, name, _absent(name))
+        if "utils" not in sys.modules:
+            parent = types.ModuleType("utils")
+            parent.__path__ = []
+            parent.__hipt_amd_stub__ = True
+            sys.modules["utils"] = parent
+        sys.modules[_SAMPLING_MOD] = mod
+        setattr(sys.modules["utils"], "sampling_utils", mod)
+    for ref_name, ours in _SAMPLING_NAMES.items():
+        setattr(mod, ref_name, getattr(sampling, ours))
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_SAMPLING_MOD}.{{{', '.join(_SAMPLING_NAMES)}}} -> {sampling.__name__} ({_saved[_SAMPLING_MOD][0]})")
+
+
+def _uninstall_sampling():
+    if _SAMPLING_MOD not in _saved:
+        return
+    how, prev = _saved.pop(_SAMPLING_MOD)
+    if how == "rebound":
+        for n, fn in prev.items():
+            setattr(sys.modules[_SAMPLING_MOD], n, fn)
+        return
+    parent = sys.modules.get("utils")
+    if prev is None:
+        sys.modules.pop(_SAMPLING_MOD, None)
+        if parent is not None and hasattr(parent, "sampling_utils"):
+            delattr(parent, "sampling_utils")
+    else:
+        sys.modules[_SAMPLING_MOD] = prev
+        if parent is not None:
+            parent.sampling_utils = prev
+    if getattr(parent, "__hipt_amd_stub__", False):
+        sys.modules.pop("utils", None)
+
+
+def install(verbose: bool = False, resnet: bool = False, sampling: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
-    ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone."""
+    ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
+    ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling)."""
     done = {}
+    if sampling:
+        _install_sampling(verbose)
+        done[_SAMPLING_MOD] = f"{__name__.rsplit('.', 1)[0]}.sampling"
     pkg = __name__.rsplit(".", 1)[0]
     for ref_name, ours in list(_MAP.items()) + (list(_RESNET_MAP.items()) if resnet else []):
         mod = importlib.import_module(f"{pkg}.{ours}")
@@ -69,6 +140,7 @@ def install(verbose: bool = False, resnet: bool = False):
 
 
 def uninstall():
+    _uninstall_sampling()
     for ref_name in _MAP:
         sys.modules.pop(ref_name, None)
     for ref_name in _RESNET_MAP:

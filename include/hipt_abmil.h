@@ -511,6 +511,44 @@ int hipt_resnet_maxpool(const void* x, int n, int h, int w, int c, void* out, in
 /* AdaptiveAvgPool2d(1) on NHWC x[n, hw, c] -> out[n, c] fp32, each sum in pixel order. */
 int hipt_resnet_avgpool(const void* x, int n, int hw, int c, float* out, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * DRAS-MIL attention-guided sampling (eval.py --sampling: utils/eval_utils.py:182-565 summary_sampling, helpers in
+ * utils/sampling_utils.py:11-187): the two device pieces of a sampling round.
+ * ---------------------------------------------------------------------------------- */
+enum { HIPT_KNN_SPATIAL = 0, HIPT_KNN_TEXTURAL = 1 };
+enum { HIPT_SAMPLING_MAX = 0, HIPT_SAMPLING_NEWEST = 1, HIPT_SAMPLING_AVERAGE = 2 };
+
+/* Brute-force k nearest neighbours of S rows of the point set itself: replaces NearestNeighbors(n_neighbors=k,
+ * algorithm='ball_tree').fit(X) and .kneighbors(X[sample_idxs]) (eval_utils.py:285,390-391,413).  Queries are the rows
+ * q_idx int64 [S] of X.  Results: ids int64 [S, k] and dist [S, k], every row in ascending (squared distance, index) order --
+ * a defined order, which sklearn's is not: a query's first neighbour is itself unless an identical point has a lower index.
+ *   HIPT_KNN_SPATIAL:  X int32 [N, 2] (patch coordinates, |value| <= 2^30), D = 2; squared distances are 64-bit integers,
+ *                      so the lists are exact; dist is float64 [S, k] = sqrt of that integer converted to float64.
+ *   HIPT_KNN_TEXTURAL: X fp32 [N, D], D a multiple of 4 up to 2048, 16-byte aligned; the squared distance is the fp32 sum
+ *                      over the features, in ascending order, of the squared fp32 difference (never the |a|^2+|b|^2-2ab
+ *                      expansion); dist is fp32 [S, k] = its square root.
+ * Envelope: 1 <= k <= 64, k <= N (else HIPT_E_BADARG, as sklearn raises), S <= 4096, N <= 2^20.  X is read from memory once
+ * per 128 queries.  workspace: 256-byte aligned, hipt_knn_workspace_bytes.  Results are bitwise repeatable. */
+size_t hipt_knn_workspace_bytes(int N, int S, int k);
+int hipt_knn(const void* X, int kind, int N, int D, const int64_t* q_idx, int S, int k, int64_t* ids, void* dist,
+             void* workspace, size_t ws_bytes, void* stream);
+
+/* update_sampling_weights(..., normalise=False, repeats_allowed=False) of one round (sampling_utils.py:66-187), in place on
+ * weights float64 [N].  scores fp32 [S] >= 0 (the softmaxed attention of the round's sample); ids int64 [S, k_stride], of
+ * which the first `neighbors` columns of every row are used; all_sampled int64 [T].  Row i contributes scores[i] to every
+ * target j in its prefix (ids outside [0, N) are ignored):
+ *   HIPT_SAMPLING_MAX      new[j] = max_i scores[i];  weights[j] = max(weights[j], new[j] ** power)          (:125-172)
+ *   HIPT_SAMPLING_NEWEST   the reference assigns new[j] and never uses it (:174-177): the weights are left alone
+ *   HIPT_SAMPLING_AVERAGE  new[j] = new[j] > 0 ? (new[j] + scores[i]) / 2 : scores[i], folded over the contributions in
+ *                          ascending (i, column); weights[j] = new[j] ** power where that is > 0 (an overwrite) (:77-88)
+ * then weights[all_sampled] = 0 (:179-181).  All arithmetic is float64; the fold order and hence the result do not depend on
+ * scheduling.  sum_out float64 [1] receives the sum of the updated weights, added in a fixed order.  power > 0.
+ * workspace: 256-byte aligned, hipt_sampling_update_workspace_bytes. */
+size_t hipt_sampling_update_workspace_bytes(int N);
+int hipt_sampling_update(double* weights, int N, const float* scores, int S, const int64_t* ids, int k_stride, int neighbors,
+                         const int64_t* all_sampled, int T, double power, int mode, double* sum_out, void* workspace,
+                         size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
