@@ -19,7 +19,8 @@ CSRC = os.path.join(HERE, "csrc")
 HIPT_F32, HIPT_BF16 = 0, 1
 EPI_GELU, EPI_RESID, EPI_OUT_F32, EPI_RELU = 1, 2, 4, 16
 ABI_VERSION = 5
-PACK_QKV, PACK_PROJ, PACK_MLP, PACK_QKV_ATT = 0, 1, 2, 3
+PACK_QKV, PACK_PROJ, PACK_MLP, PACK_QKV_ATT, PACK_CLS_ABSORB = 0, 1, 2, 3, 4
+CLS_ABSORB_TAIL = 0x4B564142  # hipt_block_weights.cls_absorb (include/hipt_abmil.h)
 
 c_f32p = C.c_void_p  # device pointers travel as integers
 
@@ -28,7 +29,7 @@ class BlockWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
         "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "qkv_pk", "proj_pk", "mlp_pk")] + [
-        ("mlp_pk_fmt", C.c_int32), ("reserved", C.c_int32), ("qkv_att_pk", C.c_void_p)]
+        ("mlp_pk_fmt", C.c_int32), ("cls_absorb", C.c_int32), ("qkv_att_pk", C.c_void_p)]
 
 
 class VitWeights(C.Structure):

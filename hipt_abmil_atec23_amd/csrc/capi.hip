@@ -138,7 +138,7 @@ int linear(const void* A, int64_t lda, const void* W, int64_t ldw, const float* 
 // on how many sequences share the call (feature_store.extract_slide gathers loader batches on that promise).
 // a_row_step > 0: A is a bf16 activation image, GEMM row r its row r * a_row_step; `gather` = [M, K] scratch for the gathered rows.
 int rows_linear(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc, int M, int N, int K, int dtype,
-                hipStream_t st, int a_row_step = 0, void* gather = nullptr) {
+                hipStream_t st, int a_row_step = 0, void* gather = nullptr, int flags = 0) {
     GemmParams p;
     memset(&p, 0, sizeof(p));
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.M = M; p.N = N; p.K = K; p.bias = bias; p.out = out; p.ldc = ldc;
@@ -152,7 +152,7 @@ int rows_linear(const void* A, int64_t lda, const void* W, int64_t ldw, const fl
             p.A = gather;
         }
     }
-    return hipt_gemm_launch(p, dtype, ALOAD_PLAIN, 0, st);
+    return hipt_gemm_launch(p, dtype, ALOAD_PLAIN, flags, st);
 }
 
 // emit_last: the MLP of block b1-1 also writes LayerNorm-1 of block b1 on its output rows (bf16, s.att), for a caller
@@ -346,9 +346,26 @@ static int run_last_block_cls(const hipt_vit_weights* w, float* x, int nseq, con
             char* qa = (char*)s.hid + 4096 + al256((size_t)nseq * D * 4);
             char* qcls = qa + al256((size_t)nseq * D * 2);
             PROF(PC_LASTCLS, hipt_gather_cls_bf16_launch(s.att, qa, nseq, w->ntok, D, st, 1));
-            PROF(PC_LASTCLS, rows_linear(qa, D, b.qkv_w, D, b.qkv_b, qcls, 3 * D, nseq, 3 * D, D, w->dtype, st));
             q.img = 0;
-            PROF(PC_LASTCLS, hipt_qkv_attn_cls_launch(s.att, b.qkv_att_pk, b.qkv_b, qcls, s.qkv, nseq, attn_scale(w), st));
+            // K / V projection absorbed (cls_pool.hip): with one query per (patch, head) the scores are xn . u, u_h = Wk_h^T q_h, and the
+            // output is Wv_h z_h + bv_h, z_h the softmax-pooled xn rows -- Q rows, u, ONE streaming pass over the xn image, o.  The two
+            // per-head products run as row GEMMs on the zero-padded matrices behind the block's fused-attention image (b.cls_absorb).
+            // The same kernels whatever the call's size or company: rows_linear is row independent bit for bit, a patch is one work unit.
+            const bool absorb = b.cls_absorb == HIPT_CLS_ABSORB_TAIL && hipt_cls_pool_supported(w->dtype, D, w->heads, w->ntok) && !hipt_env_on("HIPT_NO_CLS_ABSORB");
+            if (absorb) {
+                const int HD = w->heads * D;
+                const char* wu = (const char*)b.qkv_att_pk + hipt_qkv_attn_packed_bytes();
+                const char* wo = wu + (size_t)HD * D * 2;
+                char* u = (char*)s.qkv + al256((size_t)nseq * D * 2);   // [nseq, 6, 384] fp32
+                char* z = u + al256((size_t)nseq * HD * 4);              // [nseq, 6, 384] bf16
+                PROF(PC_LASTCLS, rows_linear(qa, D, b.qkv_w, D, b.qkv_b, qcls, D, nseq, D, D, w->dtype, st));
+                PROF(PC_LASTCLS, rows_linear(qcls, D, wu, D, nullptr, u, HD, nseq, HD, D, w->dtype, st, 0, nullptr, HIPT_EPI_OUT_F32));
+                PROF(PC_LASTCLS, hipt_cls_pool_launch(s.att, (const float*)u, z, nseq, attn_scale(w), st));
+                PROF(PC_LASTCLS, rows_linear(z, HD, wo, HD, b.qkv_b + 2 * D, s.qkv, D, nseq, D, HD, w->dtype, st));
+            } else {
+                PROF(PC_LASTCLS, rows_linear(qa, D, b.qkv_w, D, b.qkv_b, qcls, 3 * D, nseq, 3 * D, D, w->dtype, st));
+                PROF(PC_LASTCLS, hipt_qkv_attn_cls_launch(s.att, b.qkv_att_pk, b.qkv_b, qcls, s.qkv, nseq, attn_scale(w), st));
+            }
             att_rows = s.qkv;
         } else {
             // Only token 0 of a sequence asks a question in this block: K and V for every row (columns 384.. of the QKV Linear: the
@@ -755,6 +772,8 @@ size_t hipt_vit_packed_bytes(const hipt_vit_weights* w, int what) {
         case HIPT_PACK_PROJ: return hipt_seqgemm_pipe_supported(w->dtype, D, D, false, 0) ? (size_t)D * D * 2 : 0;
         case HIPT_PACK_MLP: return hipt_vit_mlp_pack_format(w) != 0 ? hipt_mlp16_packed_bytes(D, w->hidden, hipt_vit_mlp_pack_format(w) == 3) : 0;
         case HIPT_PACK_QKV_ATT: return hipt_qkv_attn_supported(w->dtype, D, w->heads, w->ntok) ? hipt_qkv_attn_packed_bytes() : 0;
+        case HIPT_PACK_CLS_ABSORB:
+            return hipt_qkv_attn_supported(w->dtype, D, w->heads, w->ntok) && hipt_cls_pool_supported(w->dtype, D, w->heads, w->ntok) ? hipt_cls_absorb_packed_bytes() : 0;
         default: return 0;
     }
 }
@@ -775,6 +794,7 @@ int hipt_vit_pack_weights(const hipt_vit_weights* w, int block, int what, void* 
         case HIPT_PACK_QKV: return hipt_seqgemm_pack_launch(b.qkv_w, 3 * D, D, out, st);
         case HIPT_PACK_PROJ: return hipt_seqgemm_pack_launch(b.proj_w, D, D, out, st);
         case HIPT_PACK_QKV_ATT: return hipt_qkv_attn_pack_launch(b.qkv_w, out, st);
+        case HIPT_PACK_CLS_ABSORB: return hipt_cls_absorb_pack_launch(b.qkv_w, out, st);
         default:
             // the format the caller recorded beside the pointer (hipt_vit_mlp_pack_format): pack and launch read the same field
             if ((b.mlp_pk_fmt == 2 || b.mlp_pk_fmt == 3) && hipt_mlp16_supported(w->dtype, D, w->hidden))

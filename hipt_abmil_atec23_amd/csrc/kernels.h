@@ -165,6 +165,14 @@ int hipt_qkv_attn_pack_launch(const void* qkv_w, void* packed, hipStream_t st);
 int hipt_qkv_attn_launch(const void* xn_img, const void* wpk, const float* qkv_b, const void* qkv_cls, void* out_img, int nseq, float scale, hipStream_t st);
 int hipt_qkv_attn_cls_launch(const void* xn_img, const void* wpk, const float* qkv_b, const void* qkv_cls, void* out_rows, int nseq, float scale, hipStream_t st);
 
+// The [CLS]-pruned last block with the K / V projection absorbed (cls_pool.hip): z[nseq, 6, 384] bf16 = softmax-pooled rows of the bf16
+// activation image xn_img [nseq * 257, 384] under the scores scale * xn . u, u[nseq, 6, 384] fp32 (u_h = Wk_h^T q_h); the two GEMM
+// matrices around it (u = q Wu^T, o = z Wo^T + bv) as one image: Wu [2304, 384] then Wo [384, 2304], bf16 (hipt_cls_absorb_pack_launch)
+bool hipt_cls_pool_supported(int dtype, int D, int heads, int ntok);
+size_t hipt_cls_absorb_packed_bytes();
+int hipt_cls_absorb_pack_launch(const void* qkv_w, void* packed, hipStream_t st);
+int hipt_cls_pool_launch(const void* xn_img, const float* u, void* z, int nseq, float scale, hipStream_t st);
+
 // attention of the [CLS] query only (bf16, head dim 64): out[B, heads*64] bf16 and/or probs[B, heads, ntok] fp32 (either may be null)
 int hipt_attn_cls_launch(const void* qkv, void* out, float* probs, int B, int ntok, int heads, int dh, float scale, hipStream_t st);
 // probabilities of the [CLS] query only, any compute dtype, head dim 32 / 64: probs[B, heads, ntok] fp32

@@ -93,10 +93,16 @@ class _PackedVit:
             # (the image format travels with the fused-MLP image: hipt_block_weights.mlp_pk_fmt)
             fmt = lib.hipt_vit_mlp_pack_format(C.byref(self.w)) if what == N.PACK_MLP else 0
             for i in range(depth):
-                img = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                # (the last block's fused-attention image carries the K / V matrices of its [CLS]-pruned form behind it:
+                #  hipt_block_weights.cls_absorb -- constant per set of weights, like every other image here)
+                extra = lib.hipt_vit_packed_bytes(C.byref(self.w), N.PACK_CLS_ABSORB) if what == N.PACK_QKV_ATT and i == depth - 1 else 0
+                img = torch.empty(nbytes + extra, dtype=torch.uint8, device=dev)
                 if what == N.PACK_MLP:
                     self.blocks[i].mlp_pk_fmt = fmt  # (read by hipt_vit_pack_weights' twin at launch time, set before either)
                 N.call("hipt_vit_pack_weights", C.byref(self.w), i, what, N.ptr(img), N.stream_ptr(dev))
+                if extra:
+                    N.call("hipt_vit_pack_weights", C.byref(self.w), i, N.PACK_CLS_ABSORB, C.c_void_p(img.data_ptr() + nbytes), N.stream_ptr(dev))
+                    self.blocks[i].cls_absorb = N.CLS_ABSORB_TAIL
                 self.keep.append(img)
                 setattr(self.blocks[i], field, img.data_ptr())
 

@@ -79,7 +79,14 @@ typedef struct hipt_block_weights {
     /* The image format of mlp_pk: the value hipt_vit_mlp_pack_format returned when it was packed (3 = the streaming kernel's
      * fragment image on 16x16x32 MFMAs behind six units of proj_w: what this version packs; 2 = the same without the proj
      * units, still run; 0 = no packed form for this shape). */
-    int32_t      mlp_pk_fmt;  int32_t reserved;
+    int32_t      mlp_pk_fmt;
+    /* HIPT_CLS_ABSORB_TAIL (exactly that value): the qkv_att_pk image is FOLLOWED, in the same allocation, by the
+     * HIPT_PACK_CLS_ABSORB image (hipt_vit_packed_bytes(.., HIPT_PACK_CLS_ABSORB) more bytes, written by
+     * hipt_vit_pack_weights(.., HIPT_PACK_CLS_ABSORB, ..) at qkv_att_pk + hipt_vit_packed_bytes(.., HIPT_PACK_QKV_ATT)).  Read for the
+     * LAST block only: its [CLS]-pruned form then runs without the K / V projection (the K and V thirds of qkv_w absorbed into two
+     * [CLS]-row GEMMs around one pass over the tokens).  Any other value (the field was `reserved` before; zero-initialise the
+     * struct): that block projects K and V for every token, as before, and nothing is read behind the qkv_att_pk image. */
+    int32_t      cls_absorb;
     /* Optional: qkv_w once more, head by head in the operand order of the fused QKV + attention kernel (HIPT_PACK_QKV_ATT;
      * ViT-256 shape only: D = 384, 6 heads of 64, 257 tokens).  NULL: LayerNorm-chained blocks run the QKV GEMM and the
      * attention as two kernels with the q|k|v tensor in HBM between them. */
@@ -90,6 +97,8 @@ typedef struct hipt_block_weights {
 #define HIPT_PACK_PROJ 1
 #define HIPT_PACK_MLP  2   /* fc1 and fc2 in one image, in the format hipt_vit_mlp_pack_format names */
 #define HIPT_PACK_QKV_ATT 3
+#define HIPT_PACK_CLS_ABSORB 4   /* lives behind the last block's HIPT_PACK_QKV_ATT image: hipt_block_weights.cls_absorb */
+#define HIPT_CLS_ABSORB_TAIL 0x4B564142   /* hipt_block_weights.cls_absorb: "the tail image is there" (a tag, so that a stale non-zero value is not taken for it) */
 
 /* One ViT (ViT-256 `vit_small` or ViT-4K `vit4k_xs`, or any width the classes are built with).
  * `pos` is the ALREADY INTERPOLATED positional table for this token grid
