@@ -29,6 +29,8 @@ _LAZY = {
     "SamplingConfig": ("sampling", "SamplingConfig"), "dras_eval_slide": ("sampling", "dras_eval_slide"),
     "knn": ("sampling", "knn"), "update_sampling_weights": ("sampling", "update_sampling_weights"),
     "generate_sample_idxs": ("sampling", "generate_sample_idxs"), "resnet_patch_features": ("sampling", "resnet_patch_features"),
+    # bootstrapped evaluation metrics (bootstrapping.py)
+    "bootstrap_metrics": ("bootstrap", "bootstrap_metrics"), "bootstrap_eval_dir": ("bootstrap", "bootstrap_eval_dir"),
 }
 
 

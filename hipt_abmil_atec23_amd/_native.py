@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 
 HIPT_F32, HIPT_BF16 = 0, 1
 EPI_GELU, EPI_RESID, EPI_OUT_F32, EPI_RELU = 1, 2, 4, 16
-ABI_VERSION = 5
+ABI_VERSION = 6
 PACK_QKV, PACK_PROJ, PACK_MLP, PACK_QKV_ATT, PACK_CLS_ABSORB = 0, 1, 2, 3, 4
 CLS_ABSORB_TAIL = 0x4B564142  # hipt_block_weights.cls_absorb (include/hipt_abmil.h)
 
@@ -75,6 +75,8 @@ class ResnetWeights(C.Structure):
 RESNET_IN_F32, RESNET_IN_U8, RESNET_IN_U8_HWC = 0, 1, 2
 KNN_SPATIAL, KNN_TEXTURAL = 0, 1
 SAMPLING_MAX, SAMPLING_NEWEST, SAMPLING_AVERAGE = 0, 1, 2
+BOOTSTRAP_MAX_N, BOOTSTRAP_MAX_CLASSES, BOOTSTRAP_MAX_REPLICATES = 4096, 8, 1 << 20
+BOOTSTRAP_DEGENERATE, BOOTSTRAP_BAD_INPUT = 1, 2
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -148,6 +150,7 @@ SIGNATURES = {
     "hipt_knn": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "hipt_sampling_update_workspace_bytes": (_sz, [_i]),
     "hipt_sampling_update": (_i, [_p, _i, _p, _i, _p, _i, _i, _p, _i, C.c_double, _i, _p, _p, _sz, _p]),
+    "hipt_bootstrap_metrics": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -218,3 +218,8 @@ int hipt_pool_launch(const float* A, const float* h1, int N, int S1, float* gmax
                      hipStream_t st);
 int hipt_gather_h1_launch(const hipt_clam_weights* w, const void* bag, const int64_t* idx, int n_idx, float* out,
                           hipStream_t st);
+
+// ---- bootstrapped evaluation metrics (bootstrap.hip) ----
+size_t hipt_bootstrap_lds_bytes(int n);
+int hipt_launch_bootstrap(const int* Y, const int* Yh, const int* order, const int* tie, int n, int K, const int* idx, int B, double* out,
+                          int* flags, hipStream_t st);

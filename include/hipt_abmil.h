@@ -33,8 +33,9 @@ extern "C" {
 
 /* 5 (round 6): the HIPT_PACK_MLP image of format 3 is 2*D*hidden*2 + D*D*2 bytes (six proj units in front: ask
  * hipt_vit_packed_bytes, never compute the size) and packing it reads blocks[i].proj_w, which must be set first;
- * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone. */
-#define HIPT_ABI_VERSION 5
+ * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
+ * 6: hipt_bootstrap_metrics added (nothing else changed). */
+#define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
 
@@ -557,6 +558,36 @@ size_t hipt_sampling_update_workspace_bytes(int N);
 int hipt_sampling_update(double* weights, int N, const float* scores, int S, const int64_t* ids, int k_stride, int neighbors,
                          const int64_t* all_sampled, int T, double power, int mode, double* sum_out, void* workspace,
                          size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Bootstrapped evaluation metrics (bootstrapping.py:78-102): for each of B resamples (with replacement) of n pooled
+ * predictions, roc_auc_score / f1_score / accuracy_score / balanced_accuracy_score as exact ratios of integer counts
+ * (DESIGN.md 13).  One workgroup per replicate; the per-replicate state (index histogram, prefix sums, labels: 9 n + 4
+ * bytes) lives in LDS, which sets the limits:
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_BOOTSTRAP_MAX_N 4096        /* pooled predictions per replicate */
+#define HIPT_BOOTSTRAP_MAX_CLASSES 8     /* K */
+#define HIPT_BOOTSTRAP_MAX_REPLICATES (1 << 20)   /* B of one call (one workgroup each); call again for more */
+enum { HIPT_BOOTSTRAP_DEGENERATE = 1, HIPT_BOOTSTRAP_BAD_INPUT = 2 };   /* bits of *flags */
+
+/* Y, Y_hat int32 [n]: class ids in 0..K-1.  C = 1 scored class for K = 2 (class 1: p_1 against Y == 1, as roc_auc_score
+ * does for binary targets) and C = K for K > 2 (one-vs-rest, macro).  Scores do not cross this boundary; the host sorts them:
+ *   order int32 [C, n]: order[c][p] = the sample at position p when the samples are sorted ascending by class c's score;
+ *   tie   int32 [C, n]: tie[c][p] = lo | hi << 16, where [lo, hi) is the range of positions whose score equals that of
+ *                       position p (its tie group; two scores tie when their float64 values are equal).
+ * idx int32 [B, n]: the drawn sample indices of B replicates, each in 0..n-1.
+ * out float64 [B, 4]: AUC (mean over the C classes of (2 #{pos > neg} + #{pos = neg}) / (2 P N)), F1 (class 1 for K = 2,
+ * else the mean over classes of 2tp / (2tp + fp + fn), 0 where that denominator is 0), accuracy (trace / n) and balanced
+ * accuracy (mean of tp / (tp + fn) over the classes that occur).  All counting is integer, every quotient is one correctly
+ * rounded float64 division and the class means add in ascending class order, so a replicate's four values depend on its n
+ * indices alone -- not on B, its position in the call or the launch geometry.
+ * flags int32 [1]: the CALLER zeroes it; the call ORs in HIPT_BOOTSTRAP_DEGENERATE if some replicate leaves a scored class
+ * without a positive or without a negative member (its AUC is written as NaN; sklearn raises there), and
+ * HIPT_BOOTSTRAP_BAD_INPUT if a label, an index or an order entry lies outside its range (such an entry is never followed;
+ * the results of the call are then meaningless).  Beyond the limits above the call returns HIPT_E_UNSUPPORTED and launches
+ * nothing.  No workspace. */
+int hipt_bootstrap_metrics(const int32_t* Y, const int32_t* Y_hat, const int32_t* order, const int32_t* tie, int n, int K,
+                           const int32_t* idx, int B, double* out, int32_t* flags, void* stream);
 
 #ifdef __cplusplus
 }
