@@ -176,3 +176,16 @@ int hipt_launch_bootstrap(const int* Y, const int* Yh, const int* order, const i
     HIPT_CHECK_LAUNCH();
     return HIPT_OK;
 }
+
+extern "C" int hipt_bootstrap_metrics(const int32_t* Y, const int32_t* Y_hat, const int32_t* order, const int32_t* tie, int n, int K,
+                                      const int32_t* idx, int B, double* out, int32_t* flags, void* stream) {
+    HIPT_CHECK_ARG(Y && Y_hat && order && tie && idx && out && flags, "bootstrap_metrics: null argument");
+    HIPT_CHECK_ARG(n >= 1 && K >= 2 && B >= 1, "bootstrap_metrics: n=%d (>= 1), K=%d (>= 2), B=%d (>= 1)", n, K, B);
+    if (n > HIPT_BOOTSTRAP_MAX_N || K > HIPT_BOOTSTRAP_MAX_CLASSES || B > HIPT_BOOTSTRAP_MAX_REPLICATES) {
+        hipt_set_error("bootstrap_metrics: n=%d / K=%d / B=%d beyond the limits %d / %d / %d (nothing was launched)", n, K, B,
+                       HIPT_BOOTSTRAP_MAX_N, HIPT_BOOTSTRAP_MAX_CLASSES, HIPT_BOOTSTRAP_MAX_REPLICATES);
+        return HIPT_E_UNSUPPORTED;
+    }
+    HIPT_CHECK_ARG(((uintptr_t)out & 7) == 0, "bootstrap_metrics: out must be 8-byte aligned");
+    return hipt_launch_bootstrap(Y, Y_hat, order, tie, n, K, idx, B, out, flags, (hipStream_t)stream);
+}

@@ -1,4 +1,4 @@
-// extern "C" entry points of libhipt_abmil.so (include/hipt_abmil.h): argument validation, scratch
+// extern "C" ViT and CLAM entry points of libhipt_abmil.so (include/hipt_abmil.h): argument validation, scratch
 // carving and the launch sequences.  Host code only: nothing here synchronises or allocates, so a
 // caller may capture any call into a hipGraph.
 #include <stdarg.h>
@@ -24,17 +24,29 @@ inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline int esz(int dtype) { return dtype == HIPT_F32 ? 4 : 2; }
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
 
+// Every workspace is described ONCE, by the carve_*() function that hands out its parts: a forward runs it over the caller's
+// buffer, the matching *_workspace_bytes entry point over no buffer at all (the default Carver) and returns `used`.
 struct Carver {
     char* base;
     size_t cap, used = 0;
-    Carver(void* b, size_t c) : base((char*)b), cap(c) {}
+    Carver(void* b = nullptr, size_t c = SIZE_MAX) : base((char*)b), cap(c) {}
     void* take(size_t n) {
-        void* p = base + used;
+        void* p = base ? base + used : nullptr;
         used += al256(n);
         return p;
     }
     bool ok() const { return used <= cap && (((uintptr_t)base & 255) == 0 || used == 0); }
 };
+template <class F> size_t dry_run(F carve) {
+    Carver c;
+    carve(c);
+    return c.used;
+}
+int check_workspace(const Carver& c, const char* who) {
+    if (c.ok()) return HIPT_OK;
+    hipt_set_error("%s: workspace %zu B too small / unaligned (need %zu)", who, c.cap, c.used);
+    return HIPT_E_WORKSPACE;
+}
 
 // ---- optional per-kernel timing (bench.py's roofline leg): HIP events around every launch -----
 enum { PC_EMBED, PC_LN, PC_QKV, PC_ATTN, PC_PROJ, PC_FC1, PC_FC2, PC_MLP, PC_ABMIL, PC_COMBINE, PC_OTHER, PC_VIT4K, PC_LASTCLS, PC_QKVATT, PC_CLSROWS, PC_N };
@@ -88,81 +100,113 @@ int check_vit(const hipt_vit_weights* w) {
 // Attention.scale (vision_transformer.py:112): qk_scale when the module was built with one, else head_dim ** -0.5
 inline float attn_scale(const hipt_vit_weights* w) { return w->attn_scale > 0.f ? w->attn_scale : 1.0f / sqrtf((float)(w->dim / w->heads)); }
 
+// ---- the scratch of a run of ViT blocks ---------------------------------------------------------------------------------------
+// The tile queues of the streaming kernels, one 64-byte line each.  `aux`: the proj GEMM, or the [CLS]-row Q GEMM of the pruned block.
+struct TileQueues { int mlp[16], qkv[16], aux[16]; };
 struct BlockScratch {
-    void *xn, *qkv, *att, *hid;
+    void *xn, *qkv, *att, *hid;  // [rows, D] | [rows, 3 D] | [rows, D] | [rows, hidden] in the compute dtype
+    // borrowed from the hidden slot by the streaming routes, which never materialise the hidden tensor:
+    TileQueues* queues;
+    float* xc;      // [nseq, D] fp32: the compact [CLS] residual rows of the pruned last block
+    void* cls_xn;   // [nseq, D] bf16: the gathered LayerNorm-1 rows of the [CLS] tokens
+    void* cls_qkv;  // [nseq, 3 D] bf16 (+ 1 KiB the fused kernel's row DMA may read past the end): q | k | v of the [CLS] rows
+    // borrowed from the qkv slot by the K/V-absorbed last block, behind the [nseq, D] attention rows it leaves at s.qkv itself:
+    void* u;        // [nseq, heads, D] fp32
+    void* z;        // [nseq, heads, D] bf16
+    bool fits_xc, fits_cls_xn;  // queues + xc (+ cls_xn) lie inside the hidden slot
 };
 
-size_t block_scratch_bytes(const hipt_vit_weights* w, int nseq) {
-    const size_t rows = (size_t)nseq * w->ntok, e = esz(w->dtype);
-    return al256(rows * w->dim * e) * 2 + al256(rows * 3 * w->dim * e) + al256(rows * w->hidden * e);
-}
-
+// The borrowing is legal because every route that uses a borrowed buffer runs shapes whose slot holds it:
+//  - queues (192 B): the streaming routes run more than 1 088 rows of hidden >= 128 bf16 elements;
+//  - cls_qkv, u, z: the fused / absorbed kernels exist for bf16, D = 384, 6 heads, 257 tokens only.  Per sequence the hidden slot is
+//    257 * hidden * 2 B >= 65 792 B (hidden % 128 == 0) against 1 536 (xc) + 768 (cls_xn) + 2 304 (cls_qkv) = 4 608 B, plus under 3 KiB
+//    of fixed cost (queues, the 1 KiB slack, alignment); the qkv slot is 257 * 2 304 B against 768 + 9 216 + 4 608 B;
+//  - xc and cls_xn: the pruned last block takes any token count up to 320, and a model of a handful of tokens per sequence with a
+//    narrow MLP does NOT leave room (hidden = 128, 3 tokens: 768 B a sequence).  fits_xc / fits_cls_xn say so and the one user,
+//    vit256_range_impl, refuses such a call.
 BlockScratch carve_blocks(Carver& c, const hipt_vit_weights* w, int nseq) {
-    const size_t rows = (size_t)nseq * w->ntok, e = esz(w->dtype);
+    const size_t rows = (size_t)nseq * w->ntok, e = esz(w->dtype), D = w->dim, n = nseq;
     BlockScratch s;
-    s.xn = c.take(rows * w->dim * e);
-    s.qkv = c.take(rows * 3 * w->dim * e);
-    s.att = c.take(rows * w->dim * e);
+    s.xn = c.take(rows * D * e);
+    s.qkv = c.take(rows * 3 * D * e);
+    s.att = c.take(rows * D * e);
     s.hid = c.take(rows * w->hidden * e);
+    Carver h(s.hid, rows * w->hidden * e);
+    s.queues = (TileQueues*)h.take(sizeof(TileQueues));
+    s.xc = (float*)h.take(n * D * 4);
+    s.fits_xc = h.ok();
+    s.cls_xn = h.take(n * D * 2);
+    s.fits_cls_xn = h.ok();
+    s.cls_qkv = h.take(n * 3 * D * 2 + 1024);
+    Carver k(s.qkv, rows * 3 * D * e);
+    k.take(n * D * 2);
+    s.u = k.take(n * w->heads * D * 4);
+    s.z = k.take(n * w->heads * D * 2);
     return s;
 }
 
-int linear(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* resid, void* out,
-           int64_t ldc, int M, int N, int K, int dtype, int flags, hipStream_t st, int rpt = 0, const float* ln_w = nullptr,
-           const float* ln_b = nullptr, float ln_eps = 0.f, int a_row_step = 0, int small_any = 0) {
+// ---- one builder per parameter struct: a call site sets only the fields in which it differs -----------------------------------
+GemmParams gemm_params(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc, int M, int N, int K) {
     GemmParams p;
     memset(&p, 0, sizeof(p));
-    p.A = A;
-    p.lda = lda;
-    p.W = W;
-    p.ldw = ldw;
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.bias = bias;
-    p.resid = resid;
-    p.out = out;
-    p.ldc = ldc;
-    p.rpt = rpt;
-    p.ln_w = ln_w;  // (set: A is the fp32 residual rows and the GEMM normalises them itself -- small calls, gemm.hip)
-    p.ln_b = ln_b;
-    p.ln_eps = ln_eps;
-    p.a_row_step = a_row_step;  // (> 0: A is a bf16 activation image and row r is its row r * a_row_step)
-    p.small_any = small_any;
-    return hipt_gemm_launch(p, dtype, ALOAD_PLAIN, flags, st);
+    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.out = out; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+    return p;
 }
+inline int linear(const GemmParams& p, int dtype, int flags, hipStream_t st) { return hipt_gemm_launch(p, dtype, ALOAD_PLAIN, flags, st); }
+
+// The QKV projection of block `blk` over M rows of the residual stream x, LayerNorm-1 in the load (launch with ln = true), into s.qkv.
+// qkv_from_xn(): the rows are bf16 operands another kernel already normalised instead (launch with ln = false).
+SeqGemmParams qkv_params(const hipt_vit_weights* w, int blk, int M, const float* x, const BlockScratch& s) {
+    const hipt_block_weights& b = w->blocks[blk];
+    const int D = w->dim;
+    SeqGemmParams q;
+    memset(&q, 0, sizeof(q));
+    q.M = M; q.K = D; q.ln_eps = w->ln_eps;
+    q.A = x; q.lda = D; q.ln_w = b.ln1_w; q.ln_b = b.ln1_b; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = 3 * D; q.bias = b.qkv_b;
+    q.out = s.qkv; q.ldc = 3 * D; q.out_ntok = w->ntok;
+    q.counter = s.queues->qkv;
+    return q;
+}
+inline void qkv_from_xn(SeqGemmParams& q, const void* xn) { q.A = xn, q.ln_w = q.ln_b = nullptr; }
+
+// The fused MLP of block `blk` over M rows of x, the attention branch's output y1 in s.xn
+MlpParams mlp_params(const hipt_vit_weights* w, int blk, int M, float* x, const BlockScratch& s) {
+    const hipt_block_weights& b = w->blocks[blk];
+    MlpParams m;
+    memset(&m, 0, sizeof(m));
+    m.x = x; m.y1 = s.xn; m.bproj = b.proj_b; m.ln_w = b.ln2_w; m.ln_b = b.ln2_b; m.ln_eps = w->ln_eps;
+    m.w1 = b.fc1_w; m.b1 = b.fc1_b; m.w2 = b.fc2_w; m.b2 = b.fc2_b; m.wpk = b.mlp_pk; m.wpk_fmt = b.mlp_pk_fmt; m.M = M; m.D = w->dim; m.hidden = w->hidden;
+    m.counter = s.queues->mlp;
+    return m;
+}
+// ... which also leaves LayerNorm-1 of block `next` of the rows it finishes in xn_out
+inline void mlp_emit_xn(MlpParams& m, const hipt_block_weights& next, void* xn_out) { m.ln_next_w = next.ln1_w, m.ln_next_b = next.ln1_b, m.xn_out = xn_out; }
 
 // Linears over ONE row per sequence (the [CLS] rows: M = nseq).  Up to 1 088 rows the small-M GEMM (gemm.hip: a wave per 16 x 32 output
 // tile, reading the rows out of the activation image itself when a_row_step > 0), above that a gather launch (image rows only) + the
 // tiled GEMM -- and BOTH walk k in the same ascending 32-element steps (GemmParams::asc), so that a sequence's bits do not depend
 // on how many sequences share the call (feature_store.extract_slide gathers loader batches on that promise).
 // a_row_step > 0: A is a bf16 activation image, GEMM row r its row r * a_row_step; `gather` = [M, K] scratch for the gathered rows.
-int rows_linear(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc, int M, int N, int K, int dtype,
-                hipStream_t st, int a_row_step = 0, void* gather = nullptr, int flags = 0) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.M = M; p.N = N; p.K = K; p.bias = bias; p.out = out; p.ldc = ldc;
+int rows_linear(GemmParams p, int dtype, int flags, hipStream_t st, int a_row_step = 0, void* gather = nullptr) {
     p.asc = 1;
     if (a_row_step > 0) {
-        if (!hipt_generic_only() && hipt_gemm_arows_supported(M, K, dtype, ALOAD_PLAIN, 0)) {
+        if (!hipt_generic_only() && hipt_gemm_arows_supported(p.M, p.K, dtype, ALOAD_PLAIN, 0)) {
             p.a_row_step = a_row_step;
         } else {
-            int rc = hipt_gather_cls_bf16_launch(A, gather, M, a_row_step, K, st, 1);
+            int rc = hipt_gather_cls_bf16_launch(p.A, gather, p.M, a_row_step, p.K, st, 1);
             if (rc) return rc;
             p.A = gather;
         }
     }
-    return hipt_gemm_launch(p, dtype, ALOAD_PLAIN, flags, st);
+    return linear(p, dtype, flags, st);
 }
 
-// emit_last: the MLP of block b1-1 also writes LayerNorm-1 of block b1 on its output rows (bf16, s.att), for a caller
-// that runs block b1 itself (the [CLS]-pruned last block); *have_xn tells it whether that happened
-// img_ok / x_img_out: the caller owns x and accepts it back as an fp32 activation image (kernels.h): blocks after the
-// first then exchange y1 / xn / x as images (coalesced row phases); *x_img_out tells whether x came back as one
+// ---- the route of a call: decided once, here, from the model, the call's size and the environment switches --------------------
 // at most four 272-row sequences: what gemm.hip's small-M kernel takes (HIPT_GENERIC keeps its meaning: the generic kernels either way)
 static bool small_call(const hipt_vit_weights* w, int nseq) { return (int64_t)nseq * w->ntok <= 1088; }
 
-// do blocks [b0, b1) of a call of nseq sequences run LayerNorm-chained on the streaming kernels / exchange activation images?
+// do blocks [b0, b1) of a call of nseq sequences run LayerNorm-chained on the streaming kernels?  (only those have the LayerNorm
+// epilogue / prologue: every block of the range needs its packed weight images)
 static bool blocks_chain(const hipt_vit_weights* w, int nseq, int b0, int b1) {
     const int D = w->dim, dt = w->dtype;
     bool chain = hipt_seqgemm_supported(dt, D) && hipt_mlp_supported(dt, D, w->hidden) && !small_call(w, nseq) && !hipt_generic_only() &&
@@ -170,243 +214,258 @@ static bool blocks_chain(const hipt_vit_weights* w, int nseq, int b0, int b1) {
     for (int i = b0; i < b1 && chain; ++i) chain = w->blocks[i].qkv_pk && w->blocks[i].proj_pk && w->blocks[i].mlp_pk && (w->blocks[i].mlp_pk_fmt == 2 || w->blocks[i].mlp_pk_fmt == 3);
     return chain;
 }
-static bool blocks_images(const hipt_vit_weights* w, int nseq, int b0, int b1) {
-    return blocks_chain(w, nseq, b0, b1) && ((int64_t)nseq * w->ntok) % 16 == 0 && !hipt_env_on("HIPT_NO_IMG") &&
-           hipt_attention64_supported(w->dtype, w->dim / w->heads, w->ntok, false);
-}
-
-// xn_ready (round 5): the caller's embedding already left x as the fp32 activation image and LayerNorm-1 of block b0 as the bf16 image s.att
-// (embed32.hip, LNOUT): block b0 then runs like every later block.  Only with img_ok and blocks_images(..) true (checked).
-int run_blocks(const hipt_vit_weights* w, float* x, int nseq, int b0, int b1, float* probs, const BlockScratch& s,
-               hipStream_t st, bool emit_last = false, bool* have_xn_out = nullptr, bool img_ok = false, bool* x_img_out = nullptr, bool xn_ready = false,
-               bool force_small = false) {
-    const int D = w->dim, M = nseq * w->ntok, dt = w->dtype, dh = D / w->heads;
-    const float scale = attn_scale(w);
-    int rc;
-    // A call of a few hundred rows (ONE 256 x 256 patch: 257; the second-level ViT of one region: 257) is latency, not throughput: the
-    // A-stationary kernels would put it on two 192-row tiles, the fused MLP on seventeen 16-row tiles that each stream the whole weight
-    // image (55 us a block).  Such calls take the per-operator path below, whose Linears run on the small-M GEMM (gemm.hip: a wave per
-    // 16 x 32 output tile, 51-204 workgroups): seven launches of a few microseconds per block.
-    // force_small (hipt_vit4k_forward): the small-call kernels for ANY number of rows -- one launch per operator for all the regions of a call
-    const bool small = small_call(w, nseq) || force_small;
-    const int sa = force_small ? 1 : 0;
-    const bool seq = hipt_seqgemm_supported(dt, D) && hipt_mlp_supported(dt, D, w->hidden) && !small;
-    // timing categories: the kernels of the small second-level ViT (D = 192, a few hundred rows) are booked together,
-    // so that the per-kernel categories hold only the ViT-256 launches the roofline is computed on
-    const bool big = D >= 384;
-    const int cQKV = big ? PC_QKV : PC_VIT4K, cATTN = big ? PC_ATTN : PC_VIT4K, cPROJ = big ? PC_PROJ : PC_VIT4K, cMLP = big ? PC_MLP : PC_VIT4K;
-    // pipelined path: the MLP of block i applies LayerNorm-1 of block i+1 to the rows it finishes and leaves them in
-    // s.att as bf16 operands; block i+1's QKV GEMM then skips the fp32 row load + LayerNorm
-    // (only the streaming kernels have that epilogue / prologue: every block of the range needs its packed weight images)
-    const bool chain = !force_small && blocks_chain(w, nseq, b0, b1);
-    // activation images: chained streaming blocks, whole 16-row fragments, no probability output
-    const bool img = !force_small && img_ok && probs == nullptr && blocks_images(w, nseq, b0, b1);
-    HIPT_CHECK_ARG(!xn_ready || (img && b0 < b1), "run_blocks: image input without the image path");
-    bool have_xn = xn_ready;
-    // with them, q | k | v leave the QKV GEMM head-major (the attention kernel's K / V staging reads consecutive bytes)
-    const bool hm = img && (int64_t)M * 3 * D * 2 < ((int64_t)1 << 32) - 65536;
-    bool x_img = xn_ready;
-    // the tile queues of the streaming kernels (three ints in the unused hidden slot) reset themselves at the end of a launch:
-    // zeroed once here instead of before each of the ~44 launches (5 us each on the stream: 3 % of a one-region forward)
-    const bool qz = chain && hipMemsetAsync(s.hid, 0, 48 * sizeof(int), st) == hipSuccess;
-    for (int i = b0; i < b1; ++i) {
-        const hipt_block_weights& b = w->blocks[i];
-        const bool last_probs = probs != nullptr && i == b1 - 1;
-        if (seq) {
-            // bf16, D in {192,384}: A-stationary kernels.  QKV with LayerNorm-1 fused into the activation
-            // load; proj leaves the attention-branch output y1 in bf16 (s.xn); the fused MLP kernel folds
-            // y1 in, does LN2 + fc1 + GELU + fc2 with the hidden tensor on chip and updates x in place.
-            SeqGemmParams q;
-            memset(&q, 0, sizeof(q));
-            q.M = M; q.K = D; q.ln_eps = w->ln_eps;
-            q.A = x; q.lda = D; q.ln_w = b.ln1_w; q.ln_b = b.ln1_b; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = 3 * D; q.bias = b.qkv_b;
-            q.out = s.qkv; q.ldc = 3 * D;
-            // (the hidden tensor is never materialised on this path: its slot holds the kernels' tile queues)
-            q.counter = (int*)s.hid + 16;
-            q.counter_zeroed = qz ? 1 : 0;
-            q.out_ntok = w->ntok;
-            // LayerNorm-chained block with activation images: the QKV projection runs inside the attention kernel (qkv_attention.hip),
-            // q | k | v never reach HBM.  The [CLS] rows (257 = 8 x 32 + 1) get their q | k | v from a side GEMM over nseq rows.
-            const bool fuse = have_xn && img && b.qkv_att_pk && hipt_qkv_attn_supported(dt, D, w->heads, w->ntok) && !last_probs &&
-                              !hipt_env_on("HIPT_NO_FUSED_ATTN");
-            // image format 3 (round 5): the output projection runs at the head of the fused MLP's tiles (mlp16.hip, FOLD) -- no proj launch, no y1
-            const bool fold = chain && b.mlp_pk_fmt == 3 && !hipt_env_on("HIPT_NO_PROJ_FOLD") && !last_probs;
-            // Where the attention output goes.  Fused kernel: the (unused) qkv slot.  Two kernels: s.att -- except under the fold, where the
-            // MLP kernel reads the attention rows as y1 AND writes the next block's LayerNorm-1 rows to s.att in the same launch: the y1 slot
-            // s.xn is free then (no proj launch writes it), so the two never share a buffer.  (The kernel itself would tolerate the alias -- a
-            // workgroup loads all attention rows of its tile before it stores any, tiles own disjoint rows: mlp16.hip, "in place" -- but
-            // nothing in a launch sequence should rest on that.)
-            void* att_two = fold ? s.xn : s.att;
-            const void* att_out = att_two;
-            if (fuse) {
-                char* qa = (char*)s.hid + 4096 + al256((size_t)nseq * D * 4);   // (the hidden slot is free on this path; its head holds tile queues)
-                char* qcls = qa + al256((size_t)nseq * D * 2);                   // [nseq, 3 D] bf16 + 1 KiB the kernel's row DMA may read past the end
-                // (nseq rows are a handful of the streaming kernel's 192-row tiles -- 11 CUs for 2 048 patches; the generic GEMM tiles N as well.
-                //  Up to 1 088 sequences the small-M GEMM reads the [CLS] rows out of the image itself: one launch, not two)
-                PROF(PC_CLSROWS, rows_linear(s.att, D, b.qkv_w, D, b.qkv_b, qcls, 3 * D, nseq, 3 * D, D, dt, st, w->ntok, qa));
-                PROF(PC_QKVATT, hipt_qkv_attn_launch(s.att, b.qkv_att_pk, b.qkv_b, qcls, s.qkv, nseq, scale, st));
-                att_out = s.qkv;
-            } else if (have_xn) {  // LayerNorm-1 already applied by the previous block's MLP epilogue
-                q.A = s.att; q.ln_w = q.ln_b = nullptr;
-                q.img = (img ? 1 : 0) | (hm ? 4 : 0);
-                PROF(cQKV, hipt_seqgemm_launch(q, false, 0, st));
-            } else {
-                q.img = hm ? 4 : 0;
-                PROF(cQKV, hipt_seqgemm_launch(q, true, 0, st));
-            }
-            q.img = 0;
-            // (with activation images the attention output is one too: proj then reads its operands 1 KiB at a time)
-            if (!fuse) PROF(cATTN, hipt_attention_launch(s.qkv, att_two, last_probs ? probs : nullptr, nseq, w->ntok, w->heads, dh, scale, dt, st, img ? 1 : 0, hm ? 1 : 0));
-            if (last_probs) break;
-            if (!fold) {
-                q.A = att_out; q.ln_w = q.ln_b = nullptr; q.W = b.proj_w; q.wpk = b.proj_pk; q.N = D; q.bias = b.proj_b; q.out = s.xn; q.ldc = D;
-                q.counter = (int*)s.hid + 32;
-                q.img = img ? 3 : 0;  // A = the attention output image, out = y1 image
-                PROF(cPROJ, hipt_seqgemm_launch(q, false, 0, st));
-            }
-            MlpParams m;
-            memset(&m, 0, sizeof(m));
-            m.x = x; m.y1 = fold ? att_out : s.xn; m.ln_w = b.ln2_w; m.ln_b = b.ln2_b; m.ln_eps = w->ln_eps;
-            m.fold = fold ? 1 : 0;
-            m.bproj = b.proj_b;
-            m.w1 = b.fc1_w; m.b1 = b.fc1_b; m.w2 = b.fc2_w; m.b2 = b.fc2_b; m.wpk = b.mlp_pk; m.wpk_fmt = b.mlp_pk_fmt; m.M = M; m.D = D; m.hidden = w->hidden;
-            m.counter = (int*)s.hid;
-            m.counter_zeroed = qz ? 1 : 0;
-            have_xn = chain && (i + 1 < b1 || emit_last) && i + 1 < w->depth;
-            if (have_xn) {
-                m.ln_next_w = w->blocks[i + 1].ln1_w;
-                m.ln_next_b = w->blocks[i + 1].ln1_b;
-                m.xn_out = s.att;
-            }
-            if (img) {
-                m.img = x_img ? 3 : 1;
-                x_img = true;
-            }
-            PROF(cMLP, hipt_mlp_launch(m, st));
-            continue;
-        } else {
-            // (small calls: both LayerNorms run in the prologue of the GEMM that consumes them -- five launches a block instead of seven)
-            // (the kernel loads gamma / beta 16 bytes at a time: parameters that are views into a flat buffer off that grid keep the
-            //  separate LayerNorm launch, which has no alignment requirement)
-            const bool ln_al = (((uintptr_t)b.ln1_w | (uintptr_t)b.ln1_b | (uintptr_t)b.ln2_w | (uintptr_t)b.ln2_b) & 15) == 0;
-            const bool ln_in_gemm = small && ln_al && !hipt_generic_only() && hipt_gemm_ln_supported(M, D, ALOAD_PLAIN, 0, force_small);
-            if (ln_in_gemm) {
-                PROF(PC_QKV, linear(x, D, b.qkv_w, D, b.qkv_b, nullptr, s.qkv, 3 * D, M, 3 * D, D, dt, 0, st, w->ntok, b.ln1_w, b.ln1_b, w->ln_eps, 0, sa));
-            } else {
-                PROF(PC_LN, hipt_layernorm_launch(x, D, b.ln1_w, b.ln1_b, s.xn, dt, D, M, D, w->ln_eps, st));
-                PROF(PC_QKV, linear(s.xn, D, b.qkv_w, D, b.qkv_b, nullptr, s.qkv, 3 * D, M, 3 * D, D, dt, 0, st, w->ntok, nullptr, nullptr, 0.f, 0, sa));
-            }
-            PROF(PC_ATTN, hipt_attention_launch(s.qkv, s.att, last_probs ? probs : nullptr, nseq, w->ntok, w->heads, dh, scale, dt, st));
-            if (last_probs) break;  // Block.forward(return_attention=True) returns before the residual (:148-149)
-            PROF(PC_PROJ, linear(s.att, D, b.proj_w, D, b.proj_b, x, x, D, M, D, D, dt, HIPT_EPI_RESID | HIPT_EPI_OUT_F32, st, w->ntok, nullptr, nullptr, 0.f, 0, sa));
-            if (ln_in_gemm) {
-                PROF(PC_FC1, linear(x, D, b.fc1_w, D, b.fc1_b, nullptr, s.hid, w->hidden, M, w->hidden, D, dt, HIPT_EPI_GELU, st, w->ntok, b.ln2_w, b.ln2_b,
-                                    w->ln_eps, 0, sa));
-            } else {
-                PROF(PC_LN, hipt_layernorm_launch(x, D, b.ln2_w, b.ln2_b, s.xn, dt, D, M, D, w->ln_eps, st));
-                PROF(PC_FC1, linear(s.xn, D, b.fc1_w, D, b.fc1_b, nullptr, s.hid, w->hidden, M, w->hidden, D, dt, HIPT_EPI_GELU, st, w->ntok, nullptr, nullptr, 0.f, 0, sa));
-            }
-        }
-        PROF(PC_FC2, linear(s.hid, w->hidden, b.fc2_w, w->hidden, b.fc2_b, x, x, D, M, D, w->hidden, dt,
-                            HIPT_EPI_RESID | HIPT_EPI_OUT_F32, st, w->ntok, nullptr, nullptr, 0.f, 0, sa));
-    }
-    if (have_xn_out) *have_xn_out = have_xn;
-    if (x_img_out) *x_img_out = x_img;
-    return HIPT_OK;
-}
 
 // Last block when only the [CLS] row is consumed afterwards (ViT.forward returns norm(x)[:, 0], vision_transformer.py:248-253):
-// K and V are needed for every token, everything after that only for token 0 of each sequence -- the attention of one
-// query per (sequence, head), then proj / residual / MLP on nseq rows instead of nseq * ntok (allowed, and
-// the pruned FLOP figure is the one the roofline uses).  Leaves the final residual rows compact in xc [nseq, D].
+// K and V are needed for every token, everything after that only for token 0 of each sequence (run_last_block_cls)
 static bool can_prune_last(const hipt_vit_weights* w) {
     return w->dtype == HIPT_BF16 && w->dim == 384 && w->dim / w->heads == 64 && w->ntok <= 320 && hipt_seqgemm_supported(w->dtype, w->dim) &&
            hipt_mlp_supported(w->dtype, w->dim, w->hidden) && !hipt_env_on("HIPT_NO_PRUNE");
 }
 
-static int run_last_block_cls(const hipt_vit_weights* w, float* x, int nseq, const BlockScratch& s, float* xc, bool have_xn, bool x_img, hipStream_t st) {
-    const int D = w->dim, M = nseq * w->ntok;
-    const hipt_block_weights& b = w->blocks[w->depth - 1];
+// what the caller of run_blocks can accept
+enum {
+    RT_EMIT_LAST = 1,    // it runs block b1 itself and takes LayerNorm-1 of that block from the MLP of block b1 - 1 (bf16, s.att), when there is one
+    RT_CLS_ONLY = 2,     // it owns x and consumes the [CLS] rows of the whole ViT only: the last block may be pruned, x may be an activation image
+    RT_PX_EMBED = 4,     // its embedding is embed32.hip, which can write activation images + LayerNorm-1 of block 0
+    RT_FORCE_SMALL = 8,  // the small-call kernels for ANY number of rows (hipt_vit4k_forward)
+};
+struct VitRoute {
+    int b0, b1;        // the blocks run_blocks runs (prune: b1 = depth - 1, run_last_block_cls runs the last one)
+    bool emit_last;    // RT_EMIT_LAST, or prune
+    // A call of a few hundred rows (ONE 256 x 256 patch: 257; the second-level ViT of one region: 257) is latency, not throughput: the
+    // A-stationary kernels would put it on two 192-row tiles, the fused MLP on seventeen 16-row tiles that each stream the whole weight
+    // image (55 us a block).  Such calls take the per-operator path, whose Linears run on the small-M GEMM (gemm.hip: a wave per
+    // 16 x 32 output tile, 51-204 workgroups): seven launches of a few microseconds per block.
+    bool small, force_small;
+    bool seq;          // bf16, D in {192, 384}: the A-stationary QKV / proj GEMMs and the fused MLP
+    bool chain;        // the MLP of block i applies LayerNorm-1 of block i + 1 to the rows it finishes (bf16 operands in s.att)
+    bool img;          // chained blocks exchange y1 / xn / x as activation images (kernels.h): whole 16-row fragments, no probability output
+    bool hm;           // with them, q | k | v leave the QKV GEMM head-major (the attention kernel's K / V staging reads consecutive bytes)
+    bool prune;        // the last block runs for the [CLS] rows only
+    bool pre;          // the embedding leaves x as the fp32 activation image and LayerNorm-1 of block 0 as the bf16 image s.att (embed32.hip, LNOUT)
+    bool fuse_ok, fold_ok, absorb_ok;  // the model-wide part of block_route()
+    // running state of the call
+    bool have_xn = false;  // s.att holds LayerNorm-1 of the next block to run
+    bool x_img = false;    // x (and s.att with it) is an activation image
+};
+
+VitRoute vit_route(const hipt_vit_weights* w, int nseq, int b0, int b1, bool want_probs, int accept) {
+    const int D = w->dim, dt = w->dtype;
+    const int64_t M = (int64_t)nseq * w->ntok;
+    VitRoute r;
+    r.force_small = (accept & RT_FORCE_SMALL) != 0;
+    r.small = small_call(w, nseq) || r.force_small;
+    r.prune = (accept & RT_CLS_ONLY) && can_prune_last(w) && !small_call(w, nseq);
+    r.b0 = b0;
+    r.b1 = r.prune ? w->depth - 1 : b1;
+    r.emit_last = r.prune || (accept & RT_EMIT_LAST);
+    r.seq = hipt_seqgemm_supported(dt, D) && hipt_mlp_supported(dt, D, w->hidden) && !r.small;
+    r.chain = !r.force_small && blocks_chain(w, nseq, r.b0, r.b1);
+    r.img = r.chain && r.prune && !want_probs && M % 16 == 0 && !hipt_env_on("HIPT_NO_IMG") && hipt_attention64_supported(dt, D / w->heads, w->ntok, false);
+    r.hm = r.img && M * 3 * D * 2 < ((int64_t)1 << 32) - 65536;
+    r.pre = r.img && (accept & RT_PX_EMBED) && r.b0 < r.b1 && !hipt_env_on("HIPT_NO_EMBED_LN");
+    r.fuse_ok = hipt_qkv_attn_supported(dt, D, w->heads, w->ntok) && !hipt_env_on("HIPT_NO_FUSED_ATTN");
+    r.fold_ok = r.chain && !hipt_env_on("HIPT_NO_PROJ_FOLD");
+    r.absorb_ok = hipt_cls_pool_supported(dt, D, w->heads, w->ntok) && !hipt_env_on("HIPT_NO_CLS_ABSORB");
+    return r;
+}
+
+struct BlockRoute {
+    // LayerNorm-chained block with activation images: the QKV projection runs inside the attention kernel (qkv_attention.hip),
+    // q | k | v never reach HBM.  The [CLS] rows (257 = 8 x 32 + 1) get their q | k | v from a side GEMM over nseq rows.
+    bool fuse;
+    // MLP image format 3: the output projection runs at the head of the fused MLP's tiles (mlp16.hip, FOLD) -- no proj launch, no y1
+    bool fold;
+    // (pruned last block) K / V projection absorbed (cls_pool.hip): with one query per (patch, head) the scores are xn . u, u_h = Wk_h^T q_h, and
+    // the output is Wv_h z_h + bv_h, z_h the softmax-pooled xn rows.  The two per-head products run as row GEMMs on the zero-padded
+    // matrices behind the block's fused-attention image (b.cls_absorb).
+    bool absorb;
+};
+BlockRoute block_route(const VitRoute& r, const hipt_block_weights& b, bool last_probs) {
+    BlockRoute k;
+    k.fuse = r.have_xn && r.x_img && b.qkv_att_pk && r.fuse_ok && !last_probs;
+    k.fold = r.fold_ok && b.mlp_pk_fmt == 3 && !last_probs;
+    k.absorb = k.fuse && b.cls_absorb == HIPT_CLS_ABSORB_TAIL && r.absorb_ok;
+    return k;
+}
+
+// the side GEMM of the fused attention kernels: q | k | v (N = 3 D) or q alone (N = D) of the [CLS] rows, whose LayerNorm-1 rows are
+// row r * a_row_step of the image s.att (a_row_step > 0) or the gathered rows s.cls_xn
+int cls_rows_qkv(const hipt_vit_weights* w, const hipt_block_weights& b, int nseq, int N, const BlockScratch& s, int a_row_step, hipStream_t st) {
+    const int D = w->dim;
+    return rows_linear(gemm_params(a_row_step > 0 ? s.att : s.cls_xn, D, b.qkv_w, D, b.qkv_b, s.cls_qkv, N, nseq, N, D), w->dtype, 0, st, a_row_step, s.cls_xn);
+}
+
+// Blocks [r.b0, r.b1) over the nseq sequences of x; probs != null: the attention map of block b1 - 1, after which that block stops.
+int run_blocks(const hipt_vit_weights* w, float* x, int nseq, float* probs, const BlockScratch& s, VitRoute& r, hipStream_t st) {
+    const int D = w->dim, M = nseq * w->ntok, dt = w->dtype, dh = D / w->heads;
+    const float scale = attn_scale(w);
     int rc;
-    SeqGemmParams q;
-    memset(&q, 0, sizeof(q));
-    q.M = M; q.K = D; q.ln_eps = w->ln_eps;
-    q.A = x; q.lda = D; q.ln_w = b.ln1_w; q.ln_b = b.ln1_b; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = 3 * D; q.bias = b.qkv_b;
-    q.out = s.qkv; q.ldc = 3 * D;
-    q.counter = (int*)s.hid + 16;
-    const void* att_rows = nullptr;  // [nseq, D] bf16: the attention output of the [CLS] tokens
-    if (have_xn) {  // LayerNorm-1 already applied by the previous block's MLP epilogue (bf16 operands in s.att)
-        q.A = s.att; q.ln_w = q.ln_b = nullptr;
-        q.img = x_img ? 1 : 0;  // (x and the operands s.att change layout together)
-        const bool fuse = x_img && b.qkv_att_pk && hipt_qkv_attn_supported(w->dtype, D, w->heads, w->ntok) && !hipt_env_on("HIPT_NO_FUSED_ATTN");
-        if (fuse) {
-            // The fused kernel's [CLS]-only form: K and V of every token are computed per (patch, head) and consumed in place by the one
-            // query of the patch; q | k | v of the [CLS] rows themselves from the side GEMM, as in the other blocks.  Output: the
-            // attention rows of the [CLS] tokens, compact, in the (unused) qkv slot.
-            char* qa = (char*)s.hid + 4096 + al256((size_t)nseq * D * 4);
-            char* qcls = qa + al256((size_t)nseq * D * 2);
-            PROF(PC_LASTCLS, hipt_gather_cls_bf16_launch(s.att, qa, nseq, w->ntok, D, st, 1));
-            q.img = 0;
-            // K / V projection absorbed (cls_pool.hip): with one query per (patch, head) the scores are xn . u, u_h = Wk_h^T q_h, and the
-            // output is Wv_h z_h + bv_h, z_h the softmax-pooled xn rows -- Q rows, u, ONE streaming pass over the xn image, o.  The two
-            // per-head products run as row GEMMs on the zero-padded matrices behind the block's fused-attention image (b.cls_absorb).
-            // The same kernels whatever the call's size or company: rows_linear is row independent bit for bit, a patch is one work unit.
-            const bool absorb = b.cls_absorb == HIPT_CLS_ABSORB_TAIL && hipt_cls_pool_supported(w->dtype, D, w->heads, w->ntok) && !hipt_env_on("HIPT_NO_CLS_ABSORB");
-            if (absorb) {
-                const int HD = w->heads * D;
-                const char* wu = (const char*)b.qkv_att_pk + hipt_qkv_attn_packed_bytes();
-                const char* wo = wu + (size_t)HD * D * 2;
-                char* u = (char*)s.qkv + al256((size_t)nseq * D * 2);   // [nseq, 6, 384] fp32
-                char* z = u + al256((size_t)nseq * HD * 4);              // [nseq, 6, 384] bf16
-                PROF(PC_LASTCLS, rows_linear(qa, D, b.qkv_w, D, b.qkv_b, qcls, D, nseq, D, D, w->dtype, st));
-                PROF(PC_LASTCLS, rows_linear(qcls, D, wu, D, nullptr, u, HD, nseq, HD, D, w->dtype, st, 0, nullptr, HIPT_EPI_OUT_F32));
-                PROF(PC_LASTCLS, hipt_cls_pool_launch(s.att, (const float*)u, z, nseq, attn_scale(w), st));
-                PROF(PC_LASTCLS, rows_linear(z, HD, wo, HD, b.qkv_b + 2 * D, s.qkv, D, nseq, D, HD, w->dtype, st));
+    // timing categories: the kernels of the small second-level ViT (D = 192, a few hundred rows) are booked together,
+    // so that the per-kernel categories hold only the ViT-256 launches the roofline is computed on
+    const bool big = D >= 384;
+    const int cQKV = big ? PC_QKV : PC_VIT4K, cATTN = big ? PC_ATTN : PC_VIT4K, cPROJ = big ? PC_PROJ : PC_VIT4K, cMLP = big ? PC_MLP : PC_VIT4K;
+    r.have_xn = r.x_img = r.pre;
+    // the tile queues of the streaming kernels reset themselves at the end of a launch:
+    // zeroed once here instead of before each of the ~44 launches (5 us each on the stream: 3 % of a one-region forward)
+    const int qz = r.chain && hipMemsetAsync(s.queues, 0, sizeof(TileQueues), st) == hipSuccess ? 1 : 0;
+    for (int i = r.b0; i < r.b1; ++i) {
+        const hipt_block_weights& b = w->blocks[i];
+        const bool last_probs = probs != nullptr && i == r.b1 - 1;
+        if (r.seq) {
+            // bf16, D in {192,384}: A-stationary kernels.  QKV with LayerNorm-1 fused into the activation
+            // load; proj leaves the attention-branch output y1 in bf16 (s.xn); the fused MLP kernel folds
+            // y1 in, does LN2 + fc1 + GELU + fc2 with the hidden tensor on chip and updates x in place.
+            const BlockRoute k = block_route(r, b, last_probs);
+            SeqGemmParams q = qkv_params(w, i, M, x, s);
+            q.counter_zeroed = qz;
+            // Where the attention output goes.  Fused kernel: the (unused) qkv slot.  Two kernels: s.att -- except under the fold, where the
+            // MLP kernel reads the attention rows as y1 AND writes the next block's LayerNorm-1 rows to s.att in the same launch: the y1 slot
+            // s.xn is free then (no proj launch writes it), so the two never share a buffer.  (The kernel itself would tolerate the alias -- a
+            // workgroup loads all attention rows of its tile before it stores any, tiles own disjoint rows: mlp16.hip, "in place" -- but
+            // nothing in a launch sequence should rest on that.)
+            void* att_two = k.fold ? s.xn : s.att;
+            const void* att_out = k.fuse ? s.qkv : att_two;
+            if (k.fuse) {
+                // (nseq rows are a handful of the streaming kernel's 192-row tiles -- 11 CUs for 2 048 patches; the generic GEMM tiles N as well.
+                //  Up to 1 088 sequences the small-M GEMM reads the [CLS] rows out of the image itself: one launch, not two)
+                PROF(PC_CLSROWS, cls_rows_qkv(w, b, nseq, 3 * D, s, w->ntok, st));
+                PROF(PC_QKVATT, hipt_qkv_attn_launch(s.att, b.qkv_att_pk, b.qkv_b, s.cls_qkv, s.qkv, nseq, scale, st));
             } else {
-                PROF(PC_LASTCLS, rows_linear(qa, D, b.qkv_w, D, b.qkv_b, qcls, 3 * D, nseq, 3 * D, D, w->dtype, st));
-                PROF(PC_LASTCLS, hipt_qkv_attn_cls_launch(s.att, b.qkv_att_pk, b.qkv_b, qcls, s.qkv, nseq, attn_scale(w), st));
+                if (r.have_xn) qkv_from_xn(q, s.att);  // LayerNorm-1 already applied by the previous block's MLP epilogue
+                q.img = (r.have_xn && r.img ? 1 : 0) | (r.hm ? 4 : 0);
+                PROF(cQKV, hipt_seqgemm_launch(q, !r.have_xn, 0, st));
+                // (with activation images the attention output is one too: proj then reads its operands 1 KiB at a time)
+                PROF(cATTN, hipt_attention_launch(s.qkv, att_two, last_probs ? probs : nullptr, nseq, w->ntok, w->heads, dh, scale, dt, st, r.img ? 1 : 0, r.hm ? 1 : 0));
             }
-            att_rows = s.qkv;
+            if (last_probs) break;
+            if (!k.fold) {
+                qkv_from_xn(q, att_out);
+                q.W = b.proj_w; q.wpk = b.proj_pk; q.N = D; q.bias = b.proj_b; q.out = s.xn; q.ldc = D;
+                q.counter = s.queues->aux;
+                q.img = r.img ? 3 : 0;  // A = the attention output image, out = y1 image
+                PROF(cPROJ, hipt_seqgemm_launch(q, false, 0, st));
+            }
+            MlpParams m = mlp_params(w, i, M, x, s);
+            if (k.fold) m.y1 = att_out;
+            m.fold = k.fold ? 1 : 0;
+            m.counter_zeroed = qz;
+            r.have_xn = r.chain && (i + 1 < r.b1 || r.emit_last) && i + 1 < w->depth;
+            if (r.have_xn) mlp_emit_xn(m, w->blocks[i + 1], s.att);
+            if (r.img) {
+                m.img = r.x_img ? 3 : 1;
+                r.x_img = true;
+            }
+            PROF(cMLP, hipt_mlp_launch(m, st));
+            continue;
+        }
+        // (small calls: both LayerNorms run in the prologue of the GEMM that consumes them -- five launches a block instead of seven)
+        // (the kernel loads gamma / beta 16 bytes at a time: parameters that are views into a flat buffer off that grid keep the
+        //  separate LayerNorm launch, which has no alignment requirement)
+        const bool ln_al = (((uintptr_t)b.ln1_w | (uintptr_t)b.ln1_b | (uintptr_t)b.ln2_w | (uintptr_t)b.ln2_b) & 15) == 0;
+        const bool ln_in_gemm = r.small && ln_al && !hipt_generic_only() && hipt_gemm_ln_supported(M, D, ALOAD_PLAIN, 0, r.force_small);
+        // a Linear of this path: one M tile per sequence, a residual update of x under HIPT_EPI_RESID
+        auto lin = [&](int cat, GemmParams g, int flags) -> int {
+            g.rpt = w->ntok;
+            g.small_any = r.force_small ? 1 : 0;
+            if (flags & HIPT_EPI_RESID) g.resid = x;
+            PROF(cat, linear(g, dt, flags, st));
+            return HIPT_OK;
+        };
+        // the same over LayerNorm(x; lw, lb): in the GEMM's prologue (g.A = x), or by a launch of its own into s.xn
+        auto ln_lin = [&](int cat, const float* lw, const float* lb, GemmParams g, int flags) -> int {
+            if (ln_in_gemm) {
+                g.ln_w = lw; g.ln_b = lb; g.ln_eps = w->ln_eps;
+            } else {
+                PROF(PC_LN, hipt_layernorm_launch(x, D, lw, lb, s.xn, dt, D, M, D, w->ln_eps, st));
+                g.A = s.xn;
+            }
+            return lin(cat, g, flags);
+        };
+        const int H = w->hidden;
+        if ((rc = ln_lin(PC_QKV, b.ln1_w, b.ln1_b, gemm_params(x, D, b.qkv_w, D, b.qkv_b, s.qkv, 3 * D, M, 3 * D, D), 0))) return rc;
+        PROF(PC_ATTN, hipt_attention_launch(s.qkv, s.att, last_probs ? probs : nullptr, nseq, w->ntok, w->heads, dh, scale, dt, st));
+        if (last_probs) break;  // Block.forward(return_attention=True) returns before the residual (:148-149)
+        if ((rc = lin(PC_PROJ, gemm_params(s.att, D, b.proj_w, D, b.proj_b, x, D, M, D, D), HIPT_EPI_RESID | HIPT_EPI_OUT_F32))) return rc;
+        if ((rc = ln_lin(PC_FC1, b.ln2_w, b.ln2_b, gemm_params(x, D, b.fc1_w, D, b.fc1_b, s.hid, H, M, H, D), HIPT_EPI_GELU))) return rc;
+        if ((rc = lin(PC_FC2, gemm_params(s.hid, H, b.fc2_w, H, b.fc2_b, x, D, M, D, H), HIPT_EPI_RESID | HIPT_EPI_OUT_F32))) return rc;
+    }
+    return HIPT_OK;
+}
+
+// Last block when only the [CLS] row is consumed afterwards (VitRoute::prune): the attention of one query per (sequence, head), then
+// proj / residual / MLP on nseq rows instead of nseq * ntok (allowed, and the pruned FLOP figure is the one the
+// roofline uses).  Leaves the final residual rows compact in s.xc [nseq, D].
+// (its [CLS]-row launches are booked apart: the per-kernel categories then hold full-size launches only)
+static int run_last_block_cls(const hipt_vit_weights* w, float* x, int nseq, const BlockScratch& s, const VitRoute& r, hipStream_t st) {
+    const int D = w->dim, M = nseq * w->ntok, dt = w->dtype, last = w->depth - 1;
+    const hipt_block_weights& b = w->blocks[last];
+    const float scale = attn_scale(w);
+    const BlockRoute k = block_route(r, b, false);
+    int rc;
+    const void* att_rows = s.att;  // [nseq, D] bf16: the attention output of the [CLS] tokens
+    if (k.fuse) {
+        // The fused kernel's [CLS]-only form: K and V of every token are computed per (patch, head) and consumed in place by the one
+        // query of the patch; q | k | v of the [CLS] rows themselves from the side GEMM, as in the other blocks.  Output: the
+        // attention rows of the [CLS] tokens, compact, in the (unused) qkv slot.
+        PROF(PC_LASTCLS, hipt_gather_cls_bf16_launch(s.att, s.cls_xn, nseq, w->ntok, D, st, 1));
+        if (k.absorb) {
+            // Q rows, u, ONE streaming pass over the xn image, o.  The same kernels whatever the call's size or company: rows_linear is
+            // row independent bit for bit, a patch is one work unit.
+            const int HD = w->heads * D;
+            const char* wu = (const char*)b.qkv_att_pk + hipt_qkv_attn_packed_bytes();
+            const char* wo = wu + (size_t)HD * D * 2;
+            PROF(PC_LASTCLS, cls_rows_qkv(w, b, nseq, D, s, 0, st));
+            PROF(PC_LASTCLS, rows_linear(gemm_params(s.cls_qkv, D, wu, D, nullptr, s.u, HD, nseq, HD, D), dt, HIPT_EPI_OUT_F32, st));
+            PROF(PC_LASTCLS, hipt_cls_pool_launch(s.att, (const float*)s.u, s.z, nseq, scale, st));
+            PROF(PC_LASTCLS, rows_linear(gemm_params(s.z, HD, wo, HD, b.qkv_b + 2 * D, s.qkv, D, nseq, D, HD), dt, 0, st));
         } else {
+            PROF(PC_LASTCLS, cls_rows_qkv(w, b, nseq, 3 * D, s, 0, st));
+            PROF(PC_LASTCLS, hipt_qkv_attn_cls_launch(s.att, b.qkv_att_pk, b.qkv_b, s.cls_qkv, s.qkv, nseq, scale, st));
+        }
+        att_rows = s.qkv;
+    } else {
+        SeqGemmParams q = qkv_params(w, last, M, x, s);
+        if (r.have_xn) {  // LayerNorm-1 already applied by the previous block's MLP epilogue (bf16 operands in s.att)
             // Only token 0 of a sequence asks a question in this block: K and V for every row (columns 384.. of the QKV Linear: the
             // weight image of an N tile is the 98 304 bytes of its rows, so the tail of the image IS the [K; V] matrix), Q for the
             // [CLS] rows alone -- their operands gathered into the free hidden slot, a [nseq, 384] GEMM scattered to rows s * ntok
-            bf16_t* qa = (bf16_t*)((char*)s.hid + 4096 + al256((size_t)nseq * D * 4));
-            PROF(PC_LASTCLS, hipt_gather_cls_bf16_launch(s.att, qa, nseq, w->ntok, D, st, x_img ? 1 : 0));
+            PROF(PC_LASTCLS, hipt_gather_cls_bf16_launch(s.att, s.cls_xn, nseq, w->ntok, D, st, r.x_img ? 1 : 0));
             const size_t wq = (size_t)D * D * 2;
+            qkv_from_xn(q, s.att);
+            q.img = r.x_img ? 1 : 0;  // (x and the operands s.att change layout together)
             q.W = (const char*)b.qkv_w + wq; q.wpk = b.qkv_pk ? (const char*)b.qkv_pk + wq : nullptr; q.N = 2 * D; q.bias = b.qkv_b + D;
             q.out = (bf16_t*)s.qkv + D;
-            PROF(PC_LASTCLS, hipt_seqgemm_launch(q, false, 0, st));  // (booked apart: the QKV category holds full-size launches only)
-            q.img = 0;
-            q.M = nseq; q.A = qa; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = D; q.bias = b.qkv_b; q.out = s.qkv; q.ldc = w->ntok * 3 * D;
-            q.counter = (int*)s.hid + 32;
             PROF(PC_LASTCLS, hipt_seqgemm_launch(q, false, 0, st));
-            q.M = M; q.ldc = 3 * D;
+            q.img = 0;
+            q.M = nseq; q.A = s.cls_xn; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = D; q.bias = b.qkv_b; q.out = s.qkv; q.ldc = w->ntok * 3 * D;
+            q.counter = s.queues->aux;
+            PROF(PC_LASTCLS, hipt_seqgemm_launch(q, false, 0, st));
+        } else {
+            PROF(PC_QKV, hipt_seqgemm_launch(q, true, 0, st));
         }
-        q.img = 0;
-    } else {
-        PROF(PC_QKV, hipt_seqgemm_launch(q, true, 0, st));
+        PROF(PC_LASTCLS, hipt_attn_cls_launch(s.qkv, s.att, nullptr, nseq, w->ntok, w->heads, D / w->heads, scale, st));
     }
-    // (the [CLS]-row launches of the pruned block are booked apart: the per-kernel categories then hold full-size launches only)
-    if (!att_rows) {
-        PROF(PC_LASTCLS, hipt_attn_cls_launch(s.qkv, s.att, nullptr, nseq, w->ntok, w->heads, D / w->heads, attn_scale(w), st));
-        att_rows = s.att;
-    }
-    PROF(PC_OTHER, hipt_gather_cls_launch(x, xc, nseq, (int64_t)w->ntok * D, D, st, x_img ? 1 : 0));
+    PROF(PC_OTHER, hipt_gather_cls_launch(x, s.xc, nseq, (int64_t)w->ntok * D, D, st, r.x_img ? 1 : 0));
     // (nseq rows: the generic GEMM tiles N as well -- see the side GEMM of the fused blocks)
-    PROF(PC_LASTCLS, rows_linear(att_rows, D, b.proj_w, D, b.proj_b, s.xn, D, nseq, D, D, w->dtype, st));
-    MlpParams m;
-    memset(&m, 0, sizeof(m));
-    m.x = xc; m.y1 = s.xn; m.ln_w = b.ln2_w; m.ln_b = b.ln2_b; m.ln_eps = w->ln_eps;
-    m.w1 = b.fc1_w; m.b1 = b.fc1_b; m.w2 = b.fc2_w; m.b2 = b.fc2_b; m.wpk = b.mlp_pk; m.wpk_fmt = b.mlp_pk_fmt; m.M = nseq; m.D = D; m.hidden = w->hidden;
-    m.counter = (int*)s.hid;
-    PROF(PC_LASTCLS, hipt_mlp_launch(m, st));
+    PROF(PC_LASTCLS, rows_linear(gemm_params(att_rows, D, b.proj_w, D, b.proj_b, s.xn, D, nseq, D, D), dt, 0, st));
+    PROF(PC_LASTCLS, hipt_mlp_launch(mlp_params(w, last, nseq, s.xc, s), st));
     return HIPT_OK;
 }
 
 int64_t image_elems(const hipt_image_layout* lay, int nseq_total) {
     const int per = lay->grid_w * lay->grid_h;
     return (int64_t)((nseq_total + per - 1) / per) * lay->batch_stride;
+}
+
+// input image kinds: fp32 [.., 3, W, H], or uint8 in the same layout / interleaved [.., W, H, 3] (normalised on device)
+enum { IMG_F32 = 0, IMG_U8_CHW = 1, IMG_U8_HWC = 2 };
+
+// the image tensor in the compute dtype: bf16 mode holds a bf16 image, fp32 mode an fp32 one for uint8 input, and none where fp32
+// input is used where it lies
+size_t image_compute_bytes(const hipt_vit_weights* w, const hipt_image_layout* lay, int nseq, int kind) {
+    const size_t n = (size_t)image_elems(lay, nseq);
+    return w->dtype == HIPT_BF16 ? al256(n * 2) : kind != IMG_F32 ? al256(n * 4) : 0;
 }
 
 // tokens of sequences [seq0, seq0+nseq) from an image tensor already in the compute dtype
@@ -417,24 +476,10 @@ int embed256(const hipt_vit_weights* w, const void* img, const hipt_image_layout
     const int nty = lay->patch_h / 16, ntx = lay->patch_w / 16;
     HIPT_CHECK_ARG(nty * ntx + 1 == w->ntok, "vit256: image gives %d tokens, weights expect %d", nty * ntx + 1, w->ntok);
     HIPT_CHECK_ARG(w->embed_k == 768, "vit256: embed_k must be 768 (3x16x16)");
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = img;
-    p.W = w->embed_w;
-    p.ldw = w->embed_k;
-    p.M = nseq * nty * ntx;
-    p.N = w->dim;
-    p.K = w->embed_k;
-    p.bias = w->embed_b;
-    p.out = x;
-    p.ldc = w->dim;
+    GemmParams p = gemm_params(img, 0, w->embed_w, w->embed_k, w->embed_b, x, w->dim, nseq * nty * ntx, w->dim, w->embed_k);
     p.pos = w->pos;
-    p.rows_per_seq = nty * ntx;
-    p.rpt = nty * ntx;
-    p.im = *lay;
-    p.im_nty = nty;
-    p.im_ntx = ntx;
-    p.im_seq0 = seq0;
+    p.rows_per_seq = p.rpt = nty * ntx;
+    p.im = *lay; p.im_nty = nty; p.im_ntx = ntx; p.im_seq0 = seq0;
     int rc;
     PROF(PC_EMBED, hipt_gemm_launch(p, w->dtype, ALOAD_IM2COL, HIPT_EPI_OUT_F32 | EPI_ROWMAP, st));
     PROF(PC_OTHER, hipt_cls_init_launch(x, w->cls, w->pos, nseq, w->ntok, w->dim, st));
@@ -442,9 +487,9 @@ int embed256(const hipt_vit_weights* w, const void* img, const hipt_image_layout
 }
 
 // may the embedding read fp32 pixels itself (embed32.hip)?  `slot` bytes are available for its packed weight + tile queue
-static bool embed_fused_ok(const hipt_vit_weights* w, const void* images, const hipt_image_layout* lay, size_t slot, int kind = 0) {
+static bool embed_fused_ok(const hipt_vit_weights* w, const void* images, const hipt_image_layout* lay, size_t slot, int kind = IMG_F32) {
     // (uint8: 8-byte pixel runs; interleaved tensors are whole [n, W, H, 3] images: batch_stride = 3 * chan_stride)
-    if (kind != 0 && (lay->row_stride % 8 != 0 || lay->chan_stride % 8 != 0 || lay->batch_stride != 3 * lay->chan_stride))
+    if (kind != IMG_F32 && (lay->row_stride % 8 != 0 || lay->chan_stride % 8 != 0 || lay->batch_stride != 3 * lay->chan_stride))
         return false;
     return lay->patch_w % 16 == 0 && lay->patch_h % 16 == 0 &&
            hipt_embed32_supported(w->dtype, w->dim, w->embed_k, lay->patch_h / 16, lay->patch_w / 16) &&
@@ -452,67 +497,98 @@ static bool embed_fused_ok(const hipt_vit_weights* w, const void* images, const 
            lay->row_stride % 4 == 0 && lay->chan_stride % 4 == 0 && lay->batch_stride % 4 == 0;
 }
 
-// the same from the fp32 image itself (embed32.hip): `wpk` = the packed Conv2d weight, `counter` = the kernel's tile queue
-// xn_img != null: x leaves as the fp32 activation image and LayerNorm-1 of the first block as the bf16 image xn_img (run_blocks: xn_ready)
-int embed256_f32(const hipt_vit_weights* w, const void* img, const hipt_image_layout* lay, int seq0, int nseq, float* x, const void* wpk,
-                 int* counter, hipStream_t st, int kind = 0, void* xn_img = nullptr) {
+// the same from the fp32 / uint8 image itself (embed32.hip): `wpk` = the packed Conv2d weight with the kernel's tile queue behind it
+// xn_img != null: x leaves as the fp32 activation image and LayerNorm-1 of the first block as the bf16 image xn_img (VitRoute::pre)
+int embed256_px(const hipt_vit_weights* w, const void* img, int kind, const hipt_image_layout* lay, int seq0, int nseq, float* x, const void* wpk,
+                void* xn_img, hipStream_t st) {
     EmbedParams p;
     memset(&p, 0, sizeof(p));
-    p.img = img;
-    p.kind = kind;
-    p.im = *lay;
-    p.nty = lay->patch_h / 16;
-    p.ntx = lay->patch_w / 16;
-    p.seq0 = seq0;
-    p.nseq = nseq;
-    p.wpk = wpk;
-    p.bias = w->embed_b;
-    p.pos = w->pos;
-    p.x = x;
-    p.ntok = w->ntok;
-    p.counter = counter;
-    int rc;
+    p.img = img; p.kind = kind; p.im = *lay; p.nty = lay->patch_h / 16; p.ntx = lay->patch_w / 16; p.seq0 = seq0; p.nseq = nseq;
+    p.wpk = wpk; p.bias = w->embed_b; p.pos = w->pos; p.x = x; p.ntok = w->ntok;
+    p.counter = (int*)((char*)wpk + hipt_embed32_packed_bytes());
     if (xn_img) {
-        p.xn_out = xn_img;
-        p.ln_w = w->blocks[0].ln1_w;
-        p.ln_b = w->blocks[0].ln1_b;
-        p.ln_eps = w->ln_eps;
-        PROF(PC_EMBED, hipt_embed32_launch(p, st));
-        PROF(PC_OTHER, hipt_cls_init_img_launch(x, xn_img, w->cls, w->pos, p.ln_w, p.ln_b, p.ln_eps, nseq, w->ntok, w->dim, st));
-        return HIPT_OK;
+        p.xn_out = xn_img; p.ln_w = w->blocks[0].ln1_w; p.ln_b = w->blocks[0].ln1_b; p.ln_eps = w->ln_eps;
     }
+    int rc;
     PROF(PC_EMBED, hipt_embed32_launch(p, st));
-    PROF(PC_OTHER, hipt_cls_init_launch(x, w->cls, w->pos, nseq, w->ntok, w->dim, st));
+    if (xn_img)
+        PROF(PC_OTHER, hipt_cls_init_img_launch(x, xn_img, w->cls, w->pos, p.ln_w, p.ln_b, p.ln_eps, nseq, w->ntok, w->dim, st));
+    else
+        PROF(PC_OTHER, hipt_cls_init_launch(x, w->cls, w->pos, nseq, w->ntok, w->dim, st));
     return HIPT_OK;
 }
 
 int embed4k(const hipt_vit_weights* w, const void* tokens, int nseq, float* x, hipStream_t st, int small_any = 0) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
+    const int K = w->embed_k;
+    GemmParams p = gemm_params(tokens, K, w->embed_w, K, w->embed_b, x, w->dim, nseq * (w->ntok - 1), w->dim, K);
     p.small_any = small_any;
-    p.A = tokens;
-    p.lda = w->embed_k;
-    p.W = w->embed_w;
-    p.ldw = w->embed_k;
-    p.M = nseq * (w->ntok - 1);
-    p.N = w->dim;
-    p.K = w->embed_k;
-    p.bias = w->embed_b;
-    p.out = x;
-    p.ldc = w->dim;
     p.pos = w->pos;
-    p.rows_per_seq = w->ntok - 1;
-    p.rpt = w->ntok - 1;
+    p.rows_per_seq = p.rpt = w->ntok - 1;
     int rc = HIPT_OK;
     if (p.M > 0) PROF(PC_EMBED, hipt_gemm_launch(p, w->dtype, ALOAD_PLAIN, HIPT_EPI_GELU | HIPT_EPI_OUT_F32 | EPI_ROWMAP, st));
     PROF(PC_OTHER, hipt_cls_init_launch(x, w->cls, w->pos, nseq, w->ntok, w->dim, st));
     return HIPT_OK;
 }
 
-int default_chunk(int nseq) { return nseq < 2048 ? nseq : 2048; }
+// ---- the workspaces of the forwards ---------------------------------------------------------------------------------------------
+// ViT-4K forward: the residual stream (with_x) | block scratch | the bf16 copy of the input tokens (the only extra of the prepare_tokens calls)
+struct Vit4kWs { float* x; BlockScratch s; void* tok; };
+Vit4kWs carve_vit4k(Carver& c, const hipt_vit_weights* w, int nseq, bool with_x) {
+    Vit4kWs k;
+    k.x = with_x ? (float*)c.take((size_t)nseq * w->ntok * w->dim * 4) : nullptr;
+    k.s = carve_blocks(c, w, nseq);
+    k.tok = c.take((size_t)nseq * w->ntok * w->embed_k * 2);
+    return k;
+}
 
-// input image kinds: fp32 [.., 3, W, H], or uint8 in the same layout / interleaved [.., W, H, 3] (normalised on device)
-enum { IMG_F32 = 0, IMG_U8_CHW = 1, IMG_U8_HWC = 2 };
+// ViT-256 over a range of sequences, `chunk` at a time (<= 0: 2 048): the residual stream of one chunk + its block scratch
+struct RangeWs { int chunk; float* x; BlockScratch s; };
+int default_chunk(int nseq) { return nseq < 2048 ? nseq : 2048; }
+RangeWs carve_range(Carver& c, const hipt_vit_weights* w, int nseq, int chunk) {
+    RangeWs g;
+    if (chunk <= 0) chunk = default_chunk(nseq);
+    g.chunk = chunk < nseq ? chunk : nseq;
+    g.x = (float*)c.take((size_t)g.chunk * w->ntok * w->dim * 4);
+    g.s = carve_blocks(c, w, g.chunk);
+    return g;
+}
+
+// ... behind it one slot of `nslot` bytes: the image in the compute dtype, or the pixel-reading embedding's packed weight + tile queue
+struct Vit256Ws { void *range, *slot; size_t nrange, nslot; };
+Vit256Ws carve_vit256(Carver& c, const hipt_vit_weights* w, int nseq, int chunk, size_t nslot) {
+    Vit256Ws v;
+    v.nrange = dry_run([&](Carver& d) { carve_range(d, w, nseq, chunk); });
+    v.nslot = al256(nslot);
+    v.range = c.take(v.nrange);
+    v.slot = c.take(v.nslot);
+    return v;
+}
+inline size_t embed_px_slot_bytes() { return hipt_embed32_packed_bytes() + 256; }
+
+static hipt_image_layout region_layout(int W, int H) {
+    hipt_image_layout lay;
+    lay.grid_w = W / 256;
+    lay.grid_h = H / 256;
+    lay.patch_h = lay.patch_w = 256;
+    lay.row_stride = H;
+    lay.chan_stride = (int64_t)W * H;
+    lay.batch_stride = 3 * lay.chan_stride;
+    return lay;
+}
+
+// HIPT_4K over nreg regions of w_256 x h_256 patches: the [CLS] grid of the first level | ViT-256 forward | ViT-4K forward
+struct Hipt4kWs { float* cls; void *ws256, *ws4k; size_t n256, n4k; };
+Hipt4kWs carve_hipt4k(Carver& c, const hipt_vit_weights* w256, const hipt_vit_weights* w4k, int nreg, int w_256, int h_256, int chunk, int kind) {
+    const hipt_image_layout lay = region_layout(w_256 * 256, h_256 * 256);
+    const int nseq = nreg * w_256 * h_256;
+    Hipt4kWs h;
+    h.n256 = dry_run([&](Carver& d) { carve_vit256(d, w256, nseq, chunk, image_compute_bytes(w256, &lay, nseq, kind)); });
+    h.n4k = dry_run([&](Carver& d) { carve_vit4k(d, w4k, nreg, true); });
+    h.cls = (float*)c.take((size_t)nseq * w256->dim * 4);
+    h.ws256 = c.take(h.n256);
+    h.ws4k = c.take(h.n4k);
+    return h;
+}
 
 }  // namespace
 
@@ -567,7 +643,9 @@ int hipt_linear(const void* A, int64_t lda, const void* W, int64_t ldw, const fl
     HIPT_CHECK_ARG((flags & ~(HIPT_EPI_GELU | HIPT_EPI_RESID | HIPT_EPI_OUT_F32 | HIPT_EPI_RELU)) == 0, "linear: bad flags %d",
                    flags);
     HIPT_CHECK_ARG(!(flags & HIPT_EPI_RESID) || resid != nullptr, "linear: RESID without a residual pointer");
-    return linear(A, lda, W, ldw, bias, resid, out, ldc, M, N, K, dtype, flags, S(stream));
+    GemmParams p = gemm_params(A, lda, W, ldw, bias, out, ldc, M, N, K);
+    p.resid = resid;
+    return linear(p, dtype, flags, S(stream));
 }
 
 int hipt_attention(const void* qkv, void* out, float* probs, int B, int ntok, int heads, int dh, float scale, int dtype,
@@ -576,20 +654,15 @@ int hipt_attention(const void* qkv, void* out, float* probs, int B, int ntok, in
 }
 
 size_t hipt_vit_workspace_bytes(const hipt_vit_weights* w, int nseq) {
-    // block scratch; the 4K token conversion buffer is the only extra of the prepare_tokens calls
-    return block_scratch_bytes(w, nseq) + al256((size_t)nseq * w->ntok * w->embed_k * 2);
+    return dry_run([&](Carver& c) { carve_vit4k(c, w, nseq, false); });
 }
 
 size_t hipt_vit256_forward_workspace_bytes(const hipt_vit_weights* w, const hipt_image_layout* lay, int nseq, int chunk) {
-    if (chunk <= 0) chunk = default_chunk(nseq);
-    if (chunk > nseq) chunk = nseq;
-    size_t n = al256((size_t)chunk * w->ntok * w->dim * 4) + block_scratch_bytes(w, chunk);
-    if (w->dtype == HIPT_BF16) n += al256((size_t)image_elems(lay, nseq) * 2);
-    return n;
+    return dry_run([&](Carver& c) { carve_vit256(c, w, nseq, chunk, image_compute_bytes(w, lay, nseq, IMG_F32)); });
 }
 
 size_t hipt_vit4k_forward_workspace_bytes(const hipt_vit_weights* w, int nseq) {
-    return al256((size_t)nseq * w->ntok * w->dim * 4) + hipt_vit_workspace_bytes(w, nseq);
+    return dry_run([&](Carver& c) { carve_vit4k(c, w, nseq, true); });
 }
 
 int hipt_vit256_prepare_tokens(const hipt_vit_weights* w, const float* images, const hipt_image_layout* lay, int seq0,
@@ -600,13 +673,12 @@ int hipt_vit256_prepare_tokens(const hipt_vit_weights* w, const float* images, c
     const void* img = images;
     if (w->dtype == HIPT_BF16) {
         const int64_t n = image_elems(lay, seq0 + nseq);
-        if (ws_bytes < al256((size_t)n * 2) || ((uintptr_t)workspace & 255)) {
-            hipt_set_error("vit256_prepare_tokens: workspace %zu B too small / unaligned (need %zu)", ws_bytes, al256((size_t)n * 2));
-            return HIPT_E_WORKSPACE;
-        }
+        Carver c(workspace, ws_bytes);
+        c.take((size_t)n * 2);
+        if ((rc = check_workspace(c, "vit256_prepare_tokens"))) return rc;
         if (embed_fused_ok(w, images, lay, ws_bytes)) {
             if ((rc = hipt_embed32_pack_launch(w->embed_w, workspace, S(stream)))) return rc;
-            return embed256_f32(w, images, lay, seq0, nseq, x, workspace, (int*)((char*)workspace + hipt_embed32_packed_bytes()), S(stream));
+            return embed256_px(w, images, IMG_F32, lay, seq0, nseq, x, workspace, nullptr, S(stream));
         }
         if ((rc = hipt_f32_to_bf16_launch(images, workspace, n, S(stream)))) return rc;
         img = workspace;
@@ -622,10 +694,9 @@ int hipt_vit4k_prepare_tokens(const hipt_vit_weights* w, const float* tokens_in,
     const void* tok = tokens_in;
     const int64_t n = (int64_t)nseq * (w->ntok - 1) * w->embed_k;
     if (w->dtype == HIPT_BF16 && n > 0) {
-        if (ws_bytes < al256((size_t)n * 2) || ((uintptr_t)workspace & 255)) {
-            hipt_set_error("vit4k_prepare_tokens: workspace %zu B too small / unaligned (need %zu)", ws_bytes, al256((size_t)n * 2));
-            return HIPT_E_WORKSPACE;
-        }
+        Carver c(workspace, ws_bytes);
+        c.take((size_t)n * 2);
+        if ((rc = check_workspace(c, "vit4k_prepare_tokens"))) return rc;
         if ((rc = hipt_f32_to_bf16_launch(tokens_in, workspace, n, S(stream)))) return rc;
         tok = workspace;
     }
@@ -640,11 +711,9 @@ int hipt_vit_blocks(const hipt_vit_weights* w, float* x, int nseq, int blk_begin
                    blk_begin, blk_end);
     Carver c(workspace, ws_bytes);
     BlockScratch s = carve_blocks(c, w, nseq);
-    if (!c.ok()) {
-        hipt_set_error("vit_blocks: workspace %zu B too small / unaligned (need %zu)", ws_bytes, c.used);
-        return HIPT_E_WORKSPACE;
-    }
-    return run_blocks(w, x, nseq, blk_begin, blk_end, probs, s, S(stream));
+    if ((rc = check_workspace(c, "vit_blocks"))) return rc;
+    VitRoute r = vit_route(w, nseq, blk_begin, blk_end, probs != nullptr, 0);
+    return run_blocks(w, x, nseq, probs, s, r, S(stream));
 }
 
 // the [CLS] row of the last block's attention map, probs_cls[nseq, heads, ntok], without the
@@ -654,35 +723,28 @@ int hipt_vit_cls_attention(const hipt_vit_weights* w, float* x, int nseq, float*
     int rc = check_vit(w);
     if (rc) return rc;
     HIPT_CHECK_ARG(x && probs_cls && nseq > 0, "vit_cls_attention: null/empty argument");
-    const int D = w->dim, dh = D / w->heads, M = nseq * w->ntok;
+    const int D = w->dim, dh = D / w->heads, M = nseq * w->ntok, last = w->depth - 1;
     Carver c(workspace, ws_bytes);
     BlockScratch s = carve_blocks(c, w, nseq);
-    if (!c.ok()) {
-        hipt_set_error("vit_cls_attention: workspace %zu B too small / unaligned (need %zu)", ws_bytes, c.used);
-        return HIPT_E_WORKSPACE;
-    }
+    if ((rc = check_workspace(c, "vit_cls_attention"))) return rc;
     hipStream_t st = S(stream);
-    const hipt_block_weights& b = w->blocks[w->depth - 1];
-    if (w->dtype == HIPT_BF16 && dh == 64 && hipt_seqgemm_supported(w->dtype, D)) {  // ViT-256 hot case: chained kernels
-        bool have_xn = false;
-        if ((rc = run_blocks(w, x, nseq, 0, w->depth - 1, nullptr, s, st, true, &have_xn))) return rc;
-        SeqGemmParams q;
-        memset(&q, 0, sizeof(q));
-        q.M = M; q.K = D; q.ln_eps = w->ln_eps;
-        q.A = x; q.lda = D; q.ln_w = b.ln1_w; q.ln_b = b.ln1_b; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = 3 * D; q.bias = b.qkv_b;
-        q.out = s.qkv; q.ldc = 3 * D;
-        q.counter = (int*)s.hid + 16;
-        if (have_xn) {
-            q.A = s.att; q.ln_w = q.ln_b = nullptr;
-        }
-        if ((rc = hipt_seqgemm_launch(q, !have_xn, 0, st))) return rc;
+    // ViT-256 hot case: the A-stationary QKV GEMM (LayerNorm-1 from the chained MLP before it where there is one) + the one-query kernel
+    const bool hot = w->dtype == HIPT_BF16 && dh == 64 && hipt_seqgemm_supported(w->dtype, D);
+    VitRoute r = vit_route(w, nseq, 0, last, false, hot ? RT_EMIT_LAST : 0);
+    if ((rc = run_blocks(w, x, nseq, nullptr, s, r, st))) return rc;
+    if (hot) {
+        SeqGemmParams q = qkv_params(w, last, M, x, s);
+        if (r.have_xn) qkv_from_xn(q, s.att);
+        if ((rc = hipt_seqgemm_launch(q, !r.have_xn, 0, st))) return rc;
         return hipt_attn_cls_launch(s.qkv, nullptr, probs_cls, nseq, w->ntok, w->heads, dh, attn_scale(w), st);
     }
-    // every other configuration (fp32; head dim 32 = ViT-4K): the blocks before the last, then LayerNorm-1 + the QKV
-    // projection of the last one and the probabilities of the [CLS] query from the one-query kernel
-    if ((rc = run_blocks(w, x, nseq, 0, w->depth - 1, nullptr, s, st))) return rc;
+    // every other configuration (fp32; head dim 32 = ViT-4K): LayerNorm-1 + the QKV projection of the last block and the
+    // probabilities of the [CLS] query from the one-query kernel
+    const hipt_block_weights& b = w->blocks[last];
+    GemmParams g = gemm_params(s.xn, D, b.qkv_w, D, b.qkv_b, s.qkv, 3 * D, M, 3 * D, D);
+    g.rpt = w->ntok;
     if ((rc = hipt_layernorm_launch(x, D, b.ln1_w, b.ln1_b, s.xn, w->dtype, D, M, D, w->ln_eps, st))) return rc;
-    if ((rc = linear(s.xn, D, b.qkv_w, D, b.qkv_b, nullptr, s.qkv, 3 * D, M, 3 * D, D, w->dtype, 0, st, w->ntok))) return rc;
+    if ((rc = linear(g, w->dtype, 0, st))) return rc;
     return hipt_attn_cls_probs_launch(s.qkv, probs_cls, nseq, w->ntok, w->heads, dh, attn_scale(w), w->dtype, st);
 }
 
@@ -698,28 +760,21 @@ int hipt_vit_attention_unit(const hipt_vit_weights* w, int block, const void* xn
     }
     Carver c(workspace, ws_bytes);
     BlockScratch s = carve_blocks(c, w, nseq);
-    if (!c.ok()) {
-        hipt_set_error("vit_attention_unit: workspace %zu B too small / unaligned (need %zu)", ws_bytes, c.used);
-        return HIPT_E_WORKSPACE;
-    }
+    if ((rc = check_workspace(c, "vit_attention_unit"))) return rc;
     hipStream_t st = S(stream);
     const hipt_block_weights& b = w->blocks[block];
-    SeqGemmParams q;
-    memset(&q, 0, sizeof(q));
-    q.K = D; q.lda = D; q.W = b.qkv_w; q.wpk = b.qkv_pk; q.N = 3 * D; q.bias = b.qkv_b; q.ldc = 3 * D; q.out_ntok = w->ntok;
-    q.counter = (int*)s.hid;
+    SeqGemmParams q = qkv_params(w, block, M, nullptr, s);
+    qkv_from_xn(q, xn_img);
     HIPT_CHECK_ARG(b.qkv_pk != nullptr, "vit_attention_unit: blocks[%d].qkv_pk is NULL", block);
     if (fused) {
         HIPT_CHECK_ARG(b.qkv_att_pk != nullptr, "vit_attention_unit: blocks[%d].qkv_att_pk is NULL", block);
-        char* qa = (char*)s.hid + 4096;
-        char* qcls = qa + al256((size_t)nseq * D * 2);
-        if ((rc = hipt_gather_cls_bf16_launch(xn_img, qa, nseq, w->ntok, D, st, 1))) return rc;
-        q.M = nseq; q.A = qa; q.out = qcls;
+        if ((rc = hipt_gather_cls_bf16_launch(xn_img, s.cls_xn, nseq, w->ntok, D, st, 1))) return rc;
+        q.M = nseq; q.A = s.cls_xn; q.out = s.cls_qkv;
         if ((rc = hipt_seqgemm_launch(q, false, 0, st))) return rc;
-        return hipt_qkv_attn_launch(xn_img, b.qkv_att_pk, b.qkv_b, qcls, out_img, nseq, attn_scale(w), st);
+        return hipt_qkv_attn_launch(xn_img, b.qkv_att_pk, b.qkv_b, s.cls_qkv, out_img, nseq, attn_scale(w), st);
     }
     const bool hm = (int64_t)M * 3 * D * 2 < ((int64_t)1 << 32) - 65536;
-    q.M = M; q.A = xn_img; q.out = s.qkv; q.img = 1 | (hm ? 4 : 0);
+    q.img = 1 | (hm ? 4 : 0);
     if ((rc = hipt_seqgemm_launch(q, false, 0, st))) return rc;
     return hipt_attention_launch(s.qkv, out_img, nullptr, nseq, w->ntok, w->heads, D / w->heads, attn_scale(w), w->dtype, st, 1, hm ? 1 : 0);
 }
@@ -739,27 +794,22 @@ int hipt_vit_mlp_unit(const hipt_vit_weights* w, int block, float* x_img, const 
         hipt_set_error("vit_mlp_unit: workspace %zu B too small / unaligned (need 256)", ws_bytes);
         return HIPT_E_WORKSPACE;
     }
-    MlpParams m;
-    memset(&m, 0, sizeof(m));
-    m.x = x_img; m.y1 = att_img; m.fold = 1; m.bproj = b.proj_b;
-    m.ln_w = b.ln2_w; m.ln_b = b.ln2_b; m.ln_eps = w->ln_eps;
-    m.w1 = b.fc1_w; m.b1 = b.fc1_b; m.w2 = b.fc2_w; m.b2 = b.fc2_b; m.wpk = b.mlp_pk; m.wpk_fmt = b.mlp_pk_fmt; m.M = M; m.D = D; m.hidden = w->hidden;
-    m.counter = (int*)workspace;
+    BlockScratch s = {};
+    s.queues = (TileQueues*)workspace;  // (the one queue it needs: the first line of the 256 bytes)
+    MlpParams m = mlp_params(w, block, M, x_img, s);
+    m.y1 = att_img;
+    m.fold = 1;
     m.img = 3;
-    if (xn_out_img) {
-        const hipt_block_weights& nb = w->blocks[block + 1 < w->depth ? block + 1 : block];
-        m.ln_next_w = nb.ln1_w; m.ln_next_b = nb.ln1_b; m.xn_out = xn_out_img;
-    }
+    if (xn_out_img) mlp_emit_xn(m, w->blocks[block + 1 < w->depth ? block + 1 : block], xn_out_img);
     hipStream_t st = S(stream);
     PROF(PC_MLP, hipt_mlp_launch(m, st));
     return HIPT_OK;
 }
 
-// Format of the fused MLP's weight image: 2 = csrc/mlp16.hip (16x16x32 MFMAs), 0 = this shape has no packed form.  (Format 1 was the
-// 32x32x16 form of rounds 2-4, tools/experiments/mlp32_r4.hip: a tie on the MLP launches themselves, 3 % behind on the kernels that run
-// between them -- DESIGN.md -- and retired in round 5; an image packed as format 1 is refused by the chain test in run_blocks and its
-// model falls back to the generic kernels.)
-// 3 (round 5, what this version packs) = format 2 behind six units of the proj matrix: the attention block's output projection then runs at the
+// Format of the fused MLP's weight image: 2 = csrc/mlp16.hip (16x16x32 MFMAs), 0 = this shape has no packed form.  (Format 1 was a
+// 32x32x16 form, tools/experiments/mlp32_r4.hip, since retired -- DESIGN.md; an image packed as format 1 is refused by blocks_chain
+// and its model falls back to the generic kernels.)
+// 3 (what this version packs) = format 2 behind six units of the proj matrix: the attention block's output projection then runs at the
 // head of the fused MLP's tiles (mlp16.hip, FOLD) and the chained blocks have no proj launch.  HIPT_NO_PROJ_FOLD=1 at LAUNCH time runs proj as its
 // own kernel again from the same image (the MLP's own units lie behind the proj units); an image packed as format 2 by an older binding still runs.
 int hipt_vit_mlp_pack_format(const hipt_vit_weights* w) { return w && hipt_mlp16_supported(w->dtype, w->dim, w->hidden) ? 3 : 0; }
@@ -813,60 +863,36 @@ int hipt_vit_head(const hipt_vit_weights* w, const float* x, int nseq, int cls_o
     return hipt_layernorm_launch(x, D, w->norm_w, w->norm_b, out, HIPT_F32, D, nseq * w->ntok, D, w->ln_eps, S(stream));
 }
 
-// images: fp32 [.., 3, W, H] (kind 0), or uint8 in the same layout (kind 1) / interleaved [.., W, H, 3] (kind 2), which
-// are normalised on device into the compute dtype
-
-static size_t image_extra_bytes(const hipt_vit_weights* w, const hipt_image_layout* lay, int nseq, int kind) {
-    // bf16 mode already holds a bf16 image in its workspace; fp32 mode needs an fp32 one for uint8 input
-    return (kind != IMG_F32 && w->dtype == HIPT_F32) ? al256((size_t)image_elems(lay, nseq) * 4) : 0;
-}
-
 // ViT-256 over the sequences [seq0, seq0 + nseq) of an image tensor that is ALREADY in the compute dtype, chunk by chunk:
-// out[i] = [CLS] feature of sequence seq0 + i.  Scratch: the residual stream of one chunk + its block scratch.
-// (embed_pk != null: `img` is the fp32 image and the embedding reads it directly -- embed32.hip; the tile queue sits behind the image)
+// out[i] = [CLS] feature of sequence seq0 + i.
+// (embed_pk != null: `img` is the fp32 / uint8 image and the embedding reads it directly -- embed32.hip)
 static int vit256_range_impl(const hipt_vit_weights* w, const void* img, const hipt_image_layout* lay, int seq0, int nseq, int chunk, float* out,
-                             void* workspace, size_t ws_bytes, hipStream_t st, const void* embed_pk = nullptr, int embed_kind = 0) {
+                             void* workspace, size_t ws_bytes, hipStream_t st, const void* embed_pk = nullptr, int embed_kind = IMG_F32) {
     int rc;
-    if (chunk <= 0) chunk = default_chunk(nseq);
-    if (chunk > nseq) chunk = nseq;
+    const int D = w->dim;
     Carver c(workspace, ws_bytes);
-    float* x = (float*)c.take((size_t)chunk * w->ntok * w->dim * 4);
-    BlockScratch s = carve_blocks(c, w, chunk);
-    if (!c.ok()) {
-        hipt_set_error("vit256_forward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, c.used);
-        return HIPT_E_WORKSPACE;
-    }
-    for (int s0 = 0; s0 < nseq; s0 += chunk) {
-        const int n = nseq - s0 < chunk ? nseq - s0 : chunk;
-        const bool prune = can_prune_last(w) && !small_call(w, n);
-        // the embedding hands the first block its operands as activation images when the blocks exchange images anyway (HIPT_NO_EMBED_LN: off)
-        const bool pre = embed_pk && prune && w->depth > 1 && blocks_images(w, n, 0, w->depth - 1) && !hipt_env_on("HIPT_NO_EMBED_LN");
-        if (embed_pk) {
-            if ((rc = embed256_f32(w, img, lay, seq0 + s0, n, x, embed_pk, (int*)((char*)embed_pk + hipt_embed32_packed_bytes()), st, embed_kind, pre ? s.att : nullptr)))
-                return rc;
-        } else if ((rc = embed256(w, img, lay, seq0 + s0, n, x, st))) {
-            return rc;
+    const RangeWs g = carve_range(c, w, nseq, chunk);
+    if ((rc = check_workspace(c, "vit256_forward"))) return rc;
+    for (int s0 = 0; s0 < nseq; s0 += g.chunk) {
+        const int n = nseq - s0 < g.chunk ? nseq - s0 : g.chunk;
+        VitRoute r = vit_route(w, n, 0, w->depth, false, RT_CLS_ONLY | (embed_pk ? RT_PX_EMBED : 0));
+        if (r.prune && !(r.chain ? g.s.fits_cls_xn : g.s.fits_xc)) {
+            hipt_set_error("vit256_forward: %d tokens x hidden %d leave no room in the block scratch for the [CLS] rows of the pruned last block "
+                           "(HIPT_NO_PRUNE=1 runs it in full)", w->ntok, w->hidden);
+            return HIPT_E_WORKSPACE;
         }
-        if (prune) {
-            float* xc = (float*)((char*)s.hid + 4096);  // (the hidden-tensor slot is free on this path; its head holds tile queues)
-            bool have_xn = false, x_img = false;  // (x is this function's own buffer: it may come back as an activation image)
-            if ((rc = run_blocks(w, x, n, 0, w->depth - 1, nullptr, s, st, true, &have_xn, true, &x_img, pre))) return rc;
-            if ((rc = run_last_block_cls(w, x, n, s, xc, have_xn, x_img, st))) return rc;
-            PROF(PC_LN, hipt_layernorm_launch(xc, w->dim, w->norm_w, w->norm_b, out + (size_t)s0 * w->dim, HIPT_F32, w->dim, n, w->dim,
-                                              w->ln_eps, st));
-        } else {
-            if ((rc = run_blocks(w, x, n, 0, w->depth, nullptr, s, st))) return rc;
-            PROF(PC_LN, hipt_layernorm_launch(x, (int64_t)w->ntok * w->dim, w->norm_w, w->norm_b, out + (size_t)s0 * w->dim, HIPT_F32,
-                                              w->dim, n, w->dim, w->ln_eps, st));
-        }
+        if (embed_pk)
+            rc = embed256_px(w, img, embed_kind, lay, seq0 + s0, n, g.x, embed_pk, r.pre ? g.s.att : nullptr, st);
+        else
+            rc = embed256(w, img, lay, seq0 + s0, n, g.x, st);
+        if (rc) return rc;
+        if ((rc = run_blocks(w, g.x, n, nullptr, g.s, r, st))) return rc;
+        if (r.prune && (rc = run_last_block_cls(w, g.x, n, g.s, r, st))) return rc;
+        // the [CLS] rows: compact after the pruned block, row 0 of every sequence otherwise
+        PROF(PC_LN, hipt_layernorm_launch(r.prune ? g.s.xc : g.x, r.prune ? D : (int64_t)w->ntok * D, w->norm_w, w->norm_b, out + (size_t)s0 * D,
+                                          HIPT_F32, D, n, D, w->ln_eps, st));
     }
     return HIPT_OK;
-}
-
-static size_t vit256_range_bytes(const hipt_vit_weights* w, int nseq, int chunk) {
-    if (chunk <= 0) chunk = default_chunk(nseq);
-    if (chunk > nseq) chunk = nseq;
-    return al256((size_t)chunk * w->ntok * w->dim * 4) + block_scratch_bytes(w, chunk);
 }
 
 // the input image tensor in the compute dtype: fp32 input in fp32 mode is used where it lies (returns `images`), everything
@@ -896,24 +922,19 @@ static int vit256_forward_impl(const hipt_vit_weights* w, const void* images, in
     if (rc) return rc;
     HIPT_CHECK_ARG(images && lay && out && nseq > 0, "vit256_forward: null/empty argument");
     hipStream_t st = S(stream);
-    const size_t nrange = vit256_range_bytes(w, nseq, chunk);
-    const int64_t n_img = image_elems(lay, nseq);
-    const size_t nimg = w->dtype == HIPT_BF16 ? al256((size_t)n_img * 2) : kind != IMG_F32 ? al256((size_t)n_img * 4) : 0;
-    if (ws_bytes < nrange + nimg || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("vit256_forward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, nrange + nimg);
-        return HIPT_E_WORKSPACE;
-    }
+    Carver c(workspace, ws_bytes);
+    const Vit256Ws v = carve_vit256(c, w, nseq, chunk, image_compute_bytes(w, lay, nseq, kind));
+    if ((rc = check_workspace(c, "vit256_forward"))) return rc;
     const void* img = images;
     // fp32 pixels, bf16 model, 256 x 256 patches: the embedding kernel reads the image itself; the slot of the bf16 copy holds its
     // packed weight (made here: 0.6 MB, a few microseconds) and its tile queue instead
     // (uint8 RGB, planar or interleaved: the same kernel normalises in registers -- no device copy of the image at all)
-    if (embed_fused_ok(w, images, lay, nimg, kind)) {
-        void* pk = (char*)workspace + nrange;
-        if ((rc = hipt_embed32_pack_launch(w->embed_w, pk, st))) return rc;
-        return vit256_range_impl(w, images, lay, 0, nseq, chunk, out, workspace, nrange, st, pk, kind);
+    if (embed_fused_ok(w, images, lay, v.nslot, kind)) {
+        if ((rc = hipt_embed32_pack_launch(w->embed_w, v.slot, st))) return rc;
+        return vit256_range_impl(w, images, lay, 0, nseq, chunk, out, v.range, v.nrange, st, v.slot, kind);
     }
-    if ((rc = image_to_compute(w, images, kind, lay, nseq, (char*)workspace + nrange, &img, st))) return rc;
-    return vit256_range_impl(w, img, lay, 0, nseq, chunk, out, workspace, nrange, st);
+    if ((rc = image_to_compute(w, images, kind, lay, nseq, v.slot, &img, st))) return rc;
+    return vit256_range_impl(w, img, lay, 0, nseq, chunk, out, v.range, v.nrange, st);
 }
 
 int hipt_vit256_forward(const hipt_vit_weights* w, const float* images, const hipt_image_layout* lay, int nseq, int chunk,
@@ -922,9 +943,7 @@ int hipt_vit256_forward(const hipt_vit_weights* w, const float* images, const hi
 }
 
 size_t hipt_image_compute_bytes(const hipt_vit_weights* w, const hipt_image_layout* lay, int nseq, int input_kind) {
-    if (!w || !lay || nseq <= 0) return 0;
-    const int64_t n_img = image_elems(lay, nseq);
-    return w->dtype == HIPT_BF16 ? al256((size_t)n_img * 2) : input_kind != IMG_F32 ? al256((size_t)n_img * 4) : 0;
+    return w && lay && nseq > 0 ? image_compute_bytes(w, lay, nseq, input_kind) : 0;
 }
 
 int hipt_image_to_compute(const hipt_vit_weights* w, const void* images, int input_kind, const hipt_image_layout* lay, int nseq, void* dst,
@@ -937,7 +956,9 @@ int hipt_image_to_compute(const hipt_vit_weights* w, const void* images, int inp
     return image_to_compute(w, images, input_kind, lay, nseq, dst, &img, S(stream));
 }
 
-size_t hipt_vit256_range_workspace_bytes(const hipt_vit_weights* w, int nseq, int chunk) { return w && nseq > 0 ? vit256_range_bytes(w, nseq, chunk) : 0; }
+size_t hipt_vit256_range_workspace_bytes(const hipt_vit_weights* w, int nseq, int chunk) {
+    return w && nseq > 0 ? dry_run([&](Carver& c) { carve_range(c, w, nseq, chunk); }) : 0;
+}
 
 int hipt_vit256_forward_range(const hipt_vit_weights* w, const void* images_cd, const hipt_image_layout* lay, int seq0, int nseq, int chunk,
                               float* out, void* workspace, size_t ws_bytes, void* stream) {
@@ -950,9 +971,9 @@ int hipt_vit256_forward_range(const hipt_vit_weights* w, const void* images_cd, 
 // the same over fp32 pixels where the embedding kernel reads them itself (embed32.hip): no image in the compute dtype is needed
 size_t hipt_vit256_range_px_workspace_bytes(const hipt_vit_weights* w, const hipt_image_layout* lay, int nseq, int chunk) {
     if (!w || !lay || nseq <= 0 || lay->patch_h <= 0 || lay->patch_w <= 0) return 0;
-    const size_t slot = al256(hipt_embed32_packed_bytes() + 256);
     // (the pointer's alignment is checked at the call; any non-null 16-byte aligned value stands in for it here)
-    return embed_fused_ok(w, (const void*)16, lay, slot) ? vit256_range_bytes(w, nseq, chunk) + slot : 0;
+    if (!embed_fused_ok(w, (const void*)16, lay, embed_px_slot_bytes())) return 0;
+    return dry_run([&](Carver& c) { carve_vit256(c, w, nseq, chunk, embed_px_slot_bytes()); });
 }
 
 int hipt_vit256_forward_range_px(const hipt_vit_weights* w, const float* images, const hipt_image_layout* lay, int seq0, int nseq, int chunk,
@@ -960,18 +981,15 @@ int hipt_vit256_forward_range_px(const hipt_vit_weights* w, const float* images,
     int rc = check_vit(w);
     if (rc) return rc;
     HIPT_CHECK_ARG(images && lay && out && nseq > 0 && seq0 >= 0, "vit256_forward_range_px: null/empty argument");
-    const size_t slot = al256(hipt_embed32_packed_bytes() + 256), nrange = vit256_range_bytes(w, nseq, chunk);
-    if (!embed_fused_ok(w, images, lay, slot)) {
+    if (!embed_fused_ok(w, images, lay, embed_px_slot_bytes())) {
         hipt_set_error("vit256_forward_range_px: this model / layout has no pixel-reading embedding (hipt_vit256_range_px_workspace_bytes returns 0)");
         return HIPT_E_UNSUPPORTED;
     }
-    if (ws_bytes < nrange + slot || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("vit256_forward_range_px: workspace %zu B too small / unaligned (need %zu)", ws_bytes, nrange + slot);
-        return HIPT_E_WORKSPACE;
-    }
-    void* pk = (char*)workspace + nrange;
-    if ((rc = hipt_embed32_pack_launch(w->embed_w, pk, S(stream)))) return rc;
-    return vit256_range_impl(w, images, lay, seq0, nseq, chunk, out, workspace, nrange, S(stream), pk);
+    Carver c(workspace, ws_bytes);
+    const Vit256Ws v = carve_vit256(c, w, nseq, chunk, embed_px_slot_bytes());
+    if ((rc = check_workspace(c, "vit256_forward_range_px"))) return rc;
+    if ((rc = hipt_embed32_pack_launch(w->embed_w, v.slot, S(stream)))) return rc;
+    return vit256_range_impl(w, images, lay, seq0, nseq, chunk, out, v.range, v.nrange, S(stream), v.slot);
 }
 
 int hipt_vit4k_forward(const hipt_vit_weights* w, const float* tokens_in, int nseq, float* out, void* workspace,
@@ -981,46 +999,27 @@ int hipt_vit4k_forward(const hipt_vit_weights* w, const float* tokens_in, int ns
     HIPT_CHECK_ARG(out && nseq > 0, "vit4k_forward: null/empty argument");
     hipStream_t st = S(stream);
     Carver c(workspace, ws_bytes);
-    float* x = (float*)c.take((size_t)nseq * w->ntok * w->dim * 4);
-    BlockScratch s = carve_blocks(c, w, nseq);
-    void* tokT = c.take((size_t)nseq * w->ntok * w->embed_k * 2);
-    if (!c.ok()) {
-        hipt_set_error("vit4k_forward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, c.used);
-        return HIPT_E_WORKSPACE;
-    }
+    const Vit4kWs k = carve_vit4k(c, w, nseq, true);
+    if ((rc = check_workspace(c, "vit4k_forward"))) return rc;
     const void* tok = tokens_in;
     const int64_t n = (int64_t)nseq * (w->ntok - 1) * w->embed_k;
     if (w->dtype == HIPT_BF16 && n > 0) {
-        if ((rc = hipt_f32_to_bf16_launch(tokens_in, tokT, n, st))) return rc;
-        tok = tokT;
+        if ((rc = hipt_f32_to_bf16_launch(tokens_in, k.tok, n, st))) return rc;
+        tok = k.tok;
     }
-    // ALL the regions of a call go through the small-call kernels together (round 6; `force_small`): one wave per 16 x 32 output tile, rows
+    // ALL the regions of a call go through the small-call kernels together (RT_FORCE_SMALL): one wave per 16 x 32 output tile, rows
     // independent bit for bit, the attention one workgroup per (region, head) -- which kernels a region's 257 rows meet, and the bits they
     // write, do not depend on how many regions share the call: one region alone, eight gathered by extract_slide and a ragged tail of three
-    // agree exactly (tests).  Thirty launches per call whatever its size (round 5 walked the regions in groups of four: 30 launches per
-    // group, linear in nseq); the phi GEMM takes the small kernel too, for the same reason.
-    if ((rc = embed4k(w, tok, nseq, x, st, 1))) return rc;
-    if ((rc = run_blocks(w, x, nseq, 0, w->depth, nullptr, s, st, false, nullptr, false, nullptr, false, true))) return rc;
-    return hipt_layernorm_launch(x, (int64_t)w->ntok * w->dim, w->norm_w, w->norm_b, out, HIPT_F32, w->dim, nseq, w->dim, w->ln_eps, st);
-}
-
-static hipt_image_layout region_layout(int W, int H) {
-    hipt_image_layout lay;
-    lay.grid_w = W / 256;
-    lay.grid_h = H / 256;
-    lay.patch_h = lay.patch_w = 256;
-    lay.row_stride = H;
-    lay.chan_stride = (int64_t)W * H;
-    lay.batch_stride = 3 * lay.chan_stride;
-    return lay;
+    // agree exactly (tests).  Thirty launches per call whatever its size; the phi GEMM takes the small kernel too, for the same reason.
+    if ((rc = embed4k(w, tok, nseq, k.x, st, 1))) return rc;
+    VitRoute r = vit_route(w, nseq, 0, w->depth, false, RT_FORCE_SMALL);
+    if ((rc = run_blocks(w, k.x, nseq, nullptr, k.s, r, st))) return rc;
+    return hipt_layernorm_launch(k.x, (int64_t)w->ntok * w->dim, w->norm_w, w->norm_b, out, HIPT_F32, w->dim, nseq, w->dim, w->ln_eps, st);
 }
 
 size_t hipt_hipt4k_workspace_bytes(const hipt_vit_weights* w256, const hipt_vit_weights* w4k, int nreg, int w_256, int h_256,
                                    int chunk) {
-    const hipt_image_layout lay = region_layout(w_256 * 256, h_256 * 256);
-    const int nseq = nreg * w_256 * h_256;
-    return hipt_vit256_forward_workspace_bytes(w256, &lay, nseq, chunk) + hipt_vit4k_forward_workspace_bytes(w4k, nreg) +
-           al256((size_t)nseq * w256->dim * 4);
+    return dry_run([&](Carver& c) { carve_hipt4k(c, w256, w4k, nreg, w_256, h_256, chunk, IMG_F32); });
 }
 
 static int hipt4k_forward_impl(const hipt_vit_weights* w256, const hipt_vit_weights* w4k, const void* regions, int kind, int nreg, int W,
@@ -1032,19 +1031,15 @@ static int hipt4k_forward_impl(const hipt_vit_weights* w256, const hipt_vit_weig
     HIPT_CHECK_ARG(w4k->ntok == per + 1, "hipt4k_forward: ViT-4K weights prepared for %d tokens, region has %d", w4k->ntok, per + 1);
     HIPT_CHECK_ARG(w4k->embed_k == w256->dim, "hipt4k_forward: ViT-4K input width %d != ViT-256 width %d", w4k->embed_k, w256->dim);
     const hipt_image_layout lay = region_layout(W, H);
-    const size_t n256 = hipt_vit256_forward_workspace_bytes(w256, &lay, nseq, chunk) + image_extra_bytes(w256, &lay, nseq, kind);
-    const size_t n4k = hipt_vit4k_forward_workspace_bytes(w4k, nreg);
-    const size_t ncls = al256((size_t)nseq * w256->dim * 4);
-    if (ws_bytes < n256 + n4k + ncls || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("hipt4k_forward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, n256 + n4k + ncls);
-        return HIPT_E_WORKSPACE;
-    }
-    char* ws = (char*)workspace;
-    // cls256 [nreg * per, 384] token-major = nreg sequences of `per` tokens: exactly phi's input (hipt_4k.py:72-74)
-    float* cls = cls256_out ? cls256_out : (float*)ws;
-    int rc = vit256_forward_impl(w256, regions, kind, &lay, nseq, chunk, cls, ws + ncls, n256, stream);
+    Carver c(workspace, ws_bytes);
+    const Hipt4kWs h = carve_hipt4k(c, w256, w4k, nreg, W / 256, H / 256, chunk, kind);
+    int rc = check_workspace(c, "hipt4k_forward");
     if (rc) return rc;
-    return hipt_vit4k_forward(w4k, cls, nreg, out, ws + ncls + n256, n4k, stream);
+    // cls256 [nreg * per, 384] token-major = nreg sequences of `per` tokens: exactly phi's input (hipt_4k.py:72-74)
+    float* cls = cls256_out ? cls256_out : h.cls;
+    rc = vit256_forward_impl(w256, regions, kind, &lay, nseq, chunk, cls, h.ws256, h.n256, stream);
+    if (rc) return rc;
+    return hipt_vit4k_forward(w4k, cls, nreg, out, h.ws4k, h.n4k, stream);
 }
 
 int hipt_hipt4k_forward(const hipt_vit_weights* w256, const hipt_vit_weights* w4k, const float* regions, int nreg, int W, int H,
@@ -1054,8 +1049,7 @@ int hipt_hipt4k_forward(const hipt_vit_weights* w256, const hipt_vit_weights* w4
 
 size_t hipt_hipt4k_u8_workspace_bytes(const hipt_vit_weights* w256, const hipt_vit_weights* w4k, int nreg, int w_256, int h_256, int chunk) {
     if (!w256 || !w4k || nreg <= 0 || w_256 <= 0 || h_256 <= 0) return 0;
-    const hipt_image_layout lay = region_layout(w_256 * 256, h_256 * 256);
-    return hipt_hipt4k_workspace_bytes(w256, w4k, nreg, w_256, h_256, chunk) + image_extra_bytes(w256, &lay, nreg * w_256 * h_256, IMG_U8_CHW);
+    return dry_run([&](Carver& c) { carve_hipt4k(c, w256, w4k, nreg, w_256, h_256, chunk, IMG_U8_CHW); });
 }
 
 int hipt_hipt4k_forward_u8(const hipt_vit_weights* w256, const hipt_vit_weights* w4k, const uint8_t* regions, int interleaved, int nreg,
@@ -1078,21 +1072,26 @@ static int check_clam(const hipt_clam_weights* w) {
     return HIPT_OK;
 }
 
-static size_t clam_partials_bytes(const hipt_clam_weights* w, int N) {
-    const size_t g = 1024;  // fused: <= 512 workgroups; generic pool: <= 1024 row blocks
-    return al256(g * (2 + w->s1) * 4);
-}
-
 // The ticket block is the FIRST 256 bytes of the workspace, whatever the model's widths, and nothing else ever writes there
 // (one workspace may serve several CLAM modules of different widths / paths on a stream: the generic path's scratch must not
 // run over the streaming kernels' arrival counter).
 size_t hipt_clam_ticket_offset(const hipt_clam_weights* w, int N) { return 0; }
 
-size_t hipt_clam_workspace_bytes(const hipt_clam_weights* w, int N) {
-    // ticket | partials | gmax | h1 fp32 | ab fp32 | h1 in dtype (generic path)
-    return 256 + clam_partials_bytes(w, N) + 256 + al256((size_t)N * w->s1 * 4) + al256((size_t)N * 2 * w->s2 * 4) +
-           al256((size_t)N * w->s1 * 2);
+// ticket (hipt_clam_ticket_offset() = 0: zero before the first use, zero after every call) | partials | gmax, and for the generic path
+// h1 fp32 | ab fp32 | h1 in the compute dtype
+struct ClamWs { unsigned* ticket; float *partials, *gmax, *h1, *ab; void* h1T; };
+static ClamWs carve_clam(Carver& c, const hipt_clam_weights* w, int N) {
+    ClamWs k;
+    k.ticket = (unsigned*)c.take(256);
+    k.partials = (float*)c.take((size_t)1024 * (2 + w->s1) * 4);  // fused: <= 512 workgroups; generic pool: <= 1024 row blocks
+    k.gmax = (float*)c.take(256);
+    k.h1 = (float*)c.take((size_t)N * w->s1 * 4);
+    k.ab = (float*)c.take((size_t)N * 2 * w->s2 * 4);
+    k.h1T = c.take((size_t)N * w->s1 * 2);
+    return k;
 }
+
+size_t hipt_clam_workspace_bytes(const hipt_clam_weights* w, int N) { return dry_run([&](Carver& c) { carve_clam(c, w, N); }); }
 
 size_t hipt_clam_stream_packed_bytes(const hipt_clam_weights* w) { return w ? hipt_clam_stream_image_bytes(w) : 0; }
 
@@ -1112,7 +1111,7 @@ static int gated_scores(const hipt_clam_weights* w, const void* x, int xdtype, i
             if ((rc = hipt_f32_to_bf16_launch((const float*)x, xT, (int64_t)N * w->s1, st))) return rc;
             a = xT;
         }
-        rc = linear(a, w->s1, w->wab, w->s1, w->bab, nullptr, ab, n2, N, n2, w->s1, w->dtype, HIPT_EPI_OUT_F32, st);
+        rc = linear(gemm_params(a, w->s1, w->wab, w->s1, w->bab, ab, n2, N, n2, w->s1), w->dtype, HIPT_EPI_OUT_F32, st);
     } else {
         rc = hipt_small_ab_launch(x, xdtype, N, w->s1, n2, w->wab, w->dtype, w->bab, ab, st);
     }
@@ -1132,42 +1131,39 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
         hipt_set_error("clam_sb_forward: S0=%d must be a multiple of %d and S1=%d of 4", w->s0, kb, w->s1);
         return HIPT_E_UNSUPPORTED;
     }
-    if (ws_bytes < hipt_clam_workspace_bytes(w, N) || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("clam_sb_forward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, hipt_clam_workspace_bytes(w, N));
-        return HIPT_E_WORKSPACE;
-    }
-    hipStream_t st = S(stream);
     Carver c(workspace, ws_bytes);
-    unsigned* ticket = (unsigned*)c.take(256);  // (hipt_clam_ticket_offset() = 0: zero before the first use, zero after every call)
-    float* partials = (float*)c.take(clam_partials_bytes(w, N));
-    float* gmax = (float*)c.take(256);
+    const ClamWs k = carve_clam(c, w, N);
+    if ((rc = check_workspace(c, "clam_sb_forward"))) return rc;
+    hipStream_t st = S(stream);
     int G = 0;
     if (hipt_clam_stream_supported(w)) {  // bf16 [S0,128,64]: weight-stationary streaming kernel
-        PROF(PC_ABMIL, hipt_clam_stream_launch(w, bag, N, attention_only, A_raw, partials, &G, ticket, M, logits, Y_prob, Y_hat, st));
+        PROF(PC_ABMIL, hipt_clam_stream_launch(w, bag, N, attention_only, A_raw, k.partials, &G, k.ticket, M, logits, Y_prob, Y_hat, st));
         if (!attention_only && G == 0) return HIPT_OK;
     } else if (hipt_clam_fused_supported(w)) {
-        PROF(PC_ABMIL, hipt_clam_fused_launch(w, bag, N, attention_only, A_raw, partials, &G, st));
+        PROF(PC_ABMIL, hipt_clam_fused_launch(w, bag, N, attention_only, A_raw, k.partials, &G, st));
     } else {
-        float* h1 = (float*)c.take((size_t)N * w->s1 * 4);
-        float* ab = (float*)c.take((size_t)N * 2 * w->s2 * 4);
-        void* h1T = c.take((size_t)N * w->s1 * 2);
-        if ((rc = linear(bag, w->s0, w->w1, w->s0, w->b1, nullptr, h1, w->s1, N, w->s1, w->s0, w->dtype,
-                         HIPT_EPI_RELU | HIPT_EPI_OUT_F32, st)))
-            return rc;
-        if ((rc = gated_scores(w, h1, HIPT_F32, N, ab, h1T, A_raw, st))) return rc;
-        if (!attention_only && (rc = hipt_pool_launch(A_raw, h1, N, w->s1, gmax, partials, &G, st))) return rc;
+        if ((rc = linear(gemm_params(bag, w->s0, w->w1, w->s0, w->b1, k.h1, w->s1, N, w->s1, w->s0), w->dtype, HIPT_EPI_RELU | HIPT_EPI_OUT_F32, st))) return rc;
+        if ((rc = gated_scores(w, k.h1, HIPT_F32, N, k.ab, k.h1T, A_raw, st))) return rc;
+        if (!attention_only && (rc = hipt_pool_launch(A_raw, k.h1, N, w->s1, k.gmax, k.partials, &G, st))) return rc;
     }
     if (attention_only) return HIPT_OK;
-    PROF(PC_COMBINE, hipt_clam_combine_launch(partials, G, w, M, logits, Y_prob, Y_hat, st));
+    PROF(PC_COMBINE, hipt_clam_combine_launch(k.partials, G, w, M, logits, Y_prob, Y_hat, st));
     return HIPT_OK;
 }
 
 int hipt_clam_mb_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_mb_stream_supported(w) ? 1 : 0; }
 
-size_t hipt_clam_mb_workspace_bytes(const hipt_clam_weights* w, int N) {
-    // ticket | partials of <= 128 workgroups x K branches | h1 as a bf16 image
-    return 256 + al256((size_t)128 * 4 * (4 + 128) * 4) + al256(hipt_clam_mb_h1_bytes(N > 0 ? N : 1));
+// ticket | partials of <= 128 workgroups x 4 branches | h1 as a bf16 image
+struct ClamMbWs { unsigned* ticket; float* partials; void* h1; };
+static ClamMbWs carve_clam_mb(Carver& c, int N) {
+    ClamMbWs k;
+    k.ticket = (unsigned*)c.take(256);
+    k.partials = (float*)c.take((size_t)128 * 4 * (4 + 128) * 4);
+    k.h1 = c.take(hipt_clam_mb_h1_bytes(N > 0 ? N : 1));
+    return k;
 }
+
+size_t hipt_clam_mb_workspace_bytes(const hipt_clam_weights* w, int N) { return dry_run([&](Carver& c) { carve_clam_mb(c, N); }); }
 
 int hipt_clam_mb_forward(const hipt_clam_weights* w, const void* bag, int N, int attention_only, float* A_raw, float* M, float* logits, void* workspace,
                          size_t ws_bytes, void* stream) {
@@ -1181,18 +1177,13 @@ int hipt_clam_mb_forward(const hipt_clam_weights* w, const void* bag, int N, int
                        "call hipt_clam_sb_forward per branch");
         return HIPT_E_UNSUPPORTED;
     }
-    if (ws_bytes < hipt_clam_mb_workspace_bytes(w, N) || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("clam_mb_forward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, hipt_clam_mb_workspace_bytes(w, N));
-        return HIPT_E_WORKSPACE;
-    }
-    hipStream_t st = S(stream);
     Carver c(workspace, ws_bytes);
-    unsigned* ticket = (unsigned*)c.take(256);
-    float* partials = (float*)c.take((size_t)128 * 4 * (4 + 128) * 4);
-    void* h1 = c.take(hipt_clam_mb_h1_bytes(N));
+    const ClamMbWs k = carve_clam_mb(c, N);
+    if ((rc = check_workspace(c, "clam_mb_forward"))) return rc;
+    hipStream_t st = S(stream);
     // (the two launches are booked apart: 'abmil_fused' = the streaming pass, 'abmil_combine' = the pooling pass)
-    PROF(PC_ABMIL, hipt_clam_mb_stream_launch(w, bag, N, 1, A_raw, h1, partials, ticket, M, logits, st));  // (passes = 1: the streaming pass)
-    if (!attention_only) PROF(PC_COMBINE, hipt_clam_mb_stream_launch(w, bag, N, 2, A_raw, h1, partials, ticket, M, logits, st));  // (passes = 2: the pooling pass)
+    PROF(PC_ABMIL, hipt_clam_mb_stream_launch(w, bag, N, 1, A_raw, k.h1, k.partials, k.ticket, M, logits, st));  // (passes = 1: the streaming pass)
+    if (!attention_only) PROF(PC_COMBINE, hipt_clam_mb_stream_launch(w, bag, N, 2, A_raw, k.h1, k.partials, k.ticket, M, logits, st));  // (passes = 2: the pooling pass)
     return HIPT_OK;
 }
 
@@ -1201,12 +1192,10 @@ int hipt_attn_net_gated(const hipt_clam_weights* w, const void* x, int N, float*
     int rc = check_clam(w);
     if (rc) return rc;
     HIPT_CHECK_ARG(x && A && N > 0, "attn_net_gated: null/empty input");
-    const size_t need = al256((size_t)N * 2 * w->s2 * 4);
-    if (ws_bytes < need || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("attn_net_gated: workspace %zu B too small / unaligned (need %zu)", ws_bytes, need);
-        return HIPT_E_WORKSPACE;
-    }
-    return gated_scores(w, x, w->dtype, N, (float*)workspace, nullptr, A, S(stream));
+    Carver c(workspace, ws_bytes);
+    float* ab = (float*)c.take((size_t)N * 2 * w->s2 * 4);
+    if ((rc = check_workspace(c, "attn_net_gated"))) return rc;
+    return gated_scores(w, x, w->dtype, N, ab, nullptr, A, S(stream));
 }
 
 int hipt_clam_gather_h1(const hipt_clam_weights* w, const void* bag, const int64_t* idx, int n_idx, float* out, void* stream) {
@@ -1214,20 +1203,6 @@ int hipt_clam_gather_h1(const hipt_clam_weights* w, const void* bag, const int64
     if (rc) return rc;
     HIPT_CHECK_ARG(bag && idx && out && n_idx > 0, "clam_gather_h1: null/empty argument");
     return hipt_gather_h1_launch(w, bag, idx, n_idx, out, S(stream));
-}
-
-// ---- bootstrapped evaluation metrics (bootstrapping.py:78-102; kernel in bootstrap.hip) ----
-int hipt_bootstrap_metrics(const int32_t* Y, const int32_t* Y_hat, const int32_t* order, const int32_t* tie, int n, int K,
-                           const int32_t* idx, int B, double* out, int32_t* flags, void* stream) {
-    HIPT_CHECK_ARG(Y && Y_hat && order && tie && idx && out && flags, "bootstrap_metrics: null argument");
-    HIPT_CHECK_ARG(n >= 1 && K >= 2 && B >= 1, "bootstrap_metrics: n=%d (>= 1), K=%d (>= 2), B=%d (>= 1)", n, K, B);
-    if (n > HIPT_BOOTSTRAP_MAX_N || K > HIPT_BOOTSTRAP_MAX_CLASSES || B > HIPT_BOOTSTRAP_MAX_REPLICATES) {
-        hipt_set_error("bootstrap_metrics: n=%d / K=%d / B=%d beyond the limits %d / %d / %d (nothing was launched)", n, K, B,
-                       HIPT_BOOTSTRAP_MAX_N, HIPT_BOOTSTRAP_MAX_CLASSES, HIPT_BOOTSTRAP_MAX_REPLICATES);
-        return HIPT_E_UNSUPPORTED;
-    }
-    HIPT_CHECK_ARG(((uintptr_t)out & 7) == 0, "bootstrap_metrics: out must be 8-byte aligned");
-    return hipt_launch_bootstrap(Y, Y_hat, order, tie, n, K, idx, B, out, flags, (hipStream_t)stream);
 }
 
 }  // extern "C"

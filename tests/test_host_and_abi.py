@@ -576,3 +576,25 @@ def test_wait_count_audits_catch_a_miscounted_wait(tmp_path):
     badq.write_text(q[:k] + m.group(1) + "\n" + q[k:])  # a ninth output store
     r = run("audit_qkv_wait.py", str(badq))
     assert r.returncode == 1 and "expected exactly eight" in r.stdout
+
+
+def test_pruned_last_block_refuses_a_hidden_slot_too_small_for_its_cls_rows(monkeypatch):
+    """The [CLS]-pruned last ViT-256 block keeps its compact residual rows (nseq x D fp32) in the block scratch's hidden slot.  A model
+    of three tokens per sequence and a 128-wide MLP leaves 768 bytes a sequence there against the 1 536 the rows take: the call must
+    be refused before anything is launched (HIPT_E_WORKSPACE; host arithmetic only, so this runs without a GPU) and not write past
+    its workspace."""
+    import ctypes as C
+    for k in ("HIPT_NO_PRUNE", "HIPT_GENERIC"):
+        monkeypatch.delenv(k, raising=False)
+    lib = N.lib()
+    blocks = (N.BlockWeights * 2)()
+    w = N.VitWeights(dtype=N.HIPT_BF16, dim=384, depth=2, heads=6, hidden=128, ntok=3, embed_k=768, ln_eps=1e-6)
+    w.blocks = C.cast(blocks, C.POINTER(N.BlockWeights))
+    lay = N.ImageLayout(grid_w=1, grid_h=1, patch_h=16, patch_w=32, row_stride=32, chan_stride=16 * 32, batch_stride=3 * 16 * 32)
+    nseq = 600  # 1 800 token rows: beyond the small-call border, so the last block is pruned
+    need = lib.hipt_vit256_range_workspace_bytes(C.byref(w), nseq, 0)
+    assert need > 0
+    fake = C.c_void_p(1 << 20)  # never dereferenced: the call returns before its first launch
+    rc = lib.hipt_vit256_forward_range(C.byref(w), fake, C.byref(lay), 0, nseq, 0, fake, fake, need, None)
+    assert rc == -2, (rc, lib.hipt_last_error())  # HIPT_E_WORKSPACE
+    assert b"pruned last block" in lib.hipt_last_error()
