@@ -20,6 +20,7 @@
 // the bag classifier, softmax and argmax.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -488,15 +489,8 @@ int launch_fused(const hipt_clam_weights* w, const void* bag, int N, int attenti
     const int ntiles = (N + TM - 1) / TM;
     int grid = ntiles < 512 ? ntiles : 512;
     auto k = abmil_fused_kernel<T, S1, S2>;
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(abmil) failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;
+    if (int rc = setup({(const void*)k}, G::LDS, "abmil")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), G::LDS, st, (const T*)bag, N, w->s0, (const T*)w->w1, w->b1,
                        (const T*)w->wab, w->bab, w->wc, w->bc, A_raw, partials, attention_only);
     HIPT_CHECK_LAUNCH();

@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "pipe_common.h"
 
 namespace {
@@ -707,28 +708,16 @@ int launch(const hipt_clam_weights* w, const void* bag, int N, int attention_onl
     constexpr int lds = image_bytes(KS) + 4 * TB_BYTES;
     constexpr int lds_alloc = lds > 72 * 1024 ? lds : 72 * 1024;  // (the reduction at the end uses 66.5 KiB of it)
     auto k = abmil32_kernel<KS>;
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_alloc) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(abmil32) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("abmil32: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)k}, lds_alloc, "abmil32", &ncu)) return rc;
     Abmil32Params p;
     p.bag = (const bf16_t*)bag;
     p.N = N;
     p.nblocks = (N + 31) / 32;
     // every wave the same number of blocks (+-1): 100 000 rows are 3125 blocks = 4 rounds of 782 waves (196 workgroups), not 3 rounds
     // of 1024 and a fourth of 53 -- the time is the slowest wave's either way, and the even spread asks less of the HBM per round
-    const int maxg = once.ncu[dev] < 256 ? once.ncu[dev] : 256;  // (the merge reads up to 256 partials in one round trip)
+    const int maxg = ncu < 256 ? ncu : 256;  // (the merge reads up to 256 partials in one round trip)
     const int rounds = (p.nblocks + 4 * maxg - 1) / (4 * maxg);
     const int grid = ((p.nblocks + rounds - 1) / rounds + 3) / 4;
     p.nwaves = grid * 4;
@@ -752,21 +741,13 @@ int launch(const hipt_clam_weights* w, const void* bag, int N, int attention_onl
 #ifdef HIPT_DEBUG_STAMPS
     static const bool no_traffic = getenv("HIPT_ABMIL_NO_TRAFFIC") != nullptr;
     p.no_traffic = no_traffic;  // diagnostic builds only (make DEBUG_STAMPS=1): the release library never allocates or synchronises
-    static const bool want_stamps = getenv("HIPT_ABMIL_STAMPS") != nullptr;
-    static unsigned long long* dbuf = nullptr;
-    if (want_stamps && !dbuf) (void)hipMalloc(&dbuf, 256 * 24 * sizeof(unsigned long long));
-    if (want_stamps) {
-        (void)hipMemsetAsync(dbuf, 0, 256 * 24 * sizeof(unsigned long long), st);
-        p.stamps = dbuf;
-    }
+    static StampBuffer<256, 24> stamps("HIPT_ABMIL_STAMPS");
+    p.stamps = stamps.arm(st);
 #endif
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_alloc, st, p);
     HIPT_CHECK_LAUNCH();
 #ifdef HIPT_DEBUG_STAMPS
-    if (want_stamps) {
-        static unsigned long long h[256 * 24];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbuf, (size_t)grid * 24 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (const unsigned long long* h = stamps.read(grid, st)) {
         unsigned long long t0 = ~0ull;
         for (int b = 0; b < grid; ++b)
             if (h[b * 24] < t0) t0 = h[b * 24];
@@ -962,27 +943,15 @@ int launch_mb(const hipt_clam_weights* w, const void* bag, int N, int passes, fl
     constexpr int lds = image_bytes(KS) + 4 * TB_BYTES;
     auto k = abmil32_kernel<KS, NB>;
     auto kp = clam_mb_pool_kernel<NB>;
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(abmil32 / multi-branch) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("abmil32: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)k}, lds, "abmil32 / multi-branch", &ncu)) return rc;
     Abmil32Params p;
     memset(&p, 0, sizeof(p));
     p.bag = (const bf16_t*)bag;
     p.N = N;
     p.nblocks = (N + 31) / 32;
-    const int maxg = once.ncu[dev] < 256 ? once.ncu[dev] : 256;
+    const int maxg = ncu < 256 ? ncu : 256;
     const int rounds = (p.nblocks + 4 * maxg - 1) / (4 * maxg);
     const int grid = ((p.nblocks + rounds - 1) / rounds + 3) / 4;
     p.nwaves = grid * 4;

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -200,15 +201,12 @@ int launch(const void* qkv, void* out, float* probs, int B, int ntok, int heads,
     constexpr int lds = NKT * 16 * (G::RB + G::VRB);
     const float sl2e = scale * 1.4426950408889634f;
     const dim3 grid(B * heads, B * heads <= 48 ? (((ntok + 15) >> 4) + 3) / 4 : 1), block(256);  // few sequences: one query tile per wave
-    if (probs) {
-        auto k = attn_kernel<T, DH, NKT, true>;
-        if (lds > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(k, grid, block, lds, st, (const T*)qkv, (T*)out, probs, ntok, heads, sl2e);
-    } else {
-        auto k = attn_kernel<T, DH, NKT, false>;
-        if (lds > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(k, grid, block, lds, st, (const T*)qkv, (T*)out, probs, ntok, heads, sl2e);
+    if constexpr (lds > 65536) {  // (the instantiations that fit the default 64 KiB need no setup)
+        static DeviceSetup setup;
+        if (int rc = setup({(const void*)attn_kernel<T, DH, NKT, true>, (const void*)attn_kernel<T, DH, NKT, false>}, lds, "attention")) return rc;
     }
+    if (probs) hipLaunchKernelGGL((attn_kernel<T, DH, NKT, true>), grid, block, lds, st, (const T*)qkv, (T*)out, probs, ntok, heads, sl2e);
+    else hipLaunchKernelGGL((attn_kernel<T, DH, NKT, false>), grid, block, lds, st, (const T*)qkv, (T*)out, probs, ntok, heads, sl2e);
     HIPT_CHECK_LAUNCH();
     return HIPT_OK;
 }

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -691,16 +692,8 @@ int hipt_clam_train_forward(const hipt_clam_train_weights* w, const float* bag, 
         hipt_set_error("clam_train_forward: widths [%d,%d,%d] need %zu B of LDS", w->s0, w->s1, w->s2, lds);
         return HIPT_E_UNSUPPORTED;
     }
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)clam_train_fwd_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)clam_train_bwd_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(clam_train) failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;
+    if (int rc = setup({(const void*)clam_train_fwd_rows, (const void*)clam_train_bwd_rows}, 160 * 1024, "clam_train")) return rc;
     hipLaunchKernelGGL(clam_train_fwd_rows, dim3((N + TR - 1) / TR), dim3(256), lds, st, bag, d, p, m1, ma, mb, h1, t, s, A_raw);
     HIPT_CHECK_LAUNCH();
     const int prepooled = N > POOL_SPLIT_N ? 1 : 0;
@@ -742,15 +735,8 @@ int hipt_clam_train_backward(const hipt_clam_train_weights* w, const float* bag,
         hipt_set_error("clam_train_backward: widths [%d,%d,%d] need %zu B of LDS", S0, S1, S2, lds);
         return HIPT_E_UNSUPPORTED;
     }
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)clam_train_bwd_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(clam_train_bwd_rows) failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;
+    if (int rc = setup({(const void*)clam_train_bwd_rows}, 160 * 1024, "clam_train_bwd_rows")) return rc;
     BwdIn in{dlogits, dM, dA_raw, dh1_sel, sel_ids, n_sel};
     hipLaunchKernelGGL(clam_train_bwd_rows, dim3(G), dim3(256), lds, st, d, p, in, A_raw, stats, M, h1, t, s, m1, ma, mb, duv, dz, wcpart, g->dbag);
     HIPT_CHECK_LAUNCH();

@@ -27,6 +27,7 @@
 // partials), normalised and written as bf16 z[nseq, 6, 384].  No hand-counted waits: every wait is the compiler's.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -220,22 +221,14 @@ int hipt_cls_absorb_pack_launch(const void* qkv_w, void* packed, hipStream_t st)
 int hipt_cls_pool_launch(const void* xn_img, const float* u, void* z, int nseq, float scale, hipStream_t st) {
     HIPT_CHECK_ARG(nseq > 0 && ((int64_t)nseq * CP_NTOK) % 16 == 0, "cls_pool: nseq * 257 = %lld rows are not whole 16-row fragments", (long long)nseq * CP_NTOK);
     HIPT_CHECK_ARG(((uintptr_t)xn_img % 16) == 0 && ((uintptr_t)u % 16) == 0 && ((uintptr_t)z % 8) == 0, "cls_pool: unaligned operands");
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("cls_pool: hipGetDeviceProperties failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;  // (no LDS opt-in: the CU count only)
+    int ncu;
+    if (int rc = setup({}, 0, "cls_pool", &ncu)) return rc;
     ClsPoolParams p;
     p.xn = (const bf16_t*)xn_img; p.u = u; p.z = (bf16_t*)z; p.nseq = nseq; p.scale = scale;
     // two workgroups per CU; an eighth of the patches per XCD, as in the fused attention kernel (a patch's bits do not depend on the split)
     p.px = (nseq + 7) / 8;
-    const int per_xcd = 2 * once.ncu[dev] / 8 > 0 ? 2 * once.ncu[dev] / 8 : 1;
+    const int per_xcd = 2 * ncu / 8 > 0 ? 2 * ncu / 8 : 1;
     p.nslots = p.px < per_xcd ? p.px : per_xcd;
     hipLaunchKernelGGL(cls_pool_kernel, dim3(8 * p.nslots), dim3(CP_THREADS), 0, st, p);
     HIPT_CHECK_LAUNCH();

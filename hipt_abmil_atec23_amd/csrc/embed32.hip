@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "pipe_common.h"
 
 namespace {
@@ -413,33 +414,15 @@ int hipt_embed32_launch(const EmbedParams& p_in, hipStream_t st) {
     const bool lnout = p.xn_out != nullptr;
     HIPT_CHECK_ARG(!lnout || (p.ln_w && p.ln_b && ((int64_t)p.nseq * p.ntok) % 16 == 0), "embed32: image output needs LayerNorm parameters and whole 16-row fragments");
     const int lds = 3 * UNIT + (lnout ? 3 : 1) * D * 4 + 16;
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)embed32_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)embed32_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)embed32_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)embed32_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)embed32_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)embed32_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(embed32) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("embed32: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
-    const int ncu = once.ncu[dev];
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)embed32_kernel<0, false>, (const void*)embed32_kernel<1, false>, (const void*)embed32_kernel<2, false>,
+                        (const void*)embed32_kernel<0, true>, (const void*)embed32_kernel<1, true>, (const void*)embed32_kernel<2, true>},
+                       160 * 1024, "embed32", &ncu))
+        return rc;
     p.ntiles = p.nseq * (p.nty / 8);
     const int grid = p.ntiles < ncu ? p.ntiles : ncu;
-    if (hipMemsetAsync(p.counter, 0, sizeof(int), st) != hipSuccess) {
-        hipt_set_error("embed32: hipMemsetAsync(counter) failed");
-        return HIPT_E_LAUNCH;
-    }
+    if (int rc = hipt_zero_queue(p.counter, false, st, "embed32")) return rc;
     auto k = lnout ? (p.kind == 2 ? embed32_kernel<2, true> : (p.kind == 1 ? embed32_kernel<1, true> : embed32_kernel<0, true>))
                    : (p.kind == 2 ? embed32_kernel<2, false> : (p.kind == 1 ? embed32_kernel<1, false> : embed32_kernel<0, false>));
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, p);

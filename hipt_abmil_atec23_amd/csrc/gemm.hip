@@ -15,6 +15,7 @@
 // each lane ends with 4 consecutive output columns of one row: 8/16-byte epilogue stores, no LDS hop.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -479,16 +480,8 @@ int launch(const GemmParams& p, hipStream_t st) {
         }
     }
     const int tiles = ((p.M + p.rpt - 1) / p.rpt) * ((p.N + BN - 1) / BN);
-    static DevOnce once;  // > 64 KiB dynamic LDS needs the opt-in once per kernel and device
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)gemm_kernel<T, ALOAD, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GEMM_LDS) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(gemm) failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;  // > 64 KiB dynamic LDS needs the opt-in once per kernel and device
+    if (int rc = setup({(const void*)gemm_kernel<T, ALOAD, FLAGS>}, GEMM_LDS, "gemm")) return rc;
     hipLaunchKernelGGL((gemm_kernel<T, ALOAD, FLAGS>), dim3(tiles), dim3(512), GEMM_LDS, st, p);
     HIPT_CHECK_LAUNCH();
     return HIPT_OK;

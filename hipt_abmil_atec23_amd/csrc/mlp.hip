@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_common.h"
 
 namespace {
@@ -395,22 +396,9 @@ int launch(const MlpParams& p_in, hipStream_t st) {
     constexpr int D = KS * 64;
     const int lds = NSLOT * SLAB_BYTES + (3 * D + p.hidden) * 4 + 16;
     auto k = mlp_kernel<KS, DBG>;
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(mlp) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("mlp: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
-    const int ncu = once.ncu[dev];
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)k}, 160 * 1024, "mlp", &ncu)) return rc;
     // whole rounds of #CU workgroups take 128 rows each; a last partial round that would be less than an
     // eighth full is cut into 16-row tiles (one active wave each: such a tile costs about half a full one)
     const int tiles = (p.M + TMR - 1) / TMR;
@@ -425,29 +413,17 @@ int launch(const MlpParams& p_in, hipStream_t st) {
     // long launches (>= 6 tiles per workgroup) start their 4 workgroup groups a quarter of a tile time apart
     const int stag_us = 20;
     p.stagger = (p.full_tiles >= 6 * ncu) ? stag_us * 100 : 0;
-    if (hipMemsetAsync(p.counter, 0, sizeof(int), st) != hipSuccess) {
-        hipt_set_error("mlp: hipMemsetAsync(counter) failed");
-        return HIPT_E_LAUNCH;
-    }
-
+    if (int rc = hipt_zero_queue(p.counter, false, st, "mlp")) return rc;
 #ifdef HIPT_DEBUG_STAMPS  // diagnostic builds only (make DEBUG_STAMPS=1): the release library never allocates or synchronises
-    static const bool want_stamps = getenv("HIPT_SEQGEMM_STAMPS") != nullptr;
-    static unsigned long long* dbuf = nullptr;
-    if (want_stamps) {
-        if (!dbuf) (void)hipMalloc(&dbuf, 4096 * 16 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbuf, 0, 4096 * 16 * sizeof(unsigned long long), st);
-        p.stamps = dbuf;
-    }
+    static StampBuffer<4096, 16> stamps("HIPT_SEQGEMM_STAMPS");
+    p.stamps = stamps.arm(st);
 #endif
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, p);
     HIPT_CHECK_LAUNCH();
-    // (a caller that zeroes the queue once for a chain of launches -- MlpParams::counter_zeroed -- gets it back zero: this kernel's queue does not reset itself)
+    // counter_zeroed callers share one queue over a chain of launches and expect it back at zero: unlike mlp16 / seqgemm_pipe, this kernel's queue does not reset itself
     if (p.counter_zeroed) (void)hipMemsetAsync(p.counter, 0, sizeof(int), st);
 #ifdef HIPT_DEBUG_STAMPS
-    if (want_stamps && grid <= 4096) {
-        static unsigned long long h[4096 * 16];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbuf, (size_t)grid * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (const unsigned long long* h = stamps.read(grid, st)) {
         unsigned long long t0 = ~0ull, t4 = 0;
         for (int b = 0; b < grid; ++b) {
             if (h[b * 16 + 11] < t0) t0 = h[b * 16 + 11];

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_common.h"
 #include "pipe_common.h"
 
@@ -840,27 +841,13 @@ int hipt_mlp16_launch_dbg(const MlpParams& p_in, hipStream_t st) {
     if (!fold && p.wpk_fmt == MLP16_FMT_FOLD) p.wpk = (const char*)p.wpk + 6 * UNIT;  // (the MLP's own units lie behind the six proj units)
     auto k = fold ? (p.img == 3 ? mlp16_kernel<true, true, DBG, true> : p.img == 1 ? mlp16_kernel<true, false, DBG, true> : mlp16_kernel<false, false, DBG, true>)
                   : (p.img == 3 ? mlp16_kernel<true, true, DBG> : p.img == 1 ? mlp16_kernel<true, false, DBG> : mlp16_kernel<false, false, DBG>);
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)mlp16_kernel<true, true, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)mlp16_kernel<true, false, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)mlp16_kernel<false, false, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)mlp16_kernel<true, true, DBG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)mlp16_kernel<true, false, DBG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)mlp16_kernel<false, false, DBG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(mlp16) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("mlp16: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
-    const int ncu = once.ncu[dev];
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)mlp16_kernel<true, true, DBG>, (const void*)mlp16_kernel<true, false, DBG>, (const void*)mlp16_kernel<false, false, DBG>,
+                        (const void*)mlp16_kernel<true, true, DBG, true>, (const void*)mlp16_kernel<true, false, DBG, true>,
+                        (const void*)mlp16_kernel<false, false, DBG, true>},
+                       160 * 1024, "mlp16", &ncu))
+        return rc;
     // Whole rounds of #CU workgroups take 128 rows each.  A last partial round less than an eighth full: in a short launch (up to 4
     // rounds: one or two regions per call) it is cut into 16-row tiles on 8x the CUs -- same pass over the weights, a fraction of
     // the row phases; in a long one the leftover tiles stay whole on their few CUs, which leaves the others to the next kernel
@@ -877,26 +864,15 @@ int hipt_mlp16_launch_dbg(const MlpParams& p_in, hipStream_t st) {
     p.ntiles = p.full_tiles + (tail_rows > 0 ? (tail_rows + 15) / 16 : 0);
     const int grid = p.ntiles < ncu ? p.ntiles : ncu;
     p.stagger = 0;
-    if (!p.counter_zeroed && hipMemsetAsync(p.counter, 0, sizeof(int), st) != hipSuccess) {
-        hipt_set_error("mlp16: hipMemsetAsync(counter) failed");
-        return HIPT_E_LAUNCH;
-    }
+    if (int rc = hipt_zero_queue(p.counter, p.counter_zeroed, st, "mlp16")) return rc;
 #ifdef HIPT_DEBUG_STAMPS  // diagnostic builds only (make DEBUG_STAMPS=1): the release library never allocates or synchronises
-    static const bool want_stamps = getenv("HIPT_SEQGEMM_STAMPS") != nullptr;
-    static unsigned long long* dbuf = nullptr;
-    if (want_stamps) {
-        if (!dbuf) (void)hipMalloc(&dbuf, 4096 * 16 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbuf, 0, 4096 * 16 * sizeof(unsigned long long), st);
-        p.stamps = dbuf;
-    }
+    static StampBuffer<4096, 16> stamps("HIPT_SEQGEMM_STAMPS");
+    p.stamps = stamps.arm(st);
 #endif
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, p);
     HIPT_CHECK_LAUNCH();
 #ifdef HIPT_DEBUG_STAMPS
-    if (want_stamps && grid <= 4096) {
-        static unsigned long long h[4096 * 16];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbuf, (size_t)grid * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (const unsigned long long* h = stamps.read(grid, st)) {
         unsigned long long t0 = ~0ull, t4 = 0;
         for (int b = 0; b < grid; ++b) {
             if (h[b * 16 + 11] < t0) t0 = h[b * 16 + 11];

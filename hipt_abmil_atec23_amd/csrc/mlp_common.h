@@ -1,5 +1,5 @@
-// Device helpers shared by the fused-MLP kernels (mlp.hip: generic persistent kernel; mlp_pipe.hip: the
-// software-pipelined D = 384 kernel).
+// Device helpers shared by the fused-MLP kernels (mlp.hip: generic persistent kernel; mlp16.hip: the streaming
+// D = 384 kernel on its packed weight image).
 #pragma once
 #include "common.h"
 
@@ -33,7 +33,7 @@ __device__ __forceinline__ f32x2 gelu2(f32x2 x) {
 // leading term never flips the sign of the exponent): |gelu error| <= 2.6e-5 for every finite fp32 x (tools/fit_gelu.py 3).
 // Why un-packed: v_pk_{mul,fma,add}_f32 do NOT run beside an MFMA -- tools/issue_mix_probe.hip: 16 packed FMAs in the gaps of
 // four 32x32x16 MFMAs take the four MFMAs' 128 cycles PLUS 8 cycles each, with one or with two waves per SIMD, while plain v_fma_f32
-// / v_exp_f32 issue in the 24 cycles per MFMA the matrix pipe leaves free.  mlp32.hip is compiled with -fno-slp-vectorize so
+// / v_exp_f32 issue in the 24 cycles per MFMA the matrix pipe leaves free.  mlp16.hip is compiled with -fno-slp-vectorize so
 // that hipcc does not re-pack these.
 __device__ __forceinline__ float gelu1(float x) {
 #pragma clang fp contract(off)

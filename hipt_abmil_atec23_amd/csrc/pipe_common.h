@@ -1,5 +1,5 @@
-// Building blocks of the software-pipelined A-stationary kernels (mlp_pipe.hip, seqgemm_pipe.hip): compile-time
-// loops, inline-asm LDS reads with counted waits, LayerNorm into MFMA operand fragments.
+// Building blocks of the software-pipelined streaming kernels (seqgemm_pipe.hip, mlp16.hip, embed32.hip, qkv_attention.hip,
+// abmil32.hip): compile-time loops, inline-asm LDS reads with counted waits, LayerNorm into MFMA operand fragments.
 #pragma once
 #include <type_traits>
 

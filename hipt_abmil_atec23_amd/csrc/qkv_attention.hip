@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "pipe_common.h"
 
 namespace {
@@ -751,11 +752,6 @@ static int qkv_attn_launch(const void* xn_img, const void* wpk, const float* qkv
     HIPT_CHECK_ARG((int64_t)nseq * NTOK * D * 2 < ((int64_t)1 << 32) - 65536, "qkv_attention: output image beyond 4 GiB");
     HIPT_CHECK_ARG(((uintptr_t)xn_img % 16) == 0 && ((uintptr_t)wpk % 16) == 0 && ((uintptr_t)qkv_cls % 16) == 0 && ((uintptr_t)out_img % 16) == 0,
                    "qkv_attention: 16-byte alignment required");
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        bool ok = hipFuncSetAttribute((const void*)qkv_attn_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess &&
-                  hipFuncSetAttribute((const void*)qkv_attn_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
 #ifdef HIPT_DEBUG_STAMPS
 // (bit 8 -- no GEMM MFMAs -- is not instantiated: nothing then reads the asm-loaded operand registers between their loads and the
 //  fence, hipcc re-uses them while the data is still on its way, and the landing data overwrites live addresses: a memory fault)
@@ -766,21 +762,13 @@ static int qkv_attn_launch(const void* xn_img, const void* wpk, const float* qkv
 #else
 #define QKV_DBG_LIST(X) X(1) X(2) X(3) X(16) X(32) X(48) X(64)
 #endif
-#define QKV_SETATTR(n) ok = ok && hipFuncSetAttribute((const void*)qkv_attn_kernel<n>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-        QKV_DBG_LIST(QKV_SETATTR)
+#else
+#define QKV_DBG_LIST(X)
 #endif
-        if (!ok) {
-            hipt_set_error("hipFuncSetAttribute(qkv_attention) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("qkv_attention: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
+#define QKV_KERNEL(n) , (const void*)qkv_attn_kernel<n>
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)qkv_attn_kernel<0>, (const void*)qkv_attn_kernel<0, true> QKV_DBG_LIST(QKV_KERNEL)}, LDS_BYTES, "qkv_attention", &ncu)) return rc;
     QkvAttnParams p;
     p.xn = (const char*)xn_img;
     p.wpk = (const char*)wpk;
@@ -792,19 +780,13 @@ static int qkv_attn_launch(const void* xn_img, const void* wpk, const float* qkv
     p.out_bytes = (unsigned)((int64_t)nseq * (cls_only ? 1 : NTOK) * D * 2);
     p.stamps = nullptr;
     // every CU gets a workgroup; the (patch, head) units of an eighth of the patches go round the workgroups of one XCD (QkvAttnParams)
-    const int ncu = once.ncu[dev];
     p.px = (nseq + 7) / 8;
     const int per = ncu / 8 > 0 ? ncu / 8 : 1;
     p.nslots = p.px * HEADS < per ? p.px * HEADS : per;
     const int grid = 8 * p.nslots;
 #ifdef HIPT_DEBUG_STAMPS  // diagnostic builds only (make DEBUG_STAMPS=1): the release library never allocates or synchronises
-    static const bool want_stamps = getenv("HIPT_QKVATT_STAMPS") != nullptr;
-    static unsigned long long* dbuf = nullptr;
-    if (want_stamps) {
-        if (!dbuf) (void)hipMalloc(&dbuf, 1024 * 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbuf, 0, 1024 * 8 * sizeof(unsigned long long), st);
-        p.stamps = dbuf;
-    }
+    static StampBuffer<1024, 8> stamps("HIPT_QKVATT_STAMPS");
+    p.stamps = stamps.arm(st);
 #endif
 #ifdef HIPT_DEBUG_STAMPS
     static const int dbg = getenv("HIPT_QKVATT_DBG") ? atoi(getenv("HIPT_QKVATT_DBG")) : 0;
@@ -818,10 +800,7 @@ static int qkv_attn_launch(const void* xn_img, const void* wpk, const float* qkv
 #endif
     HIPT_CHECK_LAUNCH();
 #ifdef HIPT_DEBUG_STAMPS
-    if (want_stamps && grid <= 1024) {
-        static unsigned long long h[1024 * 8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbuf, (size_t)grid * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (const unsigned long long* h = stamps.read(grid, st)) {
         double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const double heads = (double)((p.px * HEADS + p.nslots - 1) / p.nslots);
         for (int b = 0; b < grid; ++b)

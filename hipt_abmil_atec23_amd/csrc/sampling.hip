@@ -18,6 +18,7 @@
 // bitwise repeatable.  No inline assembly anywhere in this file.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -405,16 +406,10 @@ extern "C" int hipt_knn(const void* X, int kind, int N, int D, const int64_t* q_
     const KnnGeo g = knn_geo(N, S, k);
     u64* cand_d = (u64*)workspace;
     int* cand_i = (int*)((char*)workspace + al256s((size_t)S * g.G * k * 8));
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)knn_spatial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spatial_lds(KNN_MAX_K)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)knn_textural_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)textural_lds(KNN_MAX_K)) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(knn kernels) failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.done[dev] = true;
-    }
+    // (one opt-in for both kernels, the larger of their two needs: the attribute is a ceiling, each launch asks for its own size)
+    static DeviceSetup setup;
+    const size_t lds_max = spatial_lds(KNN_MAX_K) > textural_lds(KNN_MAX_K) ? spatial_lds(KNN_MAX_K) : textural_lds(KNN_MAX_K);
+    if (int rc = setup({(const void*)knn_spatial_kernel, (const void*)knn_textural_kernel}, (int)lds_max, "knn kernels")) return rc;
     const dim3 grid((unsigned)g.G, (unsigned)((S + KNN_TQ - 1) / KNN_TQ));
     if (kind == HIPT_KNN_SPATIAL) {
         hipLaunchKernelGGL(knn_spatial_kernel, grid, dim3(256), spatial_lds(k), st, (const int*)X, q_idx, g, cand_d, cand_i);

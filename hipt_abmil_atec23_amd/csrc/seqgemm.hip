@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -283,32 +284,17 @@ __global__ __launch_bounds__(256, 1) void seqgemm_kernel(const SeqGemmParams p) 
 template <int KS, bool LN, int FLAGS>
 int launch(const SeqGemmParams& p, int grid, hipStream_t st) {
     auto k = seqgemm_kernel<KS, LN, FLAGS>;
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, SEQ_LDS) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(seqgemm) failed");
-            return HIPT_E_LAUNCH;
-        }
-        once.done[dev] = true;
-    }
+    static DeviceSetup setup;
+    if (int rc = setup({(const void*)k}, SEQ_LDS, "seqgemm")) return rc;
     SeqGemmParams q = p;
 #ifdef HIPT_DEBUG_STAMPS  // diagnostic builds only (make DEBUG_STAMPS=1): the release library never allocates or synchronises
-    static const bool want_stamps = getenv("HIPT_SEQGEMM_STAMPS") != nullptr;
-    static unsigned long long* dbuf = nullptr;
-    if (want_stamps) {
-        if (!dbuf) (void)hipMalloc(&dbuf, 4096 * 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbuf, 0, 4096 * 8 * sizeof(unsigned long long), st);
-        q.stamps = dbuf;
-    }
+    static StampBuffer<4096, 8> stamps("HIPT_SEQGEMM_STAMPS");
+    q.stamps = stamps.arm(st);
 #endif
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), SEQ_LDS, st, q);
     HIPT_CHECK_LAUNCH();
 #ifdef HIPT_DEBUG_STAMPS
-    if (want_stamps && grid <= 4096) {  // debug only: synchronises and prints phase medians (us)
-        static unsigned long long h[4096 * 8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbuf, (size_t)grid * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (const unsigned long long* h = stamps.read(grid, st)) {  // debug only: synchronises and prints phase medians (us)
         unsigned long long t0 = ~0ull, t5 = 0;
         for (int b = 0; b < grid; ++b) {
             if (h[b * 8] < t0) t0 = h[b * 8];

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "pipe_common.h"
 
 namespace {
@@ -443,49 +444,24 @@ int hipt_seqgemm_pipe_launch_dbg(const SeqGemmParams& p_in, hipStream_t st) {
         if (p.img == 2) k = seqgemm_pipe_kernel<false, DBG, true, false, true>;
         if (p.img == 3) k = seqgemm_pipe_kernel<false, DBG, true, true, true>;
     }
-    static DevOnce once;
-    HIPT_CUR_DEVICE(dev);
-    if (!once.done[dev]) {
-        if (hipFuncSetAttribute((const void*)seqgemm_pipe_kernel<LN, DBG, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)seqgemm_pipe_kernel<false, DBG, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)seqgemm_pipe_kernel<false, DBG, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)seqgemm_pipe_kernel<false, DBG, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)seqgemm_pipe_kernel<false, DBG, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)seqgemm_pipe_kernel<LN, DBG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            hipt_set_error("hipFuncSetAttribute(seqgemm_pipe) failed");
-            return HIPT_E_LAUNCH;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            hipt_set_error("seqgemm_pipe: cannot query the device");
-            return HIPT_E_LAUNCH;
-        }
-        once.ncu[dev] = prop.multiProcessorCount;
-        once.done[dev] = true;
-    }
-    const int ncu = once.ncu[dev];
+    static DeviceSetup setup;
+    int ncu;
+    if (int rc = setup({(const void*)seqgemm_pipe_kernel<LN, DBG, true, false, false, true>, (const void*)seqgemm_pipe_kernel<false, DBG, true, true, false, true>,
+                        (const void*)seqgemm_pipe_kernel<false, DBG, true, true, false>, (const void*)seqgemm_pipe_kernel<false, DBG, true, false, true>,
+                        (const void*)seqgemm_pipe_kernel<false, DBG, true, true, true>, (const void*)seqgemm_pipe_kernel<LN, DBG, true>},
+                       160 * 1024, "seqgemm_pipe", &ncu))
+        return rc;
     p.ntiles = (p.M + TMR - 1) / TMR;
     const int grid = p.ntiles < ncu ? p.ntiles : ncu;
-    if (!p.counter_zeroed && hipMemsetAsync(p.counter, 0, sizeof(int), st) != hipSuccess) {
-        hipt_set_error("seqgemm_pipe: hipMemsetAsync(counter) failed");
-        return HIPT_E_LAUNCH;
-    }
+    if (int rc = hipt_zero_queue(p.counter, p.counter_zeroed, st, "seqgemm_pipe")) return rc;
 #ifdef HIPT_DEBUG_STAMPS  // diagnostic builds only (make DEBUG_STAMPS=1): the release library never allocates or synchronises
-    static const bool want_stamps = getenv("HIPT_SEQGEMM_STAMPS") != nullptr;
-    static unsigned long long* dbuf = nullptr;
-    if (want_stamps) {
-        if (!dbuf) (void)hipMalloc(&dbuf, 4096 * 16 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbuf, 0, 4096 * 16 * sizeof(unsigned long long), st);
-        p.stamps = dbuf;
-    }
+    static StampBuffer<4096, 16> stamps("HIPT_SEQGEMM_STAMPS");
+    p.stamps = stamps.arm(st);
 #endif
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), PIPE_LDS, st, p);
     HIPT_CHECK_LAUNCH();
 #ifdef HIPT_DEBUG_STAMPS
-    if (want_stamps && grid <= 4096) {
-        static unsigned long long h[4096 * 16];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, dbuf, (size_t)grid * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (const unsigned long long* h = stamps.read(grid, st)) {
         unsigned long long t0 = ~0ull, t4 = 0;
         for (int b = 0; b < grid; ++b) {
             if (h[b * 16 + 11] < t0) t0 = h[b * 16 + 11];

@@ -23,6 +23,13 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, sym), sym
     assert declared == set(N.SIGNATURES), declared ^ set(N.SIGNATURES)
     assert lib.hipt_abi_version() == N.ABI_VERSION
+    # ... and nothing else (csrc/hipt_abmil.map): no C++ launcher of kernels.h, no kernel stub or handle in the dynamic symbol table
+    import subprocess
+
+    out = subprocess.run(["nm", "-D", "--defined-only", N.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+    assert not [s for s in exported if s.startswith("_Z")], sorted(s for s in exported if s.startswith("_Z"))
+    assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
 
 
 def test_struct_layouts_match_header():

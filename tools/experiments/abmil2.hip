@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "dev_once.h"
 
 namespace {
 

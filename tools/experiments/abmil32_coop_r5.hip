@@ -49,6 +49,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "dev_once.h"
 #include "pipe_common.h"
 
 namespace {

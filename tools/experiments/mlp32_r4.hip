@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "dev_once.h"
 #include "mlp_common.h"
 #include "pipe_common.h"
 

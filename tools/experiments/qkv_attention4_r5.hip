@@ -41,6 +41,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "dev_once.h"
 #include "pipe_common.h"
 
 namespace {
