@@ -23,7 +23,6 @@ have no CPU path at all.
 from __future__ import annotations
 
 import ctypes as C_
-import os
 
 import numpy as np
 import torch
@@ -32,6 +31,7 @@ import torch.nn.functional as F
 
 from . import _native as N
 from . import functional as Fn
+from ._host import WeightImageCache
 
 SIZE_DICT = {"tinier3": [1024, 32, 8], "256": [256, 64, 16], "tinier_resnet18": [512, 64, 16],
              "tinier2_resnet18": [512, 32, 8], "tiny_resnet18": [512, 128, 32], "small_resnet18": [512, 256, 64],
@@ -53,10 +53,6 @@ def initialize_weights(module):
             nn.init.constant_(m.bias, 0)
 
 
-def _default_dtype() -> str:
-    return os.environ.get("HIPT_AMD_DTYPE", "fp32")
-
-
 def _needs_autograd(module, *tensors) -> bool:
     if not torch.is_grad_enabled():
         return False
@@ -66,6 +62,47 @@ def _needs_autograd(module, *tensors) -> bool:
 def _all_on_cpu(module, x) -> bool:
     """The caller keeps module AND input on the CPU (what the reference's relocate() does where no GPU is visible)."""
     return not x.is_cuda and not any(p.is_cuda for p in module.parameters())
+
+
+def _cast_shared(code, fc1, gated):
+    """[Wa; Wb] and W1 in the compute dtype with their fp32 biases: what the K branches of ``CLAM_MB`` share (``fc1`` None: the head alone)."""
+    wa, wb = gated.attention_a[0], gated.attention_b[0]
+    keep = dict(wab=Fn.as_compute(torch.cat([wa.weight, wb.weight], dim=0), code), bab=Fn.f32c(torch.cat([wa.bias, wb.bias], dim=0)))
+    if fc1 is not None:
+        keep.update(w1=Fn.as_compute(fc1.weight, code), b1=Fn.f32c(fc1.bias))
+    return keep
+
+
+def _clam_weights(code, device, fc1, gated, wc, bc, wcls=None, bcls=None, n_classes=0, n_att=0, shared=None, bound=None, image=True):
+    """One ``hipt_clam_weights`` (include/hipt_abmil.h) and the dict of tensors that keep its pointers alive.  ``fc1`` /
+    ``gated``: the ``Linear(S0, S1)`` and the ``Attn_Net_Gated`` (``fc1`` None: the head alone, ``s0 = 0``, nothing pooled);
+    ``wc`` / ``bc`` / ``wcls`` / ``bcls``: this struct's rows of ``attention_c`` and its bag classifier; ``shared``: an
+    already-cast :func:`_cast_shared`; ``bound``: ``sum |wc|`` where the caller has read it back already."""
+    keep = dict(_cast_shared(code, fc1, gated) if shared is None else shared, wc=Fn.f32c(wc), bc=Fn.f32c(bc))
+    if wcls is not None:
+        keep.update(wcls=Fn.f32c(wcls), bcls=Fn.f32c(bcls))
+    w = N.ClamWeights()
+    w.dtype, w.s0, w.s1, w.s2 = code, fc1.in_features if fc1 is not None else 0, gated.attention_a[0].in_features, gated.attention_a[0].out_features
+    w.n_classes, w.n_att = n_classes, n_att
+    for name, t in keep.items():
+        setattr(w, name, t.data_ptr())
+    if fc1 is None:
+        return w, keep
+    # |A_raw - bc| <= sum |wc_j| (tanh * sigmoid lies in (-1, 1)): lets the streaming kernel exponentiate against a fixed
+    # shift instead of a running maximum (include/hipt_abmil.h, hipt_clam_weights.logit_bound); one tiny reduction per
+    # set of weights, read back here once
+    # (0 means "unknown" in the ABI: an all-zero attention_c -- a zero-initialised head -- has the bound 0 and still takes the
+    #  streaming kernel through the smallest positive bound.  The read-back synchronises once per set of weights; pack outside
+    #  a graph capture.)
+    w.logit_bound = max(float(keep["wc"].abs().sum().item() if bound is None else bound), 1e-30)
+    # the streaming kernel's LDS image of these weights (bf16 [384|192,128,64]): packed once here, copied straight by
+    # LDS-DMA at every launch
+    nb = N.lib().hipt_clam_stream_packed_bytes(C_.byref(w)) if image else 0
+    if nb:
+        keep["stream_pk"] = torch.empty(nb, dtype=torch.uint8, device=device)
+        N.call("hipt_clam_stream_pack", C_.byref(w), N.ptr(keep["stream_pk"]), N.stream_ptr(device))
+        w.stream_pk = keep["stream_pk"].data_ptr()
+    return w, keep
 
 
 class Attn_Net(nn.Module):
@@ -83,7 +120,7 @@ class Attn_Net(nn.Module):
         return self.module(x), x
 
 
-class Attn_Net_Gated(nn.Module):
+class Attn_Net_Gated(WeightImageCache, nn.Module):
     """Gated attention head (model_clam.py:41-64): A = (tanh(x Wa^T) * sigmoid(x Wb^T)) Wc^T."""
 
     def __init__(self, L=1024, D=256, dropout=0.0, n_classes=1):
@@ -96,37 +133,14 @@ class Attn_Net_Gated(nn.Module):
         self.attention_a = nn.Sequential(*a)
         self.attention_b = nn.Sequential(*b)
         self.attention_c = nn.Linear(D, n_classes)
-        self._compute_dtype = _default_dtype()
-        self._packed = None
-
-    def set_compute_dtype(self, name):
-        N.dtype_code(name)
-        self._compute_dtype = "bf16" if name in ("bf16", "bfloat16") else "fp32"
-        return self
+        self._init_host()
 
     def _torch_forward(self, x):
         return self.attention_c(self.attention_a(x).mul(self.attention_b(x))), x
 
-    def __getstate__(self):  # the packed weight image (ctypes struct + tensors) is a cache: never pickled / deep-copied
-        d = self.__dict__.copy()
-        d["_packed"] = None
-        return d
-
     def _pack(self, device):
-        code = N.dtype_code(self._compute_dtype)
-        N.same_device("Attn_Net_Gated", device, *self.parameters())
-        key = (code, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if self._packed is None or self._packed[0] != key:
-            wa, wb = self.attention_a[0], self.attention_b[0]
-            keep = dict(
-                wab=Fn.as_compute(torch.cat([wa.weight, wb.weight], dim=0), code),
-                bab=Fn.f32c(torch.cat([wa.bias, wb.bias], dim=0)),
-                wc=Fn.f32c(self.attention_c.weight.reshape(-1)), bc=Fn.f32c(self.attention_c.bias))
-            w = N.ClamWeights()
-            w.dtype, w.s0, w.s1, w.s2, w.n_classes = code, 0, wa.in_features, wa.out_features, 0
-            w.wab, w.bab, w.wc, w.bc = (keep[k].data_ptr() for k in ("wab", "bab", "wc", "bc"))
-            self._packed = (key, w, keep)
-        return self._packed[1]
+        c = self.attention_c
+        return self._cached(device, (), lambda code: _clam_weights(code, device, None, self, c.weight.reshape(-1), c.bias))[0]
 
     def forward(self, x):
         dropout_on = self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules())
@@ -247,7 +261,7 @@ class _ClamTrainFn(torch.autograd.Function):
                 out["dwc"].reshape(wc_shape), out["dbc"], *gcls)
 
 
-class CLAM_SB(nn.Module):
+class CLAM_SB(WeightImageCache, nn.Module):
     """Single-branch CLAM / ABMIL (model_clam.py:77-191).
 
     ``size_arg`` is a key of the reference's size table (plus ``'hipt_384'``) or an explicit
@@ -280,17 +294,7 @@ class CLAM_SB(nn.Module):
         self._gate = gate
         self._dropout = dropout
         self._sizes = tuple(size)
-        self._compute_dtype = _default_dtype()
-        self._packed = None
-
-    def set_compute_dtype(self, name):
-        N.dtype_code(name)
-        self._compute_dtype = "bf16" if name in ("bf16", "bfloat16") else "fp32"
-        return self
-
-    @property
-    def compute_dtype(self):
-        return self._compute_dtype
+        self._init_host()
 
     def relocate(self):
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -417,45 +421,13 @@ class CLAM_SB(nn.Module):
         return dropout_on or _needs_autograd(self, h)
 
     # ---- HIP inference path ---------------------------------------------------------------------------
-    def __getstate__(self):  # the packed weight image (ctypes struct + tensors) is a cache: never pickled / deep-copied
-        d = self.__dict__.copy()
-        d["_packed"] = None
-        return d
-
     def _pack(self, device):
-        code = N.dtype_code(self._compute_dtype)
-        N.same_device(type(self).__name__, device, *self.parameters())  # e.g. relocate() never called: a clean error, not a GPU fault
-        key = (code, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if self._packed is None or self._packed[0] != key:
+        def build(code):
             fc1, gated = self.attention_net[0], self.attention_net[-1]
-            wa, wb, wc = gated.attention_a[0], gated.attention_b[0], gated.attention_c
-            keep = dict(
-                w1=Fn.as_compute(fc1.weight, code), b1=Fn.f32c(fc1.bias),
-                wab=Fn.as_compute(torch.cat([wa.weight, wb.weight], dim=0), code),
-                bab=Fn.f32c(torch.cat([wa.bias, wb.bias], dim=0)),
-                wc=Fn.f32c(wc.weight.reshape(-1)), bc=Fn.f32c(wc.bias),
-                wcls=Fn.f32c(self.classifiers.weight), bcls=Fn.f32c(self.classifiers.bias))
-            w = N.ClamWeights()
-            w.dtype, w.s0, w.s1, w.s2 = code, fc1.in_features, fc1.out_features, wa.out_features
-            w.n_classes = self.classifiers.out_features
-            for k, t in keep.items():
-                setattr(w, k, t.data_ptr())
-            # |A_raw - bc| <= sum |wc_j| (tanh * sigmoid lies in (-1, 1)): lets the streaming kernel exponentiate against a fixed
-            # shift instead of a running maximum (include/hipt_abmil.h, hipt_clam_weights.logit_bound); one tiny reduction per
-            # set of weights, read back here once
-            # (0 means "unknown" in the ABI: an all-zero attention_c -- a zero-initialised head -- has the bound 0 and still takes the
-            #  streaming kernel through the smallest positive bound.  The read-back synchronises once per set of weights; pack outside
-            #  a graph capture.)
-            w.logit_bound = max(float(keep["wc"].abs().sum().item()), 1e-30)
-            # the streaming kernel's LDS image of these weights (bf16 [384|192,128,64]): packed once here, copied straight by
-            # LDS-DMA at every launch
-            nb = N.lib().hipt_clam_stream_packed_bytes(C_.byref(w))
-            if nb:
-                keep["stream_pk"] = torch.empty(nb, dtype=torch.uint8, device=device)
-                N.call("hipt_clam_stream_pack", C_.byref(w), N.ptr(keep["stream_pk"]), N.stream_ptr(device))
-                w.stream_pk = keep["stream_pk"].data_ptr()
-            self._packed = (key, w, keep)
-        return self._packed[1]
+            c = gated.attention_c
+            return _clam_weights(code, device, fc1, gated, c.weight.reshape(-1), c.bias, self.classifiers.weight, self.classifiers.bias,
+                                 n_classes=self.classifiers.out_features)
+        return self._cached(device, (), build)[0]
 
     def forward(self, h, label=None, instance_eval=False, return_features=False, attention_only=False):
         dropout_on = self.training and self._dropout > 0
@@ -539,55 +511,24 @@ class CLAM_MB(CLAM_SB):
         return out
 
     def _pack_branches(self, device):
-        """One ``hipt_clam_weights`` per attention branch for the inference kernels: shared W1 / [Wa; Wb] tensors, the branch's row of
-        ``attention_c`` and its ``Linear(S1, 1)`` as a one-class bag classifier (cached like ``_pack``)."""
-        code = N.dtype_code(self._compute_dtype)
-        N.same_device(type(self).__name__, device, *self.parameters())
-        key = ("mb", code, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if self._packed is None or self._packed[0] != key:
-            fc1, gated = self.attention_net[0], self.attention_net[-1]
-            wa, wb, wc = gated.attention_a[0], gated.attention_b[0], gated.attention_c
-            shared = dict(
-                w1=Fn.as_compute(fc1.weight, code), b1=Fn.f32c(fc1.bias),
-                wab=Fn.as_compute(torch.cat([wa.weight, wb.weight], dim=0), code),
-                bab=Fn.f32c(torch.cat([wa.bias, wb.bias], dim=0)))
-            wc_all, bc_all = Fn.f32c(wc.weight), Fn.f32c(wc.bias)
+        """``(ws, mb)``: one ``hipt_clam_weights`` per attention branch for the inference kernels -- shared W1 / [Wa; Wb] tensors, the
+        branch's row of ``attention_c`` and its ``Linear(S1, 1)`` as a one-class bag classifier -- and the stacked struct of the one-pass
+        kernel, or None where the library does not take the configuration (cached like ``_pack``)."""
+        def build(code):
+            fc1, gated, K = self.attention_net[0], self.attention_net[-1], self.n_classes
+            shared = _cast_shared(code, fc1, gated)
+            wc_all, bc_all = Fn.f32c(gated.attention_c.weight), Fn.f32c(gated.attention_c.bias)
             bounds = wc_all.abs().sum(dim=1).tolist()  # per branch: |A_raw[k] - bc[k]| <= sum_j |wc[k][j]| (one read-back per set of weights)
-            ws, keep = [], [shared, wc_all, bc_all]
-            for k in range(self.n_classes):
-                own = dict(wc=wc_all[k], bc=bc_all[k:k + 1], wcls=Fn.f32c(self.classifiers[k].weight), bcls=Fn.f32c(self.classifiers[k].bias))
-                w = N.ClamWeights()
-                w.dtype, w.s0, w.s1, w.s2, w.n_classes = code, fc1.in_features, fc1.out_features, wa.out_features, 1
-                for name, t in {**shared, **own}.items():
-                    setattr(w, name, t.data_ptr())
-                w.logit_bound = max(float(bounds[k]), 1e-30)
-                nb = N.lib().hipt_clam_stream_packed_bytes(C_.byref(w))
-                if nb:
-                    own["stream_pk"] = torch.empty(nb, dtype=torch.uint8, device=device)
-                    N.call("hipt_clam_stream_pack", C_.byref(w), N.ptr(own["stream_pk"]), N.stream_ptr(device))
-                    w.stream_pk = own["stream_pk"].data_ptr()
-                ws.append(w)
-                keep.append(own)
+            made = [_clam_weights(code, device, fc1, gated, wc_all[k], bc_all[k:k + 1], self.classifiers[k].weight, self.classifiers[k].bias,
+                                  n_classes=1, shared=shared, bound=bounds[k]) for k in range(K)]
             # all K branches in ONE pass over the bag (hipt_clam_mb_forward, round 6) where the streaming kernel takes the configuration:
             # the same shared tensors, wc / bc / the K one-row classifiers stacked, the image packed with its K rows of wc
-            wm, mb = N.ClamWeights(), None
-            wm.dtype, wm.s0, wm.s1, wm.s2 = code, fc1.in_features, fc1.out_features, wa.out_features
-            wm.n_classes = wm.n_att = self.n_classes
-            own = dict(wc=wc_all, bc=bc_all, wcls=Fn.f32c(torch.cat([c.weight for c in self.classifiers], dim=0)),
-                       bcls=Fn.f32c(torch.cat([c.bias for c in self.classifiers], dim=0)))
-            for name, t in {**shared, **own}.items():
-                setattr(wm, name, t.data_ptr())
-            wm.logit_bound = max(max(float(b) for b in bounds), 1e-30)
-            nb = N.lib().hipt_clam_stream_packed_bytes(C_.byref(wm)) if 2 <= self.n_classes <= 4 else 0
-            if nb:
-                own["stream_pk"] = torch.empty(nb, dtype=torch.uint8, device=device)
-                N.call("hipt_clam_stream_pack", C_.byref(wm), N.ptr(own["stream_pk"]), N.stream_ptr(device))
-                wm.stream_pk = own["stream_pk"].data_ptr()
-                if N.lib().hipt_clam_mb_supported(C_.byref(wm)):
-                    mb = wm
-            keep.append(own)
-            self._packed = (key, ws, keep, mb)
-        return self._packed[1]
+            wm, keep = _clam_weights(code, device, fc1, gated, wc_all, bc_all, torch.cat([c.weight for c in self.classifiers], dim=0),
+                                     torch.cat([c.bias for c in self.classifiers], dim=0), n_classes=K, n_att=K, shared=shared,
+                                     bound=max(bounds), image=2 <= K <= 4)
+            mb = wm if wm.stream_pk and N.lib().hipt_clam_mb_supported(C_.byref(wm)) else None
+            return [w for w, _ in made], mb, (made, wm, keep)
+        return self._cached(device, ("mb",), build)[:2]
 
     def _multi_infer(self, h, label, instance_eval, return_features, attention_only):
         """model_clam.py:226-264 without autograd: A [K, N] -> softmax over N per branch -> M [K, S1] -> logits[0, c] =
@@ -595,12 +536,13 @@ class CLAM_MB(CLAM_SB):
         N.require_cuda(h, "CLAM_MB")
         if h.dim() != 2 or h.shape[0] == 0 or h.shape[1] != self._sizes[0]:
             raise ValueError(f"expected a non-empty [N, {self._sizes[0]}] bag, got {tuple(h.shape)}")
-        ws = self._pack_branches(h.device)
+        ws, mb = self._pack_branches(h.device)
+        if not self.one_pass:
+            mb = None
         dev, K, n = h.device, self.n_classes, h.shape[0]
         bag = Fn.as_compute(h, ws[0].dtype)
         st = N.stream_ptr(dev)
         A_raw = torch.empty((K, n), dtype=torch.float32, device=dev)
-        mb = self._packed[3] if self.one_pass else None
         S1 = self._sizes[1]
         if mb is not None:
             # ONE pass over the bag: gate once per row, K logits, h1 left in bf16 for the pooling kernel (two launches instead of K)

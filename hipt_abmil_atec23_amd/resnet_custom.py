@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _native as N
 from . import functional as Fn
+from ._host import WeightImageCache
 
 __all__ = ['ResNet_Baseline', 'Bottleneck_Baseline', 'resnet18_baseline', 'resnet50_baseline', 'load_pretrained_weights']
 
@@ -39,10 +40,6 @@ model_urls = {
 }
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-
-
-def _default_dtype() -> str:
-    return os.environ.get("HIPT_AMD_DTYPE", "fp32")
 
 
 def _conv_bn_struct(conv: nn.Conv2d, bn: nn.BatchNorm2d, keep: list) -> N.ConvBN:
@@ -180,7 +177,8 @@ class _PackedResnet:
         return C.byref(self.w)
 
 
-class ResNet_Baseline(nn.Module):
+class ResNet_Baseline(WeightImageCache, nn.Module):
+    _image_buffers = True  # the BN running statistics are folded into the image with the parameters
 
     def __init__(self, block, layers):
         self.inplanes = 64
@@ -200,10 +198,8 @@ class ResNet_Baseline(nn.Module):
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
-        self._compute_dtype = _default_dtype()
+        self._init_host()
         self._norm = IMAGENET_MEAN + IMAGENET_STD
-        self._packed = {}  # device -> (key, _PackedResnet): one image per device (nn.DataParallel replicas share this dict)
-        self._warned_grad = False
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -218,21 +214,7 @@ class ResNet_Baseline(nn.Module):
             layers.append(block(self.inplanes, planes))
         return nn.Sequential(*layers)
 
-    def __getstate__(self):
-        d = self.__dict__.copy()
-        d["_packed"] = {}
-        return d
-
     # ---- settings ---------------------------------------------------------------------------------------------------
-    def set_compute_dtype(self, name: str):
-        N.dtype_code(name)
-        self._compute_dtype = "bf16" if name in ("bf16", "bfloat16") else "fp32"
-        return self
-
-    @property
-    def compute_dtype(self) -> str:
-        return self._compute_dtype
-
     def set_input_normalization(self, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         """Per-channel ``Normalize(mean, std)`` applied on the device to uint8 input (after ``/ 255``); fp32 input is taken as
         already normalised.  A scalar applies to all three channels (``--use_transforms HIPT``: ``0.5, 0.5``)."""
@@ -249,37 +231,16 @@ class ResNet_Baseline(nn.Module):
         """Device the weights live on; survives DataParallel replication (``next(self.parameters())`` does not)."""
         return self.conv1.weight.device
 
-    def _tensors(self):
-        """Parameters and BN running statistics (both enter the folded image).  A ``nn.DataParallel`` replica keeps its
-        parameters in ``_former_parameters`` (torch/nn/parallel/replicate.py; extract_features_fp.py:217-218 wraps the model)."""
-        ps = list(self.parameters())
-        if not ps:
-            ps = [t for m in self.modules() for t in getattr(m, "_former_parameters", {}).values() if t is not None]
-        return ps + [b for b in self.buffers() if b.is_floating_point()]
-
-    def _version_key(self):
-        return tuple((t.data_ptr(), t._version) for t in self._tensors())
-
     def _check_inference_only(self):
         if self.training:
             raise RuntimeError("ResNet_Baseline HIP forward: BatchNorm in train() mode needs batch statistics (inference kernels "
                                "only); call .eval()")
-        if torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
-            import warnings
-            warnings.warn("HIP ResNet_Baseline forward returns tensors without grad_fn: no gradient flows into the extractor "
-                          "weights (the reference uses it as a frozen feature extractor)", stacklevel=3)
-            self._warned_grad = True
+        self._warn_no_grad_fn("HIP ResNet_Baseline forward returns tensors without grad_fn: no gradient flows into the extractor "
+                              "weights (the reference uses it as a frozen feature extractor)")
 
     def _packed_for(self, dev) -> _PackedResnet:
         self._check_inference_only()
-        code = N.dtype_code(self._compute_dtype)
-        key = (code, self._version_key())
-        pk = self._packed.get(dev)
-        if pk is None or pk[0] != key:
-            N.same_device(type(self).__name__, dev, *self._tensors())
-            pk = (key, _PackedResnet(self, code, dev))
-            self._packed[dev] = pk
-        return pk[1]
+        return self._cached(dev, (), lambda code: _PackedResnet(self, code, dev))
 
     # ---- forward ------------------------------------------------------------------------------------------------------
     @staticmethod

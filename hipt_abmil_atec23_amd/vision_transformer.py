@@ -15,7 +15,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from functools import partial
 
 import torch
@@ -23,16 +22,13 @@ import torch.nn as nn
 
 from . import _native as N
 from . import functional as Fn
+from ._host import WeightImageCache, default_dtype
 
 
 def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
     """Truncated-normal initialiser with the reference's argument meaning
     (vision_transformer.py:63-65)."""
     return nn.init.trunc_normal_(tensor, mean=mean, std=std, a=a, b=b)
-
-
-def _default_dtype() -> str:
-    return os.environ.get("HIPT_AMD_DTYPE", "fp32")
 
 
 class _PackedVit:
@@ -111,46 +107,15 @@ class _PackedVit:
         return C.byref(self.w)
 
 
-class _HipVitMixin:
+class _HipVitMixin(WeightImageCache):
     """Shared machinery of VisionTransformer / VisionTransformer4K."""
 
-    def _init_native(self):
-        self._compute_dtype = _default_dtype()
-        self._packed = {}      # device -> (key, _PackedVit): one weight image per device (nn.DataParallel replicas share this dict)
-        self._pos_cache = {}   # device -> (key, interpolated positional table)
-        self._warned_grad = False
-
-    def __getstate__(self):
-        """The device-side images (ctypes structs + packed tensors) are caches: never pickled, never deep-copied."""
-        d = self.__dict__.copy()
-        d["_packed"], d["_pos_cache"] = {}, {}
-        return d
-
-    def set_compute_dtype(self, name: str):
-        N.dtype_code(name)
-        self._compute_dtype = "bf16" if name in ("bf16", "bfloat16") else "fp32"
-        return self
-
-    @property
-    def compute_dtype(self) -> str:
-        return self._compute_dtype
-
-    def _tensors(self):
-        """The weight tensors of this module tree.  A ``nn.DataParallel`` replica has no ``parameters()`` (they are plain
-        attributes there, torch/nn/parallel/replicate.py; the reference wraps the model so whenever it sees more than one
-        GPU, extract_features_fp.py:217-218): take them from ``_former_parameters``."""
-        ps = list(self.parameters())
-        if ps:
-            return ps
-        return [t for m in self.modules() for t in getattr(m, "_former_parameters", {}).values() if t is not None]
+    _caches = ("_packed", "_pos_cache")  # device -> (key, _PackedVit); device -> (key, interpolated positional table)
 
     @property
     def weight_device(self):
         """Device the weights live on; survives DataParallel replication (``next(self.parameters())`` does not)."""
         return self.pos_embed.device
-
-    def _version_key(self):
-        return tuple((p.data_ptr(), p._version) for p in self._tensors())
 
     def _check_inference_only(self):
         """The HIP forwards are inference kernels (the ViTs are frozen feature extractors, hipt_model_utils.py:55-57):
@@ -161,11 +126,8 @@ class _HipVitMixin:
                     raise RuntimeError("HIP ViT forward: dropout p > 0 in train() mode is not implemented (inference kernels); call .eval()")
                 if isinstance(m, DropPath) and (m.drop_prob or 0.) > 0:
                     raise RuntimeError("HIP ViT forward: drop_path > 0 in train() mode is not implemented (inference kernels); call .eval()")
-        if torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
-            import warnings
-            warnings.warn("HIP ViT forward returns tensors without grad_fn: no gradient flows into the ViT weights "
-                          "(the reference freezes them, hipt_model_utils.py:55-57)", stacklevel=3)
-            self._warned_grad = True
+        self._warn_no_grad_fn("HIP ViT forward returns tensors without grad_fn: no gradient flows into the ViT weights "
+                              "(the reference freezes them, hipt_model_utils.py:55-57)")
 
     def _pos_for(self, ntok_patches: int, w: int, h: int) -> torch.Tensor:
         dev = self.pos_embed.device
@@ -179,16 +141,7 @@ class _HipVitMixin:
 
     def _packed_for(self, pos: torch.Tensor) -> _PackedVit:
         self._check_inference_only()
-        code = N.dtype_code(self._compute_dtype)
-        key = (code, pos.data_ptr(), pos.shape[1], self._version_key())
-        pk = self._packed.get(pos.device)
-        if pk is None or pk[0] != key:
-            ts = self._tensors()
-            N.same_device(type(self).__name__, pos.device, *ts)
-            ew, eb, ek = self._embed_params()
-            pk = (key, _PackedVit(self, code, pos, ew, eb, ek))
-            self._packed[pos.device] = pk
-        return pk[1]
+        return self._cached(pos.device, (pos.data_ptr(), pos.shape[1]), lambda code: _PackedVit(self, code, pos, *self._embed_params()))
 
     # ---- shared tails -------------------------------------------------------------------
     def _blocks(self, pk, x, b0, b1, probs=None):
@@ -245,7 +198,7 @@ class _HipVitMixin:
 # ------------------------------------------------------------------------------------------
 
 def _code_of(module) -> int:
-    return N.dtype_code(getattr(module, "_compute_dtype", _default_dtype()))
+    return N.dtype_code(getattr(module, "_compute_dtype", default_dtype()))
 
 
 class Mlp(nn.Module):
@@ -366,7 +319,7 @@ class VisionTransformer(_HipVitMixin, nn.Module):
         trunc_normal_(self.pos_embed, std=.02)
         trunc_normal_(self.cls_token, std=.02)
         self.apply(self._init_weights)
-        self._init_native()
+        self._init_host()
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):

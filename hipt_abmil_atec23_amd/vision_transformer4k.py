@@ -40,7 +40,7 @@ class VisionTransformer4K(_HipVitMixin, nn.Module):
         trunc_normal_(self.pos_embed, std=.02)
         trunc_normal_(self.cls_token, std=.02)
         self.apply(self._init_weights)
-        self._init_native()
+        self._init_host()
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):

@@ -1059,6 +1059,48 @@ def test_clam_generic_then_streaming_model_share_one_workspace():
             assert int(ws[:256].sum()) == 0, key
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("kind", ["attn_net_gated", "clam_sb", "clam_mb"])
+def test_clam_weight_changes_repack(kind, dtype):
+    """The cached weight image follows the weights: after an in-place change of ``attention_c.weight`` the next forward differs
+    and has the bits of a freshly constructed module loaded with the changed state dict.  'hipt_384' sizes, 33 rows (two 16-row
+    fragments and a tail of one); the halved attention_c keeps sum |wc| below the fixed-shift bound, so the bf16 modules stay on
+    the streaming kernels, whose packed image carries wc."""
+    from hipt_abmil_atec23_amd import CLAM_MB, CLAM_SB, Attn_Net_Gated
+    head, multi = kind == "attn_net_gated", kind == "clam_mb"
+    sd = synth.make_state_dict(synth.clam_param_specs((384, 128, 64), n_classes=2, multi=multi), 384 + int(multi))
+    if head:
+        sd = {k[len("attention_net.2."):]: v for k, v in sd.items() if k.startswith("attention_net.2.")}
+
+    def make(state):
+        m = Attn_Net_Gated(L=128, D=64) if head else (CLAM_MB if multi else CLAM_SB)(size_arg="hipt_384", n_classes=2)
+        m.load_state_dict(state, strict=True)
+        return m.eval().to(DEV).set_compute_dtype(dtype)
+
+    def run(m):
+        before = N.calls
+        with torch.no_grad():
+            if head:
+                out = {"A": m(x)[0]}
+            else:
+                logits, y_prob, y_hat, a_raw, res = m(x, return_features=True)
+                out = {"logits": logits, "Y_prob": y_prob, "Y_hat": y_hat, "A": a_raw, "M": res["features"]}
+        assert N.calls > before  # the HIP entry points ran
+        return {k: v.clone() for k, v in out.items()}
+
+    x = synth.hash_uniform_torch((33, 128 if head else 384), 33, device=DEV)
+    m = make(sd)
+    first = run(m)
+    with torch.no_grad():
+        (m if head else m.attention_net[-1]).attention_c.weight.mul_(0.5)
+    second = run(m)
+    assert not torch.equal(second["A"], first["A"])
+    assert head or not torch.equal(second["logits"], first["logits"])
+    fresh = run(make(m.state_dict()))
+    for k in second:
+        assert torch.equal(second[k], fresh[k]), k
+
+
 def test_clam_sb_bf16_hipt_big_stream_kernel():
     """The aggregator BASELINE configs[4] runs (CLAM_SB 'hipt_big' [192,128,64] in bf16 = abmil_stream_kernel<3>) against the
     reference golden at N = 500 and against the fp64 oracle on an 8 192 x 192 bag (the size of a slide's feature bag).
