@@ -31,6 +31,9 @@ _LAZY = {
     "generate_sample_idxs": ("sampling", "generate_sample_idxs"), "resnet_patch_features": ("sampling", "resnet_patch_features"),
     # bootstrapped evaluation metrics (bootstrapping.py)
     "bootstrap_metrics": ("bootstrap", "bootstrap_metrics"), "bootstrap_eval_dir": ("bootstrap", "bootstrap_eval_dir"),
+    # attention heat-maps (WholeSlideImage.visHeatmap)
+    "heatmap_overlay": ("heatmap", "heatmap_overlay"), "render_heatmap": ("heatmap", "render_heatmap"),
+    "vis_heatmap": ("heatmap", "vis_heatmap"),
 }
 
 

@@ -77,6 +77,7 @@ KNN_SPATIAL, KNN_TEXTURAL = 0, 1
 SAMPLING_MAX, SAMPLING_NEWEST, SAMPLING_AVERAGE = 0, 1, 2
 BOOTSTRAP_MAX_N, BOOTSTRAP_MAX_CLASSES, BOOTSTRAP_MAX_REPLICATES = 4096, 8, 1 << 20
 BOOTSTRAP_DEGENERATE, BOOTSTRAP_BAD_INPUT = 1, 2
+HEATMAP_TILE_W, HEATMAP_TILE_H, HEATMAP_MAX_DIM, HEATMAP_LUT_ENTRIES = 32, 8, 1 << 20, 258
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -151,6 +152,9 @@ SIGNATURES = {
     "hipt_sampling_update_workspace_bytes": (_sz, [_i]),
     "hipt_sampling_update": (_i, [_p, _i, _p, _i, _p, _i, _i, _p, _i, C.c_double, _i, _p, _p, _sz, _p]),
     "hipt_bootstrap_metrics": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p]),
+    "hipt_heatmap_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "hipt_heatmap_overlay": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "hipt_heatmap_render": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, C.c_double, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -11,7 +11,10 @@ The reference imports the hot-path classes by module path:
   extract_features_fp.py:19,210-211).  ``install(sampling=True)`` makes ``utils.sampling_utils.generate_sample_idxs`` and
   ``update_sampling_weights`` (what ``summary_sampling`` calls, utils/eval_utils.py:18,298-467) this package's: where the
   reference's module imports, the two names are rebound ON it (eval_utils.py takes its plotting helpers from the same module);
-  where it does not, a module is registered whose plotting names raise.  The alternative is the overlay files under ``shims/``.
+  where it does not, a module is registered whose plotting names raise.  ``install(heatmaps=True)`` binds this package's
+  ``vis_heatmap`` as ``wsi_core.WholeSlideImage.WholeSlideImage.visHeatmap`` (what create_heatmaps.py draws with) where the
+  reference's ``wsi_core`` imports (it needs openslide and cv2); elsewhere it does nothing.  The alternative is the overlay files
+  under ``shims/``.
 """
 from __future__ import annotations
 
@@ -98,11 +101,48 @@ def _uninstall_sampling():
         sys.modules.pop("utils", None)
 
 
-def install(verbose: bool = False, resnet: bool = False, sampling: bool = False):
+_WSI_MOD = "wsi_core.WholeSlideImage"
+
+
+def _install_heatmaps(verbose: bool) -> bool:
+    """Bind ``vis_heatmap`` as the reference class's ``visHeatmap`` (opt-in).  False, and nothing done, where the reference's
+    ``wsi_core.WholeSlideImage`` does not import: there is no class to bind to, and the reading, segmenting and contour code of
+    that module is not this package's."""
+    from . import heatmap
+    if _WSI_MOD in _saved:
+        return True
+    try:
+        if _WSI_MOD not in sys.modules and importlib.util.find_spec(_WSI_MOD) is None:
+            return False
+        cls = importlib.import_module(_WSI_MOD).WholeSlideImage
+    except Exception:   # no reference checkout on sys.path, or openslide / cv2 missing
+        return False
+    _saved[_WSI_MOD] = cls.__dict__.get("visHeatmap")
+    cls.visHeatmap = heatmap.vis_heatmap
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_WSI_MOD}.WholeSlideImage.visHeatmap -> {heatmap.__name__}.vis_heatmap")
+    return True
+
+
+def _uninstall_heatmaps():
+    if _WSI_MOD not in _saved:
+        return
+    prev = _saved.pop(_WSI_MOD)
+    cls = sys.modules[_WSI_MOD].WholeSlideImage
+    if prev is None:
+        del cls.visHeatmap
+    else:
+        cls.visHeatmap = prev
+
+
+def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
-    ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling)."""
+    ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
+    ``heatmaps=True`` also binds ``WholeSlideImage.visHeatmap`` where the reference's ``wsi_core`` imports (else a no-op)."""
     done = {}
+    if heatmaps and _install_heatmaps(verbose):
+        done[_WSI_MOD + ".WholeSlideImage.visHeatmap"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.vis_heatmap"
     if sampling:
         _install_sampling(verbose)
         done[_SAMPLING_MOD] = f"{__name__.rsplit('.', 1)[0]}.sampling"
@@ -141,6 +181,7 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False)
 
 def uninstall():
     _uninstall_sampling()
+    _uninstall_heatmaps()
     for ref_name in _MAP:
         sys.modules.pop(ref_name, None)
     for ref_name in _RESNET_MAP:

@@ -34,7 +34,8 @@ extern "C" {
 /* 5 (round 6): the HIPT_PACK_MLP image of format 3 is 2*D*hidden*2 + D*D*2 bytes (six proj units in front: ask
  * hipt_vit_packed_bytes, never compute the size) and packing it reads blocks[i].proj_w, which must be set first;
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
- * 6: hipt_bootstrap_metrics added (nothing else changed). */
+ * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
+ * _render) were added later under the same number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -588,6 +589,44 @@ enum { HIPT_BOOTSTRAP_DEGENERATE = 1, HIPT_BOOTSTRAP_BAD_INPUT = 2 };   /* bits 
  * nothing.  No workspace. */
 int hipt_bootstrap_metrics(const int32_t* Y, const int32_t* Y_hat, const int32_t* order, const int32_t* tie, int n, int K,
                            const int32_t* idx, int B, double* out, int32_t* flags, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Attention heat-map rasteriser (wsi_core/WholeSlideImage.py:576-684, visHeatmap with blur=False).
+ * N patches of one size pw x ph (canvas pixels) at xy[i] = (x, y), the patch's top-left canvas pixel, carry one value v[i]:
+ *   overlay[p] = (sum of v[i] over the patches covering pixel p, added in ASCENDING i, in float64) / count[p],
+ *                rounded half to even when `binarize`; 0 where count[p] = 0;
+ *   count[p]   = the number of covering patches (int32; the reference wraps a uint16);
+ *   painted[p] = 1 if some covering patch has paint[i] != 0 (paint NULL: every patch paints).
+ * Patches are clipped at the canvas edge; one that lies wholly outside covers nothing.  Pixels gather from per-tile candidate
+ * lists (tiles of HIPT_HEATMAP_TILE_W x HIPT_HEATMAP_TILE_H pixels, binned on the device and put into ascending patch index);
+ * there is no floating-point atomic, so the results are a function of the inputs alone, bit for bit what the numpy loops give.
+ * A patch touches at most (ceil(pw / TILE_W) + 1) * (ceil(ph / TILE_H) + 1) tiles, which bounds the workspace from
+ * N, pw, ph, w, h.  Envelope: w, h <= HIPT_HEATMAP_MAX_DIM and N times that tile bound < 2^31, else HIPT_E_UNSUPPORTED with
+ * nothing launched.  N = 0 is legal (no workspace needed: the size function returns 0).
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_HEATMAP_TILE_W 32
+#define HIPT_HEATMAP_TILE_H 8
+#define HIPT_HEATMAP_MAX_DIM (1 << 20)     /* canvas side in pixels */
+#define HIPT_HEATMAP_LUT_ENTRIES 258       /* 256 colours, then the under and the over colour */
+
+/* workspace: 256-byte aligned; 0 for N = 0 or a request outside the envelope. */
+size_t hipt_heatmap_workspace_bytes(int N, int pw, int ph, int w, int h);
+
+/* xy int32 [N, 2], v float64 [N], paint uint8 [N] or NULL; overlay float64 [h, w], count int32 [h, w], painted uint8 [h, w]:
+ * each output may be NULL, not all three. */
+int hipt_heatmap_overlay(const int32_t* xy, const double* v, const uint8_t* paint, int N, int pw, int ph, int w, int h,
+                         int binarize, double* overlay, int32_t* count, uint8_t* painted, void* workspace, size_t ws_bytes,
+                         void* stream);
+
+/* The image of the same overlay.  Per pixel p, with base = canvas[p] (canvas uint8 [h, w, 3], NULL = white):
+ *   colour = painted[p] and (mask NULL or mask[p] != 0; mask uint8 [h, w]) ? lut[index(overlay[p])] : base, where for
+ *            t = overlay * 256: t < 0 -> entry 256 (under), t == 256 -> entry 255, t > 256 -> entry 257 (over), else trunc(t);
+ *   img[p]  = alpha < 1 ? sat_u8(rint(float32(colour) * float32(alpha) + float32(base) * float32(1 - alpha))) : colour,
+ * each product and the sum rounded to float32 on its own (no contraction), rint half to even: cv2.addWeighted's formula.
+ * lut uint8 [HIPT_HEATMAP_LUT_ENTRIES, 3]; img uint8 [h, w, 3], 4-byte aligned, not the canvas; overlay float64 [h, w] or NULL. */
+int hipt_heatmap_render(const int32_t* xy, const double* v, const uint8_t* paint, int N, int pw, int ph, int w, int h,
+                        int binarize, const uint8_t* mask, const uint8_t* canvas, const uint8_t* lut, double alpha, uint8_t* img,
+                        double* overlay, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
