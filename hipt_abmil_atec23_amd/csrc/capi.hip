@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "workspace.h"
 
 static thread_local char g_err[512] = "";
 
@@ -20,33 +21,8 @@ void hipt_set_error(const char* fmt, ...) {
 
 namespace {
 
-inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline int esz(int dtype) { return dtype == HIPT_F32 ? 4 : 2; }
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
-
-// Every workspace is described ONCE, by the carve_*() function that hands out its parts: a forward runs it over the caller's
-// buffer, the matching *_workspace_bytes entry point over no buffer at all (the default Carver) and returns `used`.
-struct Carver {
-    char* base;
-    size_t cap, used = 0;
-    Carver(void* b = nullptr, size_t c = SIZE_MAX) : base((char*)b), cap(c) {}
-    void* take(size_t n) {
-        void* p = base ? base + used : nullptr;
-        used += al256(n);
-        return p;
-    }
-    bool ok() const { return used <= cap && (((uintptr_t)base & 255) == 0 || used == 0); }
-};
-template <class F> size_t dry_run(F carve) {
-    Carver c;
-    carve(c);
-    return c.used;
-}
-int check_workspace(const Carver& c, const char* who) {
-    if (c.ok()) return HIPT_OK;
-    hipt_set_error("%s: workspace %zu B too small / unaligned (need %zu)", who, c.cap, c.used);
-    return HIPT_E_WORKSPACE;
-}
 
 // ---- optional per-kernel timing (bench.py's roofline leg): HIP events around every launch -----
 enum { PC_EMBED, PC_LN, PC_QKV, PC_ATTN, PC_PROJ, PC_FC1, PC_FC2, PC_MLP, PC_ABMIL, PC_COMBINE, PC_OTHER, PC_VIT4K, PC_LASTCLS, PC_QKVATT, PC_CLSROWS, PC_N };
@@ -790,12 +766,10 @@ int hipt_vit_mlp_unit(const hipt_vit_weights* w, int block, float* x_img, const 
         hipt_set_error("vit_mlp_unit: bf16, D = 384, hidden %% 128 == 0, nseq * ntok %% 16 == 0 and blocks[%d].mlp_pk in format 3 only", block);
         return HIPT_E_UNSUPPORTED;
     }
-    if (ws_bytes < 256 || ((uintptr_t)workspace & 255) || !workspace) {
-        hipt_set_error("vit_mlp_unit: workspace %zu B too small / unaligned (need 256)", ws_bytes);
-        return HIPT_E_WORKSPACE;
-    }
+    Carver c(workspace, workspace ? ws_bytes : 0);  // (no buffer holds no bytes: a null workspace is refused like a short one)
     BlockScratch s = {};
-    s.queues = (TileQueues*)workspace;  // (the one queue it needs: the first line of the 256 bytes)
+    s.queues = c.take<TileQueues>(1);  // (the one queue it needs: the first line of the 256 bytes)
+    if ((rc = check_workspace(c, "vit_mlp_unit"))) return rc;
     MlpParams m = mlp_params(w, block, M, x_img, s);
     m.y1 = att_img;
     m.fold = 1;

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "launch.h"
+#include "workspace.h"
 
 namespace {
 
@@ -653,6 +654,15 @@ size_t bwd_lds(const hipt_clam_train_weights* w, bool dbag) {
            sizeof(float);
 }
 
+// the scratch of the backward: duv [N, 2 S2] | dz [N, S1] | per-tile (dwc, dbc) partials [ceil(N / TR), n_att S2 + n_att]
+struct TrainBwdWs { float *duv, *dz, *wcpart; };
+void carve_train_bwd(Carver& c, const hipt_clam_train_weights* w, int N, TrainBwdWs& ws) {
+    const size_t G = (size_t)(N + TR - 1) / TR;
+    ws.duv = c.take<float>((size_t)N * 2 * w->s2);
+    ws.dz = c.take<float>((size_t)N * w->s1);
+    ws.wcpart = c.take<float>(G * ((size_t)w->n_att * w->s2 + w->n_att));
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,9 +677,7 @@ int hipt_clam_train_shape_supported(int s0, int s1, int s2, int n_att, int n_cla
 
 size_t hipt_clam_train_workspace_bytes(const hipt_clam_train_weights* w, int N) {
     if (!w || N <= 0) return 0;
-    const size_t G = (size_t)(N + TR - 1) / TR;
-    // duv [N, 2 S2] | dz [N, S1] | per-tile (dwc, dbc) partials
-    return (((size_t)N * 2 * w->s2 + (size_t)N * w->s1 + G * ((size_t)w->n_att * w->s2 + w->n_att)) * sizeof(float) + 1023) & ~(size_t)255;
+    return dry_run([&](Carver& c) { TrainBwdWs ws; carve_train_bwd(c, w, N, ws); });
 }
 
 int hipt_clam_train_forward(const hipt_clam_train_weights* w, const float* bag, int N, const float* m1, const float* ma, const float* mb, float* h1,
@@ -719,17 +727,15 @@ int hipt_clam_train_backward(const hipt_clam_train_weights* w, const float* bag,
     HIPT_CHECK_ARG(bag && h1 && t && s && A_raw && stats && M && dlogits && g, "clam_train_backward: null buffer");
     HIPT_CHECK_ARG(g->dw1 && g->db1 && g->dwa && g->dba && g->dwb && g->dbb && g->dwc && g->dbc && g->dwcls && g->dbcls, "clam_train_backward: null gradient buffer");
     HIPT_CHECK_ARG(n_sel == 0 || (sel_ids && dh1_sel), "clam_train_backward: instance rows without ids / gradients");
-    if (ws_bytes < hipt_clam_train_workspace_bytes(w, N) || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("clam_train_backward: workspace %zu B too small / unaligned (need %zu)", ws_bytes, hipt_clam_train_workspace_bytes(w, N));
-        return HIPT_E_WORKSPACE;
-    }
+    Carver c(workspace, ws_bytes);
+    TrainBwdWs ws;
+    carve_train_bwd(c, w, N, ws);
+    if ((rc = check_workspace(c, "clam_train_backward"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const TrainDims d = dims_of(w, N);
     const TrainW p = ptrs_of(w);
     const int G = (N + TR - 1) / TR, S0 = w->s0, S1 = w->s1, S2 = w->s2, K = w->n_att;
-    float* duv = (float*)workspace;
-    float* dz = duv + (size_t)N * 2 * S2;
-    float* wcpart = dz + (size_t)N * S1;
+    float *const duv = ws.duv, *const dz = ws.dz, *const wcpart = ws.wcpart;
     const size_t lds = bwd_lds(w, g->dbag != nullptr);
     if (lds > 160 * 1024) {
         hipt_set_error("clam_train_backward: widths [%d,%d,%d] need %zu B of LDS", S0, S1, S2, lds);

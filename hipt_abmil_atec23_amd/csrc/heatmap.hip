@@ -16,6 +16,7 @@
 // -ffp-contract=off (Makefile): the blend's two products and their sum are rounded one by one.  No inline assembly.
 #include "common.h"
 #include "kernels.h"
+#include "workspace.h"
 
 namespace {
 
@@ -27,8 +28,6 @@ constexpr int HM_SORT_LDS = 1024;    // longest list sorted in LDS
 constexpr int HM_SCAN = 1024;        // tiles per scan segment
 static_assert(HM_THREADS == 256 && HM_CHUNK == HM_THREADS, "one staged candidate per thread");
 static_assert(HM_TW * 3 + 3 <= HM_TW * 4, "a tile row's bytes plus the misalignment fit one 32-bit word per lane");
-
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct HmGeo {
     int ntx, nty, nt, nb;   // tiles across / down / in all, scan segments
@@ -54,20 +53,13 @@ struct HmWs {
     int *cnt, *cur, *offs, *boff, *entries;
 };
 
-// the workspace's five arrays in order; returns the bytes they take (ws NULL: the size alone)
-size_t hm_carve(const HmGeo& g, char* base, HmWs* ws) {
-    const size_t nt4 = al256((size_t)g.nt * 4);
-    const size_t sizes[5] = {nt4, nt4, nt4, al256((size_t)g.nb * 4), al256((size_t)g.cap * 4)};
-    size_t off[6] = {0};
-    for (int i = 0; i < 5; ++i) off[i + 1] = off[i] + sizes[i];
-    if (ws) {
-        ws->cnt = (int*)(base + off[0]);
-        ws->cur = (int*)(base + off[1]);
-        ws->offs = (int*)(base + off[2]);
-        ws->boff = (int*)(base + off[3]);
-        ws->entries = (int*)(base + off[4]);
-    }
-    return off[5];
+// the workspace's five arrays in order.  cnt and cur stay adjacent: hm_run zeroes the two with one memset that ends at offs.
+void hm_carve(Carver& c, const HmGeo& g, HmWs& ws) {
+    ws.cnt = c.take<int>(g.nt);
+    ws.cur = c.take<int>(g.nt);
+    ws.offs = c.take<int>(g.nt);
+    ws.boff = c.take<int>(g.nb);
+    ws.entries = c.take<int>((size_t)g.cap);
 }
 
 // the part of patch (x, y) that lies on the canvas, as [x0, x1) x [y0, y1); empty when x1 <= x0 or y1 <= y0
@@ -344,12 +336,9 @@ int hm_run(const int32_t* xy, const double* v, const uint8_t* paint, int N, int 
     HIPT_CHECK_ARG(!img || lut, "%s: an image needs the colour table", what);
     HmWs ws = {};
     if (N > 0) {
-        const size_t need = hm_carve(g, nullptr, nullptr);
-        if (!workspace || ws_bytes < need || ((uintptr_t)workspace & 255)) {
-            hipt_set_error("%s: workspace %zu B too small / unaligned (need %zu)", what, ws_bytes, need);
-            return HIPT_E_WORKSPACE;
-        }
-        hm_carve(g, (char*)workspace, &ws);
+        Carver c(workspace, workspace ? ws_bytes : 0);  // (no buffer holds no bytes: a null workspace is refused like a short one)
+        hm_carve(c, g, ws);
+        if (int rc = check_workspace(c, what)) return rc;
         if (hipMemsetAsync(ws.cnt, 0, (size_t)((char*)ws.offs - (char*)ws.cnt), st) != hipSuccess) {   // cnt and cur
             hipt_set_error("%s: hipMemsetAsync failed", what);
             return HIPT_E_LAUNCH;
@@ -404,7 +393,7 @@ int hm_run(const int32_t* xy, const double* v, const uint8_t* paint, int N, int 
 extern "C" size_t hipt_heatmap_workspace_bytes(int N, int pw, int ph, int w, int h) {
     HmGeo g;
     if (N <= 0 || !hm_geo(N, pw, ph, w, h, &g)) return 0;
-    return hm_carve(g, nullptr, nullptr);
+    return dry_run([&](Carver& c) { HmWs ws; hm_carve(c, g, ws); });
 }
 
 extern "C" int hipt_heatmap_overlay(const int32_t* xy, const double* v, const uint8_t* paint, int N, int pw, int ph, int w, int h,

@@ -14,6 +14,7 @@
 // row is computed by the same instruction sequence whatever the batch, so features do not depend on the batch.
 // There are no hand-counted waits in this file (plain C++ loads and stores; the compiler places every s_waitcnt).
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -282,7 +283,6 @@ __global__ void rn_avgpool_kernel(const T* x, int n, int hw, int C, float* out) 
 inline int esize(int dtype) { return dtype == HIPT_BF16 ? 2 : 4; }
 inline int kslab(int dtype) { return dtype == HIPT_BF16 ? 64 : 32; }
 inline int conv_out(int x, int k, int s, int pad) { return (x + 2 * pad - k) / s + 1; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int conv_kp(int cin, int kh, int kw, int dtype) {
     const int K = cin * kh * kw, kb = kslab(dtype);
@@ -398,8 +398,14 @@ int check_weights(const hipt_resnet_weights* w, NetConv* nc, int* count) {
     return HIPT_OK;
 }
 
-size_t conv_w_bytes(int cout, int cin, int k, int dtype) { return align256((size_t)cout * conv_kp(cin, k, k, dtype) * esize(dtype)); }
-size_t conv_b_bytes(int cout) { return align256((size_t)cout * 4); }
+// the packed weight image: per conv, in the order of hipt_resnet_weights.convs, its packed weight | its folded fp32 bias
+struct ConvImg { const void* w; const float* bias; };
+void carve_packed(Carver& c, const NetConv* nc, int count, int dtype, ConvImg* out) {
+    for (int i = 0; i < count; ++i) {
+        out[i].w = c.take((size_t)nc[i].cout * conv_kp(nc[i].cin, nc[i].k, nc[i].k, dtype) * esize(dtype));
+        out[i].bias = c.take<float>(nc[i].cout);
+    }
+}
 
 // workspace: five NHWC activation buffers (A, B: block input / output, T1, T2: bottleneck interior, D: downsample), each
 // as large as the largest tensor it ever holds; T1 also holds the NHWC copy of the input.
@@ -431,8 +437,12 @@ NetPlan plan(const hipt_resnet_weights* w, int n, int h, int wd) {
         }
     }
     (void)inplanes;
-    for (auto& s : pl.sz) s = align256(s);
+    for (auto& s : pl.sz) s = al256(s);
     return pl;
+}
+
+void carve_net(Carver& c, const NetPlan& pl, char* (&buf)[5]) {
+    for (int i = 0; i < 5; ++i) buf[i] = (char*)c.take(pl.sz[i]);
 }
 
 int check_shape(int n, int h, int w) {
@@ -497,9 +507,8 @@ size_t hipt_resnet_packed_bytes(const hipt_resnet_weights* w) {
     NetConv nc[RN_MAX_CONVS];
     int count = 0;
     if (check_weights(w, nc, &count) != HIPT_OK) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < count; ++i) tot += conv_w_bytes(nc[i].cout, nc[i].cin, nc[i].k, w->dtype) + conv_b_bytes(nc[i].cout);
-    return tot;
+    ConvImg img[RN_MAX_CONVS];
+    return dry_run([&](Carver& c) { carve_packed(c, nc, count, w->dtype, img); });
 }
 
 int hipt_resnet_pack_weights(const hipt_resnet_weights* w, void* packed, void* stream) {
@@ -508,13 +517,11 @@ int hipt_resnet_pack_weights(const hipt_resnet_weights* w, void* packed, void* s
     const int rc = check_weights(w, nc, &count);
     if (rc != HIPT_OK) return rc;
     HIPT_CHECK_ARG(packed && ((uintptr_t)packed % 256) == 0, "resnet_pack_weights: packed image must be 256-byte aligned");
-    char* p = (char*)packed;
-    for (int i = 0; i < count; ++i) {
-        const size_t wb = conv_w_bytes(nc[i].cout, nc[i].cin, nc[i].k, w->dtype);
-        const int r = hipt_conv_bn_pack(&w->convs[i], w->dtype, p, (float*)(p + wb), stream);
-        if (r != HIPT_OK) return r;
-        p += wb + conv_b_bytes(nc[i].cout);
-    }
+    ConvImg img[RN_MAX_CONVS];
+    Carver c(packed);
+    carve_packed(c, nc, count, w->dtype, img);
+    for (int i = 0; i < count; ++i)
+        if (int r = hipt_conv_bn_pack(&w->convs[i], w->dtype, (void*)img[i].w, (float*)img[i].bias, stream)) return r;
     return HIPT_OK;
 }
 
@@ -522,8 +529,8 @@ size_t hipt_resnet_workspace_bytes(const hipt_resnet_weights* w, int n, int h, i
     NetConv nc[RN_MAX_CONVS];
     int count = 0;
     if (check_weights(w, nc, &count) != HIPT_OK || n < 1 || h < 1 || wd < 1) return 0;
-    const NetPlan pl = plan(w, n, h, wd);
-    return pl.sz[0] + pl.sz[1] + pl.sz[2] + pl.sz[3] + pl.sz[4];
+    char* buf[5];
+    return dry_run([&](Carver& c) { carve_net(c, plan(w, n, h, wd), buf); });
 }
 
 int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
@@ -539,17 +546,15 @@ int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const 
     HIPT_CHECK_ARG(packed && x && out && workspace && ((uintptr_t)packed % 256) == 0 && ((uintptr_t)workspace % 256) == 0 &&
                        ((uintptr_t)out % 16) == 0,
                    "resnet: null pointer, or packed / workspace not 256-byte aligned");
-    const NetPlan pl = plan(w, n, h, wd);
-    const size_t need = pl.sz[0] + pl.sz[1] + pl.sz[2] + pl.sz[3] + pl.sz[4];
-    if (ws_bytes < need) {
-        hipt_set_error("resnet: workspace %zu B too small (need %zu)", ws_bytes, need);
-        return HIPT_E_WORKSPACE;
-    }
     const int dt = w->dtype;
     hipStream_t st = (hipStream_t)stream;
     char* buf[5];
-    buf[0] = (char*)workspace;
-    for (int i = 1; i < 5; ++i) buf[i] = buf[i - 1] + pl.sz[i - 1];
+    Carver ws(workspace, ws_bytes);
+    carve_net(ws, plan(w, n, h, wd), buf);
+    if ((rc = check_workspace(ws, "resnet_forward")) != HIPT_OK) return rc;
+    ConvImg img[RN_MAX_CONVS];
+    Carver pk((void*)packed);
+    carve_packed(pk, nc, count, dt, img);
     char *A = buf[0], *B = buf[1], *T1 = buf[2], *T2 = buf[3], *D = buf[4];
 
     // input -> NHWC T in T1
@@ -562,17 +567,10 @@ int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const 
                              : launch_input<float>(x, input_kind, npx, (int64_t)h * wd, nm, (float*)T1, st);
         if (rc != HIPT_OK) return rc;
     }
-    // byte offset of every conv's packed weight (its fp32 bias follows it)
-    size_t off[RN_MAX_CONVS], o = 0;
-    for (int i = 0; i < count; ++i) {
-        off[i] = o;
-        o += conv_w_bytes(nc[i].cout, nc[i].cin, nc[i].k, dt) + conv_b_bytes(nc[i].cout);
-    }
     auto conv = [&](int i, const void* in, int hh, int ww, const void* resid, int relu, void* o, int* oh, int* ow) -> int {
         const NetConv& c = nc[i];
-        const char* pw = (const char*)packed + off[i];
         ConvArgs a = {};
-        a.x = in, a.wt = pw, a.bias = (const float*)(pw + conv_w_bytes(c.cout, c.cin, c.k, dt)), a.resid = resid, a.out = o;
+        a.x = in, a.wt = img[i].w, a.bias = img[i].bias, a.resid = resid, a.out = o;
         a.n = n, a.h = hh, a.w = ww, a.cin = c.cin, a.cout = c.cout, a.kh = c.k, a.kw = c.k, a.stride = c.stride, a.pad = c.pad;
         a.relu = relu;
         const int r = run_conv(a, dt, st);

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "launch.h"
+#include "workspace.h"
 
 namespace {
 
@@ -376,14 +377,29 @@ __global__ __launch_bounds__(256) void upd_sum_kernel(const double* __restrict__
     if (threadIdx.x == 0) *out = s;
 }
 
-size_t al256s(size_t n) { return (n + 255) & ~(size_t)255; }
+// the candidate lists of the S x G (query, segment) pairs, k entries each: keys | point ids
+struct KnnWs { u64* cand_d; int* cand_i; };
+void carve_knn(Carver& c, const KnnGeo& g, KnnWs& ws) {
+    const size_t n = (size_t)g.S * g.G * g.k;
+    ws.cand_d = c.take<u64>(n);
+    ws.cand_i = c.take<int>(n);
+}
+
+// bits and cnt are taken one after the other on purpose: AVERAGE mode zeroes the two with ONE memset of 2 * al256(4 N) bytes
+// starting at bits (hipt_sampling_update), so nothing may ever be carved between them.
+void carve_update(Carver& c, int N, UpdWs& ws) {
+    ws.bits = c.take<unsigned>(N);
+    ws.cnt = c.take<int>(N);
+    ws.first = c.take<int>(N);
+    ws.newd = c.take<double>(N);
+    ws.partial = c.take<double>(256);
+}
 
 }  // namespace
 
 extern "C" size_t hipt_knn_workspace_bytes(int N, int S, int k) {
     if (N <= 0 || S <= 0 || k <= 0 || k > KNN_MAX_K || k > N) return 0;
-    const KnnGeo g = knn_geo(N, S, k);
-    return al256s((size_t)S * g.G * k * 8) + al256s((size_t)S * g.G * k * 4);
+    return dry_run([&](Carver& c) { KnnWs ws; carve_knn(c, knn_geo(N, S, k), ws); });
 }
 
 extern "C" int hipt_knn(const void* X, int kind, int N, int D, const int64_t* q_idx, int S, int k, int64_t* ids, void* dist,
@@ -398,27 +414,25 @@ extern "C" int hipt_knn(const void* X, int kind, int N, int D, const int64_t* q_
     }
     if (kind == HIPT_KNN_SPATIAL) HIPT_CHECK_ARG(D == 2 && ((uintptr_t)X % 8) == 0, "knn: spatial points are int32 [N, 2], 8-byte aligned (D=%d)", D);
     else HIPT_CHECK_ARG(D > 0 && D <= 2048 && D % 4 == 0 && ((uintptr_t)X % 16) == 0, "knn: textural D=%d must be a multiple of 4 up to 2048, X 16-byte aligned", D);
-    if (ws_bytes < hipt_knn_workspace_bytes(N, S, k) || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("knn: workspace %zu B too small / unaligned (need %zu)", ws_bytes, hipt_knn_workspace_bytes(N, S, k));
-        return HIPT_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
     const KnnGeo g = knn_geo(N, S, k);
-    u64* cand_d = (u64*)workspace;
-    int* cand_i = (int*)((char*)workspace + al256s((size_t)S * g.G * k * 8));
+    Carver c(workspace, ws_bytes);
+    KnnWs ws;
+    carve_knn(c, g, ws);
+    if (int rc = check_workspace(c, "knn")) return rc;
+    hipStream_t st = (hipStream_t)stream;
     // (one opt-in for both kernels, the larger of their two needs: the attribute is a ceiling, each launch asks for its own size)
     static DeviceSetup setup;
     const size_t lds_max = spatial_lds(KNN_MAX_K) > textural_lds(KNN_MAX_K) ? spatial_lds(KNN_MAX_K) : textural_lds(KNN_MAX_K);
     if (int rc = setup({(const void*)knn_spatial_kernel, (const void*)knn_textural_kernel}, (int)lds_max, "knn kernels")) return rc;
     const dim3 grid((unsigned)g.G, (unsigned)((S + KNN_TQ - 1) / KNN_TQ));
     if (kind == HIPT_KNN_SPATIAL) {
-        hipLaunchKernelGGL(knn_spatial_kernel, grid, dim3(256), spatial_lds(k), st, (const int*)X, q_idx, g, cand_d, cand_i);
+        hipLaunchKernelGGL(knn_spatial_kernel, grid, dim3(256), spatial_lds(k), st, (const int*)X, q_idx, g, ws.cand_d, ws.cand_i);
         HIPT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(knn_merge_kernel<true>, dim3(S), dim3(64), 0, st, (const u64*)cand_d, (const int*)cand_i, g, ids, dist);
+        hipLaunchKernelGGL(knn_merge_kernel<true>, dim3(S), dim3(64), 0, st, (const u64*)ws.cand_d, (const int*)ws.cand_i, g, ids, dist);
     } else {
-        hipLaunchKernelGGL(knn_textural_kernel, grid, dim3(256), textural_lds(k), st, (const float*)X, q_idx, D, g, cand_d, cand_i);
+        hipLaunchKernelGGL(knn_textural_kernel, grid, dim3(256), textural_lds(k), st, (const float*)X, q_idx, D, g, ws.cand_d, ws.cand_i);
         HIPT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(knn_merge_kernel<false>, dim3(S), dim3(64), 0, st, (const u64*)cand_d, (const int*)cand_i, g, ids, dist);
+        hipLaunchKernelGGL(knn_merge_kernel<false>, dim3(S), dim3(64), 0, st, (const u64*)ws.cand_d, (const int*)ws.cand_i, g, ids, dist);
     }
     HIPT_CHECK_LAUNCH();
     return HIPT_OK;
@@ -426,7 +440,7 @@ extern "C" int hipt_knn(const void* X, int kind, int N, int D, const int64_t* q_
 
 extern "C" size_t hipt_sampling_update_workspace_bytes(int N) {
     if (N <= 0) return 0;
-    return 3 * al256s((size_t)N * 4) + al256s((size_t)N * 8) + 256 * 8;
+    return dry_run([&](Carver& c) { UpdWs ws; carve_update(c, N, ws); });
 }
 
 extern "C" int hipt_sampling_update(double* weights, int N, const float* scores, int S, const int64_t* ids, int k_stride, int neighbors,
@@ -439,21 +453,13 @@ extern "C" int hipt_sampling_update(double* weights, int N, const float* scores,
     HIPT_CHECK_ARG(S * neighbors == 0 || (scores && ids), "sampling_update: scores / ids missing");
     HIPT_CHECK_ARG(T >= 0 && (T == 0 || all_sampled), "sampling_update: all_sampled missing");
     HIPT_CHECK_ARG(power > 0.0, "sampling_update: power must be positive");
-    if (ws_bytes < hipt_sampling_update_workspace_bytes(N) || ((uintptr_t)workspace & 255)) {
-        hipt_set_error("sampling_update: workspace %zu B too small / unaligned (need %zu)", ws_bytes, hipt_sampling_update_workspace_bytes(N));
-        return HIPT_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n4 = al256s((size_t)N * 4);
+    Carver c(workspace, ws_bytes);
     UpdWs ws;
-    char* p = (char*)workspace;
-    ws.bits = (unsigned*)p;
-    ws.cnt = (int*)(p + n4);
-    ws.first = (int*)(p + 2 * n4);
-    ws.newd = (double*)(p + 3 * n4);
-    ws.partial = (double*)(p + 3 * n4 + al256s((size_t)N * 8));
+    carve_update(c, N, ws);
+    if (int rc = check_workspace(c, "sampling_update")) return rc;
+    hipStream_t st = (hipStream_t)stream;
     const bool avg = mode == HIPT_SAMPLING_AVERAGE;
-    if (hipMemsetAsync(ws.bits, 0, avg ? 2 * n4 : (size_t)N * 4, st) != hipSuccess ||
+    if (hipMemsetAsync(ws.bits, 0, avg ? 2 * al256((size_t)N * 4) : (size_t)N * 4, st) != hipSuccess ||
         (avg && (hipMemsetAsync(ws.first, 0x7f, (size_t)N * 4, st) != hipSuccess || hipMemsetAsync(ws.newd, 0, (size_t)N * 8, st) != hipSuccess))) {
         hipt_set_error("sampling_update: hipMemsetAsync failed");
         return HIPT_E_LAUNCH;

@@ -106,7 +106,8 @@ def test_train_step_with_dropout_masks_and_bag_gradient():
 
 @pytest.mark.parametrize("size,base,n,ncls,multi,k", [((1024, 512, 256), 1024, 300, 2, False, 8),   # CLAM's own default widths
                                                         ((192, 128, 64), 192, 5000, 2, False, 8),      # > 4096 rows: split weight reduction
-                                                        ((384, 128, 64), 384, 33, 4, True, 4)])        # 4 branches
+                                                        ((384, 128, 64), 384, 33, 4, True, 4),         # 4 branches
+                                                        ((32, 16, 8), 32, 37, 2, True, 4)])            # duv [37, 16] fp32 ends off the 256-byte grid
 def test_train_step_vs_oracle_other_shapes(size, base, n, ncls, multi, k):
     m = make(size, base, ncls, multi, k, True)
     h = synth.hash_uniform_torch((n, size[0]), 55, device=DEV)
