@@ -780,6 +780,40 @@ int hipt_vit_mlp_unit(const hipt_vit_weights* w, int block, float* x_img, const 
     return HIPT_OK;
 }
 
+int hipt_vit_cls_block_unit(const hipt_vit_weights* w, const void* xn_img, const float* x_img, int nseq, float* xc_out, void* att_out, void* workspace,
+                            size_t ws_bytes, void* stream) {
+    int rc = check_vit(w);
+    if (rc) return rc;
+    HIPT_CHECK_ARG(xn_img && x_img && xc_out && nseq > 0, "vit_cls_block_unit: null/empty argument");
+    const int D = w->dim;
+    const int64_t M = (int64_t)nseq * w->ntok;
+    // the route of a whole forward of this size whose embedding wrote images (vit256_range_impl), in the state run_blocks leaves it in
+    // behind the last chained block: x an fp32 image, s.att LayerNorm-1 of the last block as a bf16 image
+    VitRoute r = vit_route(w, nseq, 0, w->depth, false, RT_CLS_ONLY | RT_PX_EMBED);
+    if (!hipt_qkv_attn_supported(w->dtype, D, w->heads, w->ntok) || M % 16 != 0 || !r.prune || !r.chain || !r.img) {
+        hipt_set_error("vit_cls_block_unit: bf16, D = 384, 6 heads, 257 tokens, nseq * 257 %% 16 == 0 and a forward that prunes its last block "
+                       "on activation images only");
+        return HIPT_E_UNSUPPORTED;
+    }
+    r.have_xn = r.x_img = true;
+    Carver c(workspace, workspace ? ws_bytes : 0);  // (a null workspace is refused like a short one)
+    BlockScratch s = carve_vit4k(c, w, nseq, false).s;  // hipt_vit_workspace_bytes' layout
+    if ((rc = check_workspace(c, "vit_cls_block_unit"))) return rc;
+    HIPT_CHECK_ARG(s.fits_cls_xn, "vit_cls_block_unit: hidden %d leaves no room for the [CLS] rows in the block scratch", w->hidden);
+    hipStream_t st = S(stream);
+    // The fused routes only read the LayerNorm-1 image: they run on the caller's.  The two-kernel route leaves its attention rows in
+    // s.att, so it runs on a copy in the workspace slot.  x is read by the [CLS] residual gather alone.
+    if (block_route(r, w->blocks[w->depth - 1], false).fuse)
+        s.att = const_cast<void*>(xn_img);
+    else if (hipMemcpyAsync(s.att, xn_img, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return HIPT_E_LAUNCH;
+    const void* rows = s.att == xn_img ? s.qkv : s.att;  // where run_last_block_cls leaves att_rows
+    if ((rc = run_last_block_cls(w, const_cast<float*>(x_img), nseq, s, r, st))) return rc;
+    if (hipMemcpyAsync(xc_out, s.xc, (size_t)nseq * D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return HIPT_E_LAUNCH;
+    if (att_out && hipMemcpyAsync(att_out, rows, (size_t)nseq * D * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) return HIPT_E_LAUNCH;
+    return HIPT_OK;
+}
+
 // Format of the fused MLP's weight image: 2 = csrc/mlp16.hip (16x16x32 MFMAs), 0 = this shape has no packed form.  (Format 1 was a
 // 32x32x16 form, tools/experiments/mlp32_r4.hip, since retired -- DESIGN.md; an image packed as format 1 is refused by blocks_chain
 // and its model falls back to the generic kernels.)

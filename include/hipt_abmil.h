@@ -35,7 +35,7 @@ extern "C" {
  * hipt_vit_packed_bytes, never compute the size) and packing it reads blocks[i].proj_w, which must be set first;
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
- * _render) were added later under the same number: additive, nothing existing changed. */
+ * _render) and hipt_vit_cls_block_unit were added later under the same number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -232,6 +232,19 @@ int hipt_vit_attention_unit(const hipt_vit_weights* w, int block, const void* xn
  * (bf16, D = 384, hidden % 128 == 0), nseq * 257 a multiple of 16; workspace >= 256 bytes (the kernel's tile queue). */
 int hipt_vit_mlp_unit(const hipt_vit_weights* w, int block, float* x_img, const void* att_img, int nseq, void* xn_out_img,
                       void* workspace, size_t ws_bytes, void* stream);
+
+/* The [CLS]-pruned LAST block of a bf16 ViT-256 forward as that forward runs it (the launch sequence behind its chained blocks:
+ * [CLS]-row gather, Q rows, u = q Wu^T, the pooling kernel, o = z Wo^T + bv, proj rows, the fused MLP on nseq rows), exposed for the
+ * parity tests.  xn_img: LayerNorm-1 of the last block's input as a bf16 activation image [nseq * 257, 384]; x_img: the fp32 residual
+ * stream as an activation image (only its [CLS] rows are read).  Neither is written.  xc_out [nseq, 384] fp32, row-major: the final
+ * residual rows of the [CLS] tokens, before the final norm (hipt_vit_head with ntok = 1 strides finishes them).  att_out: NULL, or
+ * [nseq, 384] bf16 row-major: the attention rows before proj.  The route is the forward's own: HIPT_NO_CLS_ABSORB=1 takes the fused
+ * kernel's [CLS]-only form, HIPT_NO_FUSED_ATTN=1 the K | V GEMM + the one-query attention kernel (on a copy of xn_img in the
+ * workspace).  HIPT_E_UNSUPPORTED outside bf16 / D = 384 / 6 heads / 257 tokens / nseq * 257 % 16 == 0, or when a forward of this
+ * size would not prune its last block on activation images (HIPT_NO_PRUNE, HIPT_NO_IMG, HIPT_GENERIC).
+ * workspace >= hipt_vit_workspace_bytes(w, nseq), 256-byte aligned. */
+int hipt_vit_cls_block_unit(const hipt_vit_weights* w, const void* xn_img, const float* x_img, int nseq, float* xc_out, void* att_out,
+                            void* workspace, size_t ws_bytes, void* stream);
 
 /* [CLS] row of the last block's attention map: probs_cls[nseq, heads, ntok] fp32 =
  * get_last_selfattention(x)[:, :, 0, :] (vision_transformer.py:255-262 as consumed by the heat-maps,
