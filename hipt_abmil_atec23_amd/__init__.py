@@ -22,6 +22,9 @@ _LAZY = {
     "VisionTransformer4K": ("vision_transformer4k", "VisionTransformer4K"), "vit4k_xs": ("vision_transformer4k", "vit4k_xs"),
     "ResNet_Baseline": ("resnet_custom", "ResNet_Baseline"), "Bottleneck_Baseline": ("resnet_custom", "Bottleneck_Baseline"),
     "resnet50_baseline": ("resnet_custom", "resnet50_baseline"),
+    # HistoResNet-18 (the stub resnet_custom.resnet18_baseline still raises: DESIGN.md 15)
+    "ResNet18_Baseline": ("resnet18", "ResNet18_Baseline"), "BasicBlock_Baseline": ("resnet18", "BasicBlock_Baseline"),
+    "resnet18_baseline": ("resnet18", "resnet18_baseline"),
     "install": ("dropin", "install"), "build_native": ("_native", "build"),
     "FeatureWriter": ("feature_store", "FeatureWriter"), "extract_slide": ("feature_store", "extract_slide"),
     "load_bag": ("feature_store", "load_bag"), "load_coords": ("feature_store", "load_coords"),

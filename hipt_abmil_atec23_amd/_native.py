@@ -72,6 +72,11 @@ class ResnetWeights(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class ResnetBasicWeights(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("layers", C.c_int32 * 4), ("convs", C.POINTER(ConvBN)), ("n_convs", C.c_int32),
+                ("tile_rows", C.c_int32)]
+
+
 RESNET_IN_F32, RESNET_IN_U8, RESNET_IN_U8_HWC = 0, 1, 2
 KNN_SPATIAL, KNN_TEXTURAL = 0, 1
 SAMPLING_MAX, SAMPLING_NEWEST, SAMPLING_AVERAGE = 0, 1, 2
@@ -81,7 +86,7 @@ HEATMAP_TILE_W, HEATMAP_TILE_H, HEATMAP_MAX_DIM, HEATMAP_LUT_ENTRIES = 32, 8, 1 
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
-_CB, _RW = C.POINTER(ConvBN), C.POINTER(ResnetWeights)
+_CB, _RW, _RBW = C.POINTER(ConvBN), C.POINTER(ResnetWeights), C.POINTER(ResnetBasicWeights)
 _i, _i64, _p, _sz, _f = C.c_int, C.c_int64, C.c_void_p, C.c_size_t, C.c_float
 
 # name -> (restype, argtypes); mirrors include/hipt_abmil.h one to one
@@ -146,6 +151,12 @@ SIGNATURES = {
     "hipt_conv_bn_packed_bytes": (_sz, [_CB, _i]),
     "hipt_conv_bn_pack": (_i, [_CB, _i, _p, _p, _p]),
     "hipt_conv2d": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
+    "hipt_conv2d_ex": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
+    "hipt_conv_tile_rows": (_i, [_i64, _i]),
+    "hipt_resnet_basic_packed_bytes": (_sz, [_RBW]),
+    "hipt_resnet_basic_pack_weights": (_i, [_RBW, _p, _p]),
+    "hipt_resnet_basic_workspace_bytes": (_sz, [_RBW, _i, _i, _i]),
+    "hipt_resnet_basic_forward": (_i, [_RBW, _p, _p, _i, _p, _i, _i, _i, _p, _p, _sz, _p]),
     "hipt_resnet_maxpool": (_i, [_p, _i, _i, _i, _i, _p, _i, _p]),
     "hipt_resnet_avgpool": (_i, [_p, _i, _i, _i, _p, _i, _p]),
     "hipt_knn_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -7,7 +7,8 @@
 // filter tap and is a contiguous 128-byte run of the input pixel's channels (or zeros for a padding tap).  The stem
 // (Cin = 3, K = 147) takes the element-gather form of the same loader, K zero-padded to the slab.
 //
-// Tile: 128 output pixels x BN (128 or 64) output channels per 256-thread workgroup (4 waves as 2(M) x 2(N)).  Operands are
+// Tile: BM (128; 64 on the small maps of the BasicBlock network below) output pixels x BN (128 or 64) output channels per
+// 256-thread workgroup (4 waves as 2(M) x 2(N)).  Operands are
 // staged global -> registers -> LDS (two buffers, one barrier per slab), with the same 16-byte-chunk XOR swizzle as
 // gemm.hip; weights are the MFMA A operand so each lane ends with 4 consecutive output channels of one pixel (8/16-byte
 // stores).  The epilogue is bias, optional residual add, optional ReLU, store.  No split-K and no atomics: every output
@@ -30,12 +31,17 @@ struct ConvArgs {
     int n, h, w, cin, oh, ow, cout, kh, kw, stride, pad, K, kp, M, relu;
 };
 
-template <typename T, int BN, bool GATHER>
+// BM: output pixels per tile, 128 or 64 (the ResNet-18 driver's small maps).  A 64-row tile stages half as many
+// A rows per slab and gives each wave 32 rows instead of 64; the K loop, the swizzle and the column fragments are the same, so one
+// output element is accumulated by the same MFMA sequence under either height.
+template <typename T, int BN, bool GATHER, int BM = RN_BM>
 __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
     constexpr int EPC = Tr<T>::EPC, KB = Tr<T>::KB;
+    constexpr int AQ = BM / 32;       // pixel-row chunks per thread per slab
+    constexpr int MFR = BM / 32;      // 16-row fragments per wave (a wave owns BM / 2 rows)
     constexpr int WQ = BN / 32;       // weight chunks per thread per slab
     constexpr int NFR = BN / 32;      // 16-column fragments per wave (a wave owns BN / 2 columns)
-    constexpr int A_BYTES = RN_BM * 128, STAGE = A_BYTES + BN * 128;
+    constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + BN * 128;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -44,16 +50,16 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
     const int li = lane & 15, g = lane >> 4;
     const int tiles_n = p.cout / BN;
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (tile / tiles_n) * RN_BM, n0 = (tile % tiles_n) * BN;
+    const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
 
     // ---- staging slots: row (tid >> 3) + 32 q, 16-byte chunk (tid & 7) ----
     const int c = tid & 7;
     const int ohw = p.oh * p.ow;
-    int iy0[4], ix0[4];
-    int64_t pix0[4];  // element offset of image b's pixel (0, 0)
-    bool mok[4];
+    int iy0[AQ], ix0[AQ];
+    int64_t pix0[AQ];  // element offset of image b's pixel (0, 0)
+    bool mok[AQ];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < AQ; ++q) {
         const int m = m0 + (tid >> 3) + 32 * q;
         mok[q] = m < p.M;
         const int mm = mok[q] ? m : 0;
@@ -67,12 +73,12 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
 #pragma unroll
     for (int q = 0; q < WQ; ++q) wrow[q] = (const T*)p.wt + (int64_t)(n0 + (tid >> 3) + 32 * q) * p.kp + c * EPC;
 
-    u32x4 ra[4], rw[WQ];
+    u32x4 ra[AQ], rw[WQ];
     auto load = [&](int kt) {
         const int k0 = kt * KB;
         if constexpr (GATHER) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < AQ; ++q) {
                 T v[EPC];
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
@@ -87,7 +93,7 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
         } else {
             const int tap = k0 / p.cin, ci0 = k0 - tap * p.cin, ky = tap / p.kw, kx = tap - ky * p.kw;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < AQ; ++q) {
                 const int iy = iy0[q] + ky, ix = ix0[q] + kx;
                 const bool ok = mok[q] && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
                 ra[q] = ok ? *(const u32x4*)(X + pix0[q] + ((int64_t)iy * p.w + ix) * p.cin + ci0 + c * EPC) : u32x4{0u, 0u, 0u, 0u};
@@ -99,7 +105,7 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
     auto store = [&](int s) {
         char* sa = smem + s * STAGE;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < AQ; ++q) {
             const int r = (tid >> 3) + 32 * q;
             *(u32x4*)(sa + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = ra[q];
         }
@@ -114,9 +120,9 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) foff[ks] = li * 128 + (((g + 4 * ks) ^ ((li >> 1) & 7)) << 4);
 
-    f32x4 acc[4][NFR];
+    f32x4 acc[MFR][NFR];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < MFR; ++i)
 #pragma unroll
         for (int j = 0; j < NFR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
@@ -126,17 +132,17 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + 1 < nk) load(kt + 1);
-        const char* sa = smem + (kt & 1) * STAGE + wm * 64 * 128;
+        const char* sa = smem + (kt & 1) * STAGE + wm * (BM / 2) * 128;
         const char* sw = smem + (kt & 1) * STAGE + A_BYTES + wn * (BN / 2) * 128;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            u32x4 wf[NFR], af[4];
+            u32x4 wf[NFR], af[MFR];
 #pragma unroll
             for (int j = 0; j < NFR; ++j) wf[j] = *(const u32x4*)(sw + j * 16 * 128 + foff[ks]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = *(const u32x4*)(sa + i * 16 * 128 + foff[ks]);
+            for (int i = 0; i < MFR; ++i) af[i] = *(const u32x4*)(sa + i * 16 * 128 + foff[ks]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < MFR; ++i)
 #pragma unroll
                 for (int j = 0; j < NFR; ++j) Tr<T>::mma16(acc[i][j], wf[j], af[i]);
         }
@@ -144,12 +150,12 @@ __global__ __launch_bounds__(RN_THREADS) void rn_conv_kernel(const ConvArgs p) {
         __syncthreads();
     }
 
-    // ---- epilogue: lane holds C[pixel m0 + wm*64 + 16 i + li][channel n0 + wn*BN/2 + 16 j + 4 g + 0..3] ----
+    // ---- epilogue: lane holds C[pixel m0 + wm*BM/2 + 16 i + li][channel n0 + wn*BN/2 + 16 j + 4 g + 0..3] ----
     const T* R = (const T*)p.resid;
     T* O = (T*)p.out;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + wm * 64 + i * 16 + li;
+    for (int i = 0; i < MFR; ++i) {
+        const int m = m0 + wm * (BM / 2) + i * 16 + li;
         if (m >= p.M) continue;
 #pragma unroll
         for (int j = 0; j < NFR; ++j) {
@@ -289,20 +295,32 @@ int conv_kp(int cin, int kh, int kw, int dtype) {
     return (K + kb - 1) / kb * kb;
 }
 
-template <typename T, int BN>
+template <typename T, int BN, int BM>
 int launch_conv_bn(const ConvArgs& a, hipStream_t st) {
-    const int tiles = ((a.M + RN_BM - 1) / RN_BM) * (a.cout / BN);
+    const int tiles = ((a.M + BM - 1) / BM) * (a.cout / BN);
     if (a.cin % Tr<T>::KB == 0)
-        hipLaunchKernelGGL((rn_conv_kernel<T, BN, false>), dim3(tiles), dim3(RN_THREADS), 0, st, a);
+        hipLaunchKernelGGL((rn_conv_kernel<T, BN, false, BM>), dim3(tiles), dim3(RN_THREADS), 0, st, a);
     else
-        hipLaunchKernelGGL((rn_conv_kernel<T, BN, true>), dim3(tiles), dim3(RN_THREADS), 0, st, a);
+        hipLaunchKernelGGL((rn_conv_kernel<T, BN, true, BM>), dim3(tiles), dim3(RN_THREADS), 0, st, a);
     HIPT_CHECK_LAUNCH();
     return HIPT_OK;
 }
 
-template <typename T>
+template <typename T, int BM>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
-    return a.cout % 128 == 0 ? launch_conv_bn<T, 128>(a, st) : launch_conv_bn<T, 64>(a, st);
+    return a.cout % 128 == 0 ? launch_conv_bn<T, 128, BM>(a, st) : launch_conv_bn<T, 64, BM>(a, st);
+}
+
+// The tile height of the ResNet-18 driver and of hipt_conv2d_ex(tile_rows = 0): a pure function of (M, cout), so a conv's launch
+// shape never depends on anything but its own shape.  64 rows where 128-row tiles leave compute units idle (fewer workgroups
+// than the MI355X's 256 CUs) and halving the tile adds at least one workgroup; 128 rows everywhere else.
+// The 256 is a constant of this gfx950-only library, not a device query, and the rule was measured on 256 x 256 patches at
+// batch 32 and 256 only: another CU count or patch size wants its own A/B.
+constexpr int RN_CUS = 256;
+int tile_rows_rule(int64_t M, int cout) {
+    const int64_t tn = cout / (cout % 128 == 0 ? 128 : 64);
+    const int64_t t128 = (M + 127) / 128, t64 = (M + 63) / 64;
+    return (t128 * tn < RN_CUS && t64 > t128) ? 64 : 128;
 }
 
 // shape checks of one conv; fills the derived fields
@@ -328,10 +346,13 @@ int conv_setup(ConvArgs& a, int dtype) {
     return HIPT_OK;
 }
 
-int run_conv(ConvArgs& a, int dtype, hipStream_t st) {
+// rows: RN_BM (every ResNet-50 launch), 64, or 0 for tile_rows_rule
+int run_conv(ConvArgs& a, int dtype, hipStream_t st, int rows = RN_BM) {
     const int rc = conv_setup(a, dtype);
     if (rc != HIPT_OK) return rc;
-    return dtype == HIPT_BF16 ? launch_conv<bf16_t>(a, st) : launch_conv<float>(a, st);
+    if (rows == 0) rows = tile_rows_rule(a.M, a.cout);
+    if (rows == 64) return dtype == HIPT_BF16 ? launch_conv<bf16_t, 64>(a, st) : launch_conv<float, 64>(a, st);
+    return dtype == HIPT_BF16 ? launch_conv<bf16_t, RN_BM>(a, st) : launch_conv<float, RN_BM>(a, st);
 }
 
 int run_maxpool(const void* x, int n, int h, int w, int C, void* out, int dtype, hipStream_t st) {
@@ -381,21 +402,26 @@ int net_convs(const hipt_resnet_weights* w, NetConv* out) {
     return nc;
 }
 
-int check_weights(const hipt_resnet_weights* w, NetConv* nc, int* count) {
-    HIPT_CHECK_ARG(w != nullptr, "resnet: null weights");
-    HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "resnet: bad dtype %d", w->dtype);
-    for (int L = 0; L < 3; ++L)
-        HIPT_CHECK_ARG(w->layers[L] >= 1 && w->layers[L] <= 64, "resnet: layers[%d]=%d outside [1, 64]", L, w->layers[L]);
-    *count = net_convs(w, nc);
-    HIPT_CHECK_ARG(w->n_convs == *count && w->convs != nullptr, "resnet: %d convs given, the layer counts need %d", w->n_convs, *count);
-    for (int i = 0; i < *count; ++i) {
-        const hipt_conv_bn& c = w->convs[i];
+// the caller's conv records against the table the layer counts imply
+int check_convs(const hipt_conv_bn* convs, int n_convs, const NetConv* nc, int count) {
+    HIPT_CHECK_ARG(n_convs == count && convs != nullptr, "resnet: %d convs given, the layer counts need %d", n_convs, count);
+    for (int i = 0; i < count; ++i) {
+        const hipt_conv_bn& c = convs[i];
         HIPT_CHECK_ARG(c.cin == nc[i].cin && c.cout == nc[i].cout && c.kh == nc[i].k && c.kw == nc[i].k,
                        "resnet: conv %d is %dx%dx%dx%d, expected %dx%dx%dx%d", i, c.cout, c.cin, c.kh, c.kw, nc[i].cout, nc[i].cin,
                        nc[i].k, nc[i].k);
         HIPT_CHECK_ARG(c.weight && c.bn_weight && c.bn_bias && c.bn_mean && c.bn_var, "resnet: conv %d has a null tensor", i);
     }
     return HIPT_OK;
+}
+
+int check_weights(const hipt_resnet_weights* w, NetConv* nc, int* count) {
+    HIPT_CHECK_ARG(w != nullptr, "resnet: null weights");
+    HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "resnet: bad dtype %d", w->dtype);
+    for (int L = 0; L < 3; ++L)
+        HIPT_CHECK_ARG(w->layers[L] >= 1 && w->layers[L] <= 64, "resnet: layers[%d]=%d outside [1, 64]", L, w->layers[L]);
+    *count = net_convs(w, nc);
+    return check_convs(w->convs, w->n_convs, nc, *count);
 }
 
 // the packed weight image: per conv, in the order of hipt_resnet_weights.convs, its packed weight | its folded fp32 bias
@@ -458,6 +484,90 @@ int check_shape(int n, int h, int w) {
     return HIPT_OK;
 }
 
+// ---- the BasicBlock network (torchvision's ResNet-18 / -34 family: hipt_resnet_basic_weights) -----------------------------
+// conv order: stem, then per block conv1 (3x3, carries the stride), conv2 (3x3) and, in block 0 of layers 2..4, downsample (1x1).
+// layers[]: blocks of layer1..layer4; trailing zeros leave the later layers out (the output is the last built layer's width).
+int basic_layers(const hipt_resnet_basic_weights* w) {
+    int L = 0;
+    while (L < 4 && w->layers[L] > 0) ++L;
+    return L;
+}
+
+int basic_convs(const hipt_resnet_basic_weights* w, NetConv* out) {
+    int nc = 0, inplanes = 64;
+    out[nc++] = {3, 64, 7, 2, 3};
+    for (int L = 0, nl = basic_layers(w); L < nl; ++L) {
+        const int planes = 64 << L;
+        for (int b = 0; b < w->layers[L]; ++b) {
+            const int s = (L && b == 0) ? 2 : 1;
+            out[nc++] = {inplanes, planes, 3, s, 1};
+            out[nc++] = {planes, planes, 3, 1, 1};
+            if (s != 1 || inplanes != planes) out[nc++] = {inplanes, planes, 1, s, 0};
+            inplanes = planes;
+        }
+    }
+    return nc;
+}
+
+int check_basic_weights(const hipt_resnet_basic_weights* w, NetConv* nc, int* count) {
+    HIPT_CHECK_ARG(w != nullptr, "resnet_basic: null weights");
+    HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "resnet_basic: bad dtype %d", w->dtype);
+    HIPT_CHECK_ARG(w->tile_rows == 0 || w->tile_rows == RN_BM, "resnet_basic: tile_rows=%d is neither 0 (the rule) nor 128", w->tile_rows);
+    const int nl = basic_layers(w);
+    HIPT_CHECK_ARG(nl >= 1, "resnet_basic: layers[0]=%d, at least one block is needed", w->layers[0]);
+    for (int L = 0; L < 4; ++L)
+        HIPT_CHECK_ARG(L < nl ? w->layers[L] <= 64 : w->layers[L] == 0, "resnet_basic: layers[%d]=%d (1..64 blocks, then zeros only)", L,
+                       w->layers[L]);
+    *count = basic_convs(w, nc);
+    return check_convs(w->convs, w->n_convs, nc, *count);
+}
+
+// workspace: four NHWC activation buffers (A, B: block input / output, T: block interior, D: downsample), each as large as the
+// largest tensor it ever holds; T also holds the NHWC copy of the input.
+struct BasicPlan {
+    size_t sz[4];
+};
+BasicPlan basic_plan(const hipt_resnet_basic_weights* w, int n, int h, int wd) {
+    BasicPlan pl = {};
+    const size_t es = esize(w->dtype);
+    auto upd = [&](int i, size_t elems) { pl.sz[i] = pl.sz[i] > elems * es ? pl.sz[i] : elems * es; };
+    const size_t N = (size_t)n;
+    upd(2, N * h * wd * 3);
+    int hh = conv_out(h, 7, 2, 3), ww = conv_out(wd, 7, 2, 3);
+    upd(0, N * hh * ww * 64);
+    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
+    upd(1, N * hh * ww * 64);
+    for (int L = 0, nl = basic_layers(w); L < nl; ++L) {
+        const size_t planes = (size_t)64 << L;
+        for (int b = 0; b < w->layers[L]; ++b) {
+            const int s = (L && b == 0) ? 2 : 1;
+            hh = conv_out(hh, 3, s, 1), ww = conv_out(ww, 3, s, 1);
+            for (int i = 0; i < 3; ++i) upd(i, N * hh * ww * planes);
+            if (s != 1) upd(3, N * hh * ww * planes);
+        }
+    }
+    upd(3, 1);  // layer1 alone has no downsample: the carve stays non-empty
+    for (auto& s : pl.sz) s = al256(s);
+    return pl;
+}
+
+void carve_basic(Carver& c, const BasicPlan& pl, char* (&buf)[4]) {
+    for (int i = 0; i < 4; ++i) buf[i] = (char*)c.take(pl.sz[i]);
+}
+
+int check_basic_shape(int n, int h, int w) {
+    HIPT_CHECK_ARG(n >= 1 && h > 0 && w > 0, "resnet_basic: empty input n=%d h=%d w=%d", n, h, w);
+    if (h % 32 || w % 32) {
+        hipt_set_error("resnet_basic: %d x %d input outside the envelope (height and width multiples of 32, at least 32)", h, w);
+        return HIPT_E_UNSUPPORTED;
+    }
+    if ((int64_t)n * (h / 2) * (w / 2) >= ((int64_t)1 << 30)) {
+        hipt_set_error("resnet_basic: batch of %d images of %d x %d too large for one call", n, h, w);
+        return HIPT_E_UNSUPPORTED;
+    }
+    return HIPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -489,6 +599,19 @@ int hipt_conv2d(const void* x, int n, int h, int w, int cin, const void* w_packe
     a.x = x, a.wt = w_packed, a.bias = bias, a.resid = resid, a.out = out;
     a.n = n, a.h = h, a.w = w, a.cin = cin, a.cout = cout, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.relu = relu ? 1 : 0;
     return run_conv(a, dtype, (hipStream_t)stream);
+}
+
+int hipt_conv_tile_rows(int64_t m, int cout) {
+    return (m > 0 && cout > 0 && cout % 64 == 0) ? tile_rows_rule(m, cout) : 0;
+}
+
+int hipt_conv2d_ex(const void* x, int n, int h, int w, int cin, const void* w_packed, const float* bias, int cout, int kh, int kw,
+                   int stride, int pad, const void* resid, int relu, void* out, int dtype, int tile_rows, void* stream) {
+    HIPT_CHECK_ARG(tile_rows == 0 || tile_rows == 64 || tile_rows == RN_BM, "conv2d_ex: tile_rows=%d is not 0, 64 or 128", tile_rows);
+    ConvArgs a = {};
+    a.x = x, a.wt = w_packed, a.bias = bias, a.resid = resid, a.out = out;
+    a.n = n, a.h = h, a.w = w, a.cin = cin, a.cout = cout, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.relu = relu ? 1 : 0;
+    return run_conv(a, dtype, (hipStream_t)stream, tile_rows);
 }
 
 int hipt_resnet_maxpool(const void* x, int n, int h, int w, int c, void* out, int dtype, void* stream) {
@@ -595,6 +718,104 @@ int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const 
             if ((rc = conv(ci + 2, T2, h2, w2, ds ? (const void*)D : (const void*)cur, 1, nxt, &h3, &w3)) != HIPT_OK) return rc;
             ci += ds ? 4 : 3;
             C = planes * 4, hh = h3, ww = w3;
+            char* t = cur;
+            cur = nxt, nxt = t;
+        }
+    }
+    return run_avgpool(cur, n, hh * ww, C, out, dt, st);
+}
+
+size_t hipt_resnet_basic_packed_bytes(const hipt_resnet_basic_weights* w) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    if (check_basic_weights(w, nc, &count) != HIPT_OK) return 0;
+    ConvImg img[RN_MAX_CONVS];
+    return dry_run([&](Carver& c) { carve_packed(c, nc, count, w->dtype, img); });
+}
+
+int hipt_resnet_basic_pack_weights(const hipt_resnet_basic_weights* w, void* packed, void* stream) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    const int rc = check_basic_weights(w, nc, &count);
+    if (rc != HIPT_OK) return rc;
+    HIPT_CHECK_ARG(packed && ((uintptr_t)packed % 256) == 0, "resnet_basic_pack_weights: packed image must be 256-byte aligned");
+    ConvImg img[RN_MAX_CONVS];
+    Carver c(packed);
+    carve_packed(c, nc, count, w->dtype, img);
+    for (int i = 0; i < count; ++i)
+        if (int r = hipt_conv_bn_pack(&w->convs[i], w->dtype, (void*)img[i].w, (float*)img[i].bias, stream)) return r;
+    return HIPT_OK;
+}
+
+size_t hipt_resnet_basic_workspace_bytes(const hipt_resnet_basic_weights* w, int n, int h, int wd) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    if (check_basic_weights(w, nc, &count) != HIPT_OK || check_basic_shape(n, h, wd) != HIPT_OK) return 0;  // what the forward refuses
+    char* buf[4];
+    return dry_run([&](Carver& c) { carve_basic(c, basic_plan(w, n, h, wd), buf); });
+}
+
+int hipt_resnet_basic_forward(const hipt_resnet_basic_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
+                              int n, int h, int wd, float* out, void* workspace, size_t ws_bytes, void* stream) {
+    NetConv nc[RN_MAX_CONVS];
+    int count = 0;
+    int rc = check_basic_weights(w, nc, &count);
+    if (rc != HIPT_OK) return rc;
+    rc = check_basic_shape(n, h, wd);
+    if (rc != HIPT_OK) return rc;
+    HIPT_CHECK_ARG(input_kind == HIPT_RESNET_IN_F32 || input_kind == HIPT_RESNET_IN_U8 || input_kind == HIPT_RESNET_IN_U8_HWC,
+                   "resnet_basic: bad input kind %d", input_kind);
+    HIPT_CHECK_ARG(packed && x && out && workspace && ((uintptr_t)packed % 256) == 0 && ((uintptr_t)workspace % 256) == 0 &&
+                       ((uintptr_t)out % 16) == 0,
+                   "resnet_basic: null pointer, or packed / workspace not 256-byte aligned");
+    const int dt = w->dtype;
+    hipStream_t st = (hipStream_t)stream;
+    char* buf[4];
+    Carver ws(workspace, ws_bytes);
+    carve_basic(ws, basic_plan(w, n, h, wd), buf);
+    if ((rc = check_workspace(ws, "resnet_basic_forward")) != HIPT_OK) return rc;
+    ConvImg img[RN_MAX_CONVS];
+    Carver pk((void*)packed);
+    carve_packed(pk, nc, count, dt, img);
+    char *A = buf[0], *B = buf[1], *T = buf[2], *D = buf[3];
+
+    NormArgs nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
+    if (norm)
+        for (int c = 0; c < 3; ++c) nm.mean[c] = norm[c], nm.std[c] = norm[3 + c];
+    {
+        const int64_t npx = (int64_t)n * h * wd;
+        rc = dt == HIPT_BF16 ? launch_input<bf16_t>(x, input_kind, npx, (int64_t)h * wd, nm, (bf16_t*)T, st)
+                             : launch_input<float>(x, input_kind, npx, (int64_t)h * wd, nm, (float*)T, st);
+        if (rc != HIPT_OK) return rc;
+    }
+    // tile height: the rule (0) or 128 rows on every conv, as the caller's struct says; both give the same bits
+    const int rows = w->tile_rows;
+    auto conv = [&](int i, const void* in, int hh, int ww, const void* resid, int relu, void* o, int* oh, int* ow) -> int {
+        const NetConv& c = nc[i];
+        ConvArgs a = {};
+        a.x = in, a.wt = img[i].w, a.bias = img[i].bias, a.resid = resid, a.out = o;
+        a.n = n, a.h = hh, a.w = ww, a.cin = c.cin, a.cout = c.cout, a.kh = c.k, a.kw = c.k, a.stride = c.stride, a.pad = c.pad;
+        a.relu = relu;
+        const int r = run_conv(a, dt, st, rows);
+        *oh = a.oh, *ow = a.ow;
+        return r;
+    };
+    int hh, ww;
+    if ((rc = conv(0, T, h, wd, nullptr, 1, A, &hh, &ww)) != HIPT_OK) return rc;
+    if ((rc = run_maxpool(A, n, hh, ww, 64, B, dt, st)) != HIPT_OK) return rc;
+    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
+    char *cur = B, *nxt = A;
+    int ci = 1, C = 64;
+    for (int L = 0, nl = basic_layers(w); L < nl; ++L) {
+        const int planes = 64 << L;
+        for (int b = 0; b < w->layers[L]; ++b) {
+            const bool ds = (L && b == 0) || C != planes;  // the rule of basic_convs / _make_layer
+            int h1, w1, h2, w2;
+            if ((rc = conv(ci, cur, hh, ww, nullptr, 1, T, &h1, &w1)) != HIPT_OK) return rc;
+            if (ds && (rc = conv(ci + 2, cur, hh, ww, nullptr, 0, D, &h2, &w2)) != HIPT_OK) return rc;
+            if ((rc = conv(ci + 1, T, h1, w1, ds ? (const void*)D : (const void*)cur, 1, nxt, &h2, &w2)) != HIPT_OK) return rc;
+            ci += ds ? 3 : 2;
+            C = planes, hh = h2, ww = w2;
             char* t = cur;
             cur = nxt, nxt = t;
         }

@@ -13,8 +13,9 @@ The reference imports the hot-path classes by module path:
   reference's module imports, the two names are rebound ON it (eval_utils.py takes its plotting helpers from the same module);
   where it does not, a module is registered whose plotting names raise.  ``install(heatmaps=True)`` binds this package's
   ``vis_heatmap`` as ``wsi_core.WholeSlideImage.WholeSlideImage.visHeatmap`` (what create_heatmaps.py draws with) where the
-  reference's ``wsi_core`` imports (it needs openslide and cv2); elsewhere it does nothing.  The alternative is the overlay files
-  under ``shims/``.
+  reference's ``wsi_core`` imports (it needs openslide and cv2); elsewhere it does nothing.  ``install(resnet18=True)`` binds
+  ``models.resnet_custom.resnet18_baseline`` to this package's HistoResNet-18 (``resnet18.resnet18_baseline``).  The alternative is
+  the overlay files under ``shims/``.
 """
 from __future__ import annotations
 
@@ -135,11 +136,62 @@ def _uninstall_heatmaps():
         cls.visHeatmap = prev
 
 
-def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False):
+_RESNET18_MOD, _RESNET18_NAME = "models.resnet_custom", "resnet18_baseline"
+_RESNET18_KEY = _RESNET18_MOD + "." + _RESNET18_NAME
+
+
+def _install_resnet18(verbose: bool) -> bool:
+    """Bind ``resnet18.resnet18_baseline`` as ``models.resnet_custom.resnet18_baseline`` (opt-in).  On the reference's own module
+    the name is rebound; where ``install(resnet=True)`` mapped this package's ``resnet_custom``, whose stub of that name keeps
+    raising, a module with its names and this one function is registered in its place (a snapshot: names added to ``resnet_custom``
+    later do not appear in it).  That second form, and its branch of ``_uninstall_resnet18``, exist only because the stub must keep
+    raising: delete both when the stub returns ``resnet18.resnet18_baseline``.  False, and nothing done, where no
+    ``models.resnet_custom`` imports."""
+    from . import resnet18, resnet_custom
+    _uninstall_resnet18()
+    try:
+        if _RESNET18_MOD not in sys.modules and importlib.util.find_spec(_RESNET18_MOD) is None:
+            return False
+        mod = importlib.import_module(_RESNET18_MOD)
+    except Exception:   # no reference checkout on sys.path, or one of its imports (torchvision) is missing
+        return False
+    if mod is resnet_custom:
+        view = types.ModuleType(_RESNET18_MOD)
+        view.__dict__.update({k: v for k, v in vars(mod).items() if not k.startswith("__")})
+        setattr(view, _RESNET18_NAME, resnet18.resnet18_baseline)
+        sys.modules[_RESNET18_MOD] = view
+        setattr(sys.modules["models"], "resnet_custom", view)
+        _saved[_RESNET18_KEY] = ("view", view, mod)
+    else:
+        _saved[_RESNET18_KEY] = ("rebound", mod, mod.__dict__.get(_RESNET18_NAME))
+        setattr(mod, _RESNET18_NAME, resnet18.resnet18_baseline)
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_RESNET18_KEY} -> {resnet18.__name__}.resnet18_baseline")
+    return True
+
+
+def _uninstall_resnet18():
+    if _RESNET18_KEY not in _saved:
+        return
+    how, mod, prev = _saved.pop(_RESNET18_KEY)
+    if how == "view":
+        if sys.modules.get(_RESNET18_MOD) is mod:
+            sys.modules[_RESNET18_MOD] = prev
+            if "models" in sys.modules:
+                setattr(sys.modules["models"], "resnet_custom", prev)
+    elif prev is None:
+        delattr(mod, _RESNET18_NAME)
+    else:
+        setattr(mod, _RESNET18_NAME, prev)
+
+
+def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
     ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
-    ``heatmaps=True`` also binds ``WholeSlideImage.visHeatmap`` where the reference's ``wsi_core`` imports (else a no-op)."""
+    ``heatmaps=True`` also binds ``WholeSlideImage.visHeatmap`` where the reference's ``wsi_core`` imports (else a no-op).
+    ``resnet18=True`` also binds ``models.resnet_custom.resnet18_baseline`` to ``resnet18.resnet18_baseline`` (the HistoResNet-18
+    extractor), on the module ``resnet=True`` mapped or on the reference's own."""
     done = {}
     if heatmaps and _install_heatmaps(verbose):
         done[_WSI_MOD + ".WholeSlideImage.visHeatmap"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.vis_heatmap"
@@ -176,10 +228,13 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False,
         done[ref_name] = mod.__name__
         if verbose:
             print(f"[hipt_abmil_atec23_amd] {ref_name} -> {mod.__name__}")
+    if resnet18 and _install_resnet18(verbose):
+        done[_RESNET18_KEY] = f"{pkg}.resnet18.resnet18_baseline"
     return done
 
 
 def uninstall():
+    _uninstall_resnet18()
     _uninstall_sampling()
     _uninstall_heatmaps()
     for ref_name in _MAP:

@@ -209,7 +209,8 @@ def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], f
     and the features of call k are read back (on a stream of their own) only after call k + 1 has been enqueued -- the link, the GPU and the host loop overlap.  Same
     gathered tensor, same kernels, same bits as with resident batches.
 
-    ``model`` may also be a ``ResNet_Baseline`` (``--model_type resnet50``: patches ``[B, 3, H, W]``, features ``[B, 1024]``): host
+    ``model`` may also be a ``ResNet_Baseline`` (``--model_type resnet50``: patches ``[B, 3, H, W]``, features ``[B, 1024]``) or a
+    ``ResNet18_Baseline`` (``--model_type resnet18``, features ``[B, 512]`` on the Histo route): host
     batches take the same copy-stream path (keyed on the model's ``weight_device``), and loader batches of any patch size are gathered
     up to ``coalesce`` patches per call -- bit-exact, since every output row depends on its own patch only."""
     w = FeatureWriter(feat_dir, slide_id)
@@ -248,8 +249,9 @@ def extract_slide_augmented(model, batches: Iterable[Tuple[torch.Tensor, torch.T
 
 
 def _is_resnet(model) -> bool:
+    from .resnet18 import ResNet18_Baseline
     from .resnet_custom import ResNet_Baseline
-    return isinstance(model, ResNet_Baseline)
+    return isinstance(model, (ResNet_Baseline, ResNet18_Baseline))
 
 
 def _extract(model, batches, writers, run, coalesce: int) -> list:

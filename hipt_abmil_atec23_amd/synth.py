@@ -178,6 +178,39 @@ def resnet_param_specs(layers=(3, 4, 6)):
     return sp
 
 
+def resnet18_conv_bn_names(layers=(2, 2, 2, 2)):
+    """``[(conv, bn, cout, cin, k)]`` of torchvision's ResNet-18 (resnet18.ResNet18_Baseline) in state-dict order: stem, then per
+    BasicBlock conv1, conv2 and (block 0 of layers 2..4) downsample."""
+    out = [("conv1", "bn1", 64, 3, 7)]
+    inplanes = 64
+    for L, nb in enumerate(layers):
+        planes = 64 << L
+        for b in range(nb):
+            p = f"layer{L + 1}.{b}."
+            out += [(p + "conv1", p + "bn1", planes, inplanes, 3), (p + "conv2", p + "bn2", planes, planes, 3)]
+            if b == 0 and L > 0:
+                out.append((p + "downsample.0", p + "downsample.1", planes, inplanes, 1))
+            inplanes = planes
+    return out
+
+
+def resnet18_param_specs(layers=(2, 2, 2, 2), num_classes: int = 1000):
+    """``name -> (shape, scale, offset)`` of ResNet18_Baseline: the learnable tensors as in :func:`resnet_param_specs`, plus the
+    BatchNorm running statistics (means within +-0.1, variances in [0.5, 1.5]) and ``fc`` (``num_classes=0``: no fc)."""
+    sp = OrderedDict()
+    for conv, bn, cout, cin, k in resnet18_conv_bn_names(layers):
+        sp[conv + ".weight"] = ((cout, cin, k, k), math.sqrt(6.0 / (cout * k * k)), 0.0)
+        sp[bn + ".weight"] = ((cout,), 0.1, 1.0)
+        sp[bn + ".bias"] = ((cout,), 0.05, 0.0)
+        sp[bn + ".running_mean"] = ((cout,), 0.1, 0.0)
+        sp[bn + ".running_var"] = ((cout,), 0.5, 1.0)
+    if num_classes:
+        width = 64 << (len(layers) - 1)
+        sp["fc.weight"] = ((num_classes, width), math.sqrt(3.0 / width), 0.0)
+        sp["fc.bias"] = ((num_classes,), 0.02, 0.0)
+    return sp
+
+
 def hash_u8_np(shape, seed: int) -> np.ndarray:
     """uint8 array (the top byte of the hash): synthetic RGB pixels."""
     n = int(np.prod(shape)) if len(shape) else 1

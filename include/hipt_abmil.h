@@ -534,6 +534,44 @@ int hipt_conv2d(const void* x, int n, int h, int w, int cin, const void* w_packe
 int hipt_resnet_maxpool(const void* x, int n, int h, int w, int c, void* out, int dtype, void* stream);
 /* AdaptiveAvgPool2d(1) on NHWC x[n, hw, c] -> out[n, c] fp32, each sum in pixel order. */
 int hipt_resnet_avgpool(const void* x, int n, int hw, int c, float* out, int dtype, void* stream);
+/* hipt_conv2d with the output-pixel tile height chosen by the caller: tile_rows 128 (what hipt_conv2d and the ResNet-50
+ * network launch), 64, or 0 for hipt_conv_tile_rows(n*oh*ow, cout).  One output element is accumulated in the same K
+ * order under either height: the results are bit-identical, only the workgroup count differs. */
+int hipt_conv2d_ex(const void* x, int n, int h, int w, int cin, const void* w_packed, const float* bias, int cout, int kh, int kw,
+                   int stride, int pad, const void* resid, int relu, void* out, int dtype, int tile_rows, void* stream);
+/* The tile rule of the BasicBlock network, a pure function of a conv's output pixels m and channels: 64 where 128-row
+ * tiles give fewer workgroups than the chip has compute units (256) and 64-row tiles give more, else 128; 0 for a bad
+ * argument (m < 1, cout not a multiple of 64).  The 256 is the MI355X's CU count, compiled in; the rule was measured on
+ * 256 x 256 patches at batch 32 and 256 only. */
+int hipt_conv_tile_rows(int64_t m, int cout);
+
+/* ------------------------------------------------------------------------------------
+ * BasicBlock ResNet feature extractor (torchvision's resnet18, what models/resnet_custom.py:resnet18_baseline builds;
+ * extract_features_fp.py --model_type resnet18): stem conv 7x7/2 + BN + ReLU, maxpool 3x3/2, layer1..layer4 of BasicBlocks
+ * (two 3x3 convs, the stride on conv1, a 1x1 downsample in block 0 of layers 2..4), AdaptiveAvgPool2d(1) -> [n, 512] fp32
+ * (the fc layer is the caller's).  Same contract as the ResNet-50 entry points above: input kinds, norm, 256-byte
+ * alignment, error codes, nothing launched on a refusal.
+ * `convs`: HOST array in state-dict order -- conv1/bn1, then per block conv1/bn1, conv2/bn2 and, where present,
+ * downsample.0/downsample.1.  layers[]: blocks of layer1..layer4; trailing zeros leave the later layers out, and out is
+ * [n, 64 * 2^(L-1)] for the last built layer L.  tile_rows: 0 (the rule below) or 128 (128-row tiles on every conv: the
+ * other side of the rule's A/B; the results do not change, only the speed); anything else is HIPT_E_BADARG.
+ * ---------------------------------------------------------------------------------- */
+typedef struct hipt_resnet_basic_weights {
+    int32_t dtype;          /* HIPT_F32 / HIPT_BF16: GEMM operands and stored activations */
+    int32_t layers[4];
+    const hipt_conv_bn* convs;
+    int32_t n_convs;
+    int32_t tile_rows;      /* 0: hipt_conv_tile_rows picks each conv's tile height; 128: 128-row tiles on every conv */
+} hipt_resnet_basic_weights;
+
+size_t hipt_resnet_basic_packed_bytes(const hipt_resnet_basic_weights* w);   /* 0 if w is invalid */
+int hipt_resnet_basic_pack_weights(const hipt_resnet_basic_weights* w, void* packed, void* stream);
+/* 0 if w is invalid or the shape is one the forward refuses (n < 1, h or wd not a multiple of 32) */
+size_t hipt_resnet_basic_workspace_bytes(const hipt_resnet_basic_weights* w, int n, int h, int wd);
+/* h, wd multiples of 32 (every map down to layer4's is even), else HIPT_E_UNSUPPORTED.  Every output row depends on its
+ * own image only: no split-K, no atomics, and the tile height (which follows the batch) changes no bit. */
+int hipt_resnet_basic_forward(const hipt_resnet_basic_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
+                              int n, int h, int wd, float* out, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DRAS-MIL attention-guided sampling (eval.py --sampling: utils/eval_utils.py:182-565 summary_sampling, helpers in
