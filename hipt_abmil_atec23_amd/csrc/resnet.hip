@@ -378,194 +378,247 @@ int run_avgpool(const void* x, int n, int hw, int C, float* out, int dtype, hipS
 }
 
 // ---- the network ------------------------------------------------------------------------------------------------------
-// conv order of hipt_resnet_weights.convs: stem, then per block conv1, conv2, conv3 and (first block of a layer where the
-// shape changes) downsample -- the order of the reference's state dict.
+// Both networks (bottleneck: hipt_resnet_weights, BasicBlock: hipt_resnet_basic_weights) are ONE description, built per call in
+// fixed-size arrays: the conv records in the order of the caller's convs[] (the reference's state dict: stem, then block by block)
+// and the steps in launch order, each naming its activation buffers by index.  The packed image, the workspace sizes, the
+// pointers and the launches all come from it; a further network (ResNet-34, -101, ...) is a builder of a few lines.
+// Head and tail are fixed: input -> NHWC in T, stem conv T -> A, maxpool A -> B, the blocks, average pool of the last block output.
 struct NetConv {
     int cin, cout, k, stride, pad;
 };
-constexpr int RN_MAX_CONVS = 1 + 3 * 4 * 64;
+struct Step {
+    int conv, src, dst, resid, relu;  // conv record and buffers by index; resid < 0: none
+};
+constexpr int RN_MAX_CONVS = 1 + 3 * 4 * 64;  // 3 layers of 64 four-conv bottlenecks, or 4 layers of 64 three-conv BasicBlocks
+constexpr int RN_MAX_BUFS = 5;
+// A, B: block input / output, swapped block by block; T: block interior, first the NHWC copy of the input.  The buffers after
+// these are the block shape's own (bottleneck: T2, D; BasicBlock: D).
+enum { BUF_A, BUF_B, BUF_T };
+constexpr Step RN_STEM = {0, BUF_T, BUF_A, -1, 1};
 
-int net_convs(const hipt_resnet_weights* w, NetConv* out) {
-    int nc = 0, inplanes = 64;
-    out[nc++] = {3, 64, 7, 2, 3};
-    for (int L = 0; L < 3; ++L) {
-        const int planes = 64 << L, stride = L ? 2 : 1;
-        for (int b = 0; b < w->layers[L]; ++b) {
-            const int s = b ? 1 : stride;
-            out[nc++] = {inplanes, planes, 1, 1, 0};
-            out[nc++] = {planes, planes, 3, s, 1};
-            out[nc++] = {planes, planes * 4, 1, 1, 0};
-            if (b == 0 && (s != 1 || inplanes != planes * 4)) out[nc++] = {inplanes, planes * 4, 1, s, 0};
-            inplanes = planes * 4;
-        }
-    }
-    return nc;
+struct Net {
+    const char* name;  // the prefix of this network's messages
+    int dtype;
+    int rows;          // tile height of every conv launch: RN_BM, or 0 for tile_rows_rule
+    int grain;         // envelope: H and W multiples of this, at least 32
+    int n_bufs, n_convs, n_steps;
+    int cur, width;    // buffer and channels of the newest block output
+    NetConv conv[RN_MAX_CONVS];
+    Step step[RN_MAX_CONVS];
+};
+
+void net_init(Net& net, const char* name, int dtype, int rows, int grain, int n_bufs) {
+    net.name = name, net.dtype = dtype, net.rows = rows, net.grain = grain, net.n_bufs = n_bufs;
+    net.n_convs = 1, net.n_steps = 0, net.cur = BUF_B, net.width = 64;
+    net.conv[0] = {3, 64, 7, 2, 3};
+}
+int add_conv(Net& net, NetConv c) {
+    net.conv[net.n_convs] = c;
+    return net.n_convs++;
+}
+void add_step(Net& net, Step s) { net.step[net.n_steps++] = s; }
+
+// Bottleneck_Baseline, stride on conv2.  Records: conv1, conv2, conv3, downsample; launches: conv1, conv2, downsample, conv3.
+void add_bottleneck(Net& net, int planes, int s) {
+    const int in = net.width, out = planes * 4, cur = net.cur, nxt = cur ^ 1, T2 = 3, D = 4;
+    const bool ds = s != 1 || in != out;  // _make_layer's rule
+    const int c1 = add_conv(net, {in, planes, 1, 1, 0}), c2 = add_conv(net, {planes, planes, 3, s, 1});
+    const int c3 = add_conv(net, {planes, out, 1, 1, 0});
+    add_step(net, {c1, cur, BUF_T, -1, 1});
+    add_step(net, {c2, BUF_T, T2, -1, 1});
+    if (ds) add_step(net, {add_conv(net, {in, out, 1, s, 0}), cur, D, -1, 0});
+    add_step(net, {c3, T2, nxt, ds ? D : cur, 1});
+    net.cur = nxt, net.width = out;
 }
 
-// the caller's conv records against the table the layer counts imply
-int check_convs(const hipt_conv_bn* convs, int n_convs, const NetConv* nc, int count) {
-    HIPT_CHECK_ARG(n_convs == count && convs != nullptr, "resnet: %d convs given, the layer counts need %d", n_convs, count);
-    for (int i = 0; i < count; ++i) {
+// torchvision's BasicBlock, stride on conv1.  Records: conv1, conv2, downsample; launches: conv1, downsample, conv2.
+void add_basic(Net& net, int planes, int s) {
+    const int in = net.width, cur = net.cur, nxt = cur ^ 1, D = 3;
+    const bool ds = s != 1 || in != planes;  // _make_layer's rule
+    const int c1 = add_conv(net, {in, planes, 3, s, 1}), c2 = add_conv(net, {planes, planes, 3, 1, 1});
+    add_step(net, {c1, cur, BUF_T, -1, 1});
+    if (ds) add_step(net, {add_conv(net, {in, planes, 1, s, 0}), cur, D, -1, 0});
+    add_step(net, {c2, BUF_T, nxt, ds ? D : cur, 1});
+    net.cur = nxt, net.width = planes;
+}
+
+// layer L: layers[L] blocks of 64 << L planes; its first block halves the map, except in the first layer (behind the maxpool)
+void add_layers(Net& net, const int* layers, int nl, void (*add_block)(Net&, int, int)) {
+    for (int L = 0; L < nl; ++L)
+        for (int b = 0; b < layers[L]; ++b) add_block(net, 64 << L, (L && b == 0) ? 2 : 1);
+}
+
+// the caller's conv records against the ones the layer counts imply
+int check_convs(const hipt_conv_bn* convs, int n_convs, const Net& net) {
+    HIPT_CHECK_ARG(n_convs == net.n_convs && convs != nullptr, "resnet: %d convs given, the layer counts need %d", n_convs, net.n_convs);
+    for (int i = 0; i < net.n_convs; ++i) {
         const hipt_conv_bn& c = convs[i];
-        HIPT_CHECK_ARG(c.cin == nc[i].cin && c.cout == nc[i].cout && c.kh == nc[i].k && c.kw == nc[i].k,
-                       "resnet: conv %d is %dx%dx%dx%d, expected %dx%dx%dx%d", i, c.cout, c.cin, c.kh, c.kw, nc[i].cout, nc[i].cin,
-                       nc[i].k, nc[i].k);
+        const NetConv& e = net.conv[i];
+        HIPT_CHECK_ARG(c.cin == e.cin && c.cout == e.cout && c.kh == e.k && c.kw == e.k,
+                       "resnet: conv %d is %dx%dx%dx%d, expected %dx%dx%dx%d", i, c.cout, c.cin, c.kh, c.kw, e.cout, e.cin, e.k, e.k);
         HIPT_CHECK_ARG(c.weight && c.bn_weight && c.bn_bias && c.bn_mean && c.bn_var, "resnet: conv %d has a null tensor", i);
     }
     return HIPT_OK;
 }
 
-int check_weights(const hipt_resnet_weights* w, NetConv* nc, int* count) {
+// the caller's struct, checked, as a description: 128-row tiles on every conv, H and W multiples of 16
+int check_weights(const hipt_resnet_weights* w, Net& net) {
     HIPT_CHECK_ARG(w != nullptr, "resnet: null weights");
     HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "resnet: bad dtype %d", w->dtype);
     for (int L = 0; L < 3; ++L)
         HIPT_CHECK_ARG(w->layers[L] >= 1 && w->layers[L] <= 64, "resnet: layers[%d]=%d outside [1, 64]", L, w->layers[L]);
-    *count = net_convs(w, nc);
-    return check_convs(w->convs, w->n_convs, nc, *count);
+    net_init(net, "resnet", w->dtype, RN_BM, 16, 5);
+    add_layers(net, w->layers, 3, add_bottleneck);
+    return check_convs(w->convs, w->n_convs, net);
 }
 
-// the packed weight image: per conv, in the order of hipt_resnet_weights.convs, its packed weight | its folded fp32 bias
-struct ConvImg { const void* w; const float* bias; };
-void carve_packed(Carver& c, const NetConv* nc, int count, int dtype, ConvImg* out) {
-    for (int i = 0; i < count; ++i) {
-        out[i].w = c.take((size_t)nc[i].cout * conv_kp(nc[i].cin, nc[i].k, nc[i].k, dtype) * esize(dtype));
-        out[i].bias = c.take<float>(nc[i].cout);
-    }
-}
-
-// workspace: five NHWC activation buffers (A, B: block input / output, T1, T2: bottleneck interior, D: downsample), each
-// as large as the largest tensor it ever holds; T1 also holds the NHWC copy of the input.
-struct NetPlan {
-    size_t sz[5];
-};
-NetPlan plan(const hipt_resnet_weights* w, int n, int h, int wd) {
-    NetPlan pl = {};
-    const size_t es = esize(w->dtype);
-    auto upd = [&](int i, size_t elems) { pl.sz[i] = pl.sz[i] > elems * es ? pl.sz[i] : elems * es; };
-    const size_t N = (size_t)n;
-    upd(2, N * h * wd * 3);
-    int hh = conv_out(h, 7, 2, 3), ww = conv_out(wd, 7, 2, 3);
-    upd(0, N * hh * ww * 64);
-    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
-    upd(1, N * hh * ww * 64);
-    int inplanes = 64;
-    for (int L = 0; L < 3; ++L) {
-        const int planes = 64 << L;
-        for (int b = 0; b < w->layers[L]; ++b) {
-            const int s = b ? 1 : (L ? 2 : 1);
-            upd(2, N * hh * ww * planes);
-            const int h2 = conv_out(hh, 3, s, 1), w2 = conv_out(ww, 3, s, 1);
-            upd(3, N * h2 * w2 * planes);
-            upd(4, N * h2 * w2 * planes * 4);
-            upd(0, N * h2 * w2 * planes * 4);
-            upd(1, N * h2 * w2 * planes * 4);
-            hh = h2, ww = w2, inplanes = planes * 4;
-        }
-    }
-    (void)inplanes;
-    for (auto& s : pl.sz) s = al256(s);
-    return pl;
-}
-
-void carve_net(Carver& c, const NetPlan& pl, char* (&buf)[5]) {
-    for (int i = 0; i < 5; ++i) buf[i] = (char*)c.take(pl.sz[i]);
-}
-
-int check_shape(int n, int h, int w) {
-    HIPT_CHECK_ARG(n >= 1 && h > 0 && w > 0, "resnet: empty input n=%d h=%d w=%d", n, h, w);
-    if (h % 16 || w % 16 || h < 32 || w < 32) {
-        hipt_set_error("resnet: %d x %d input outside the envelope (height and width multiples of 16, at least 32)", h, w);
-        return HIPT_E_UNSUPPORTED;
-    }
-    if ((int64_t)n * (h / 2) * (w / 2) >= ((int64_t)1 << 30)) {
-        hipt_set_error("resnet: batch of %d images of %d x %d too large for one call", n, h, w);
-        return HIPT_E_UNSUPPORTED;
-    }
-    return HIPT_OK;
-}
-
-// ---- the BasicBlock network (torchvision's ResNet-18 / -34 family: hipt_resnet_basic_weights) -----------------------------
-// conv order: stem, then per block conv1 (3x3, carries the stride), conv2 (3x3) and, in block 0 of layers 2..4, downsample (1x1).
-// layers[]: blocks of layer1..layer4; trailing zeros leave the later layers out (the output is the last built layer's width).
-int basic_layers(const hipt_resnet_basic_weights* w) {
-    int L = 0;
-    while (L < 4 && w->layers[L] > 0) ++L;
-    return L;
-}
-
-int basic_convs(const hipt_resnet_basic_weights* w, NetConv* out) {
-    int nc = 0, inplanes = 64;
-    out[nc++] = {3, 64, 7, 2, 3};
-    for (int L = 0, nl = basic_layers(w); L < nl; ++L) {
-        const int planes = 64 << L;
-        for (int b = 0; b < w->layers[L]; ++b) {
-            const int s = (L && b == 0) ? 2 : 1;
-            out[nc++] = {inplanes, planes, 3, s, 1};
-            out[nc++] = {planes, planes, 3, 1, 1};
-            if (s != 1 || inplanes != planes) out[nc++] = {inplanes, planes, 1, s, 0};
-            inplanes = planes;
-        }
-    }
-    return nc;
-}
-
-int check_basic_weights(const hipt_resnet_basic_weights* w, NetConv* nc, int* count) {
+// the BasicBlock network (torchvision's ResNet-18 / -34 family).  layers[]: blocks of layer1..layer4; trailing zeros leave the later
+// layers out (the output is the last built layer's width).  Tile height as the struct says: the rule (0) or 128 rows on every conv,
+// both give the same bits.  H and W multiples of 32.
+int check_basic_weights(const hipt_resnet_basic_weights* w, Net& net) {
     HIPT_CHECK_ARG(w != nullptr, "resnet_basic: null weights");
     HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "resnet_basic: bad dtype %d", w->dtype);
     HIPT_CHECK_ARG(w->tile_rows == 0 || w->tile_rows == RN_BM, "resnet_basic: tile_rows=%d is neither 0 (the rule) nor 128", w->tile_rows);
-    const int nl = basic_layers(w);
+    int nl = 0;
+    while (nl < 4 && w->layers[nl] > 0) ++nl;
     HIPT_CHECK_ARG(nl >= 1, "resnet_basic: layers[0]=%d, at least one block is needed", w->layers[0]);
     for (int L = 0; L < 4; ++L)
         HIPT_CHECK_ARG(L < nl ? w->layers[L] <= 64 : w->layers[L] == 0, "resnet_basic: layers[%d]=%d (1..64 blocks, then zeros only)", L,
                        w->layers[L]);
-    *count = basic_convs(w, nc);
-    return check_convs(w->convs, w->n_convs, nc, *count);
+    net_init(net, "resnet_basic", w->dtype, w->tile_rows, 32, 4);
+    add_layers(net, w->layers, nl, add_basic);
+    return check_convs(w->convs, w->n_convs, net);
 }
 
-// workspace: four NHWC activation buffers (A, B: block input / output, T: block interior, D: downsample), each as large as the
-// largest tensor it ever holds; T also holds the NHWC copy of the input.
-struct BasicPlan {
-    size_t sz[4];
-};
-BasicPlan basic_plan(const hipt_resnet_basic_weights* w, int n, int h, int wd) {
-    BasicPlan pl = {};
-    const size_t es = esize(w->dtype);
-    auto upd = [&](int i, size_t elems) { pl.sz[i] = pl.sz[i] > elems * es ? pl.sz[i] : elems * es; };
-    const size_t N = (size_t)n;
-    upd(2, N * h * wd * 3);
-    int hh = conv_out(h, 7, 2, 3), ww = conv_out(wd, 7, 2, 3);
-    upd(0, N * hh * ww * 64);
-    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
-    upd(1, N * hh * ww * 64);
-    for (int L = 0, nl = basic_layers(w); L < nl; ++L) {
-        const size_t planes = (size_t)64 << L;
-        for (int b = 0; b < w->layers[L]; ++b) {
-            const int s = (L && b == 0) ? 2 : 1;
-            hh = conv_out(hh, 3, s, 1), ww = conv_out(ww, 3, s, 1);
-            for (int i = 0; i < 3; ++i) upd(i, N * hh * ww * planes);
-            if (s != 1) upd(3, N * hh * ww * planes);
-        }
-    }
-    upd(3, 1);  // layer1 alone has no downsample: the carve stays non-empty
-    for (auto& s : pl.sz) s = al256(s);
-    return pl;
-}
-
-void carve_basic(Carver& c, const BasicPlan& pl, char* (&buf)[4]) {
-    for (int i = 0; i < 4; ++i) buf[i] = (char*)c.take(pl.sz[i]);
-}
-
-int check_basic_shape(int n, int h, int w) {
-    HIPT_CHECK_ARG(n >= 1 && h > 0 && w > 0, "resnet_basic: empty input n=%d h=%d w=%d", n, h, w);
-    if (h % 32 || w % 32) {
-        hipt_set_error("resnet_basic: %d x %d input outside the envelope (height and width multiples of 32, at least 32)", h, w);
+int check_shape(const Net& net, int n, int h, int w) {
+    HIPT_CHECK_ARG(n >= 1 && h > 0 && w > 0, "%s: empty input n=%d h=%d w=%d", net.name, n, h, w);
+    if (h % net.grain || w % net.grain || h < 32 || w < 32) {
+        hipt_set_error("%s: %d x %d input outside the envelope (height and width multiples of %d, at least 32)", net.name, h, w, net.grain);
         return HIPT_E_UNSUPPORTED;
     }
     if ((int64_t)n * (h / 2) * (w / 2) >= ((int64_t)1 << 30)) {
-        hipt_set_error("resnet_basic: batch of %d images of %d x %d too large for one call", n, h, w);
+        hipt_set_error("%s: batch of %d images of %d x %d too large for one call", net.name, n, h, w);
         return HIPT_E_UNSUPPORTED;
     }
     return HIPT_OK;
+}
+
+// the packed weight image: per conv, in the order of the caller's convs[], its packed weight | its folded fp32 bias
+struct ConvImg { const void* w; const float* bias; };
+void carve_packed(Carver& c, const Net& net, ConvImg* out) {
+    for (int i = 0; i < net.n_convs; ++i) {
+        const NetConv& e = net.conv[i];
+        out[i].w = c.take((size_t)e.cout * conv_kp(e.cin, e.k, e.k, net.dtype) * esize(net.dtype));
+        out[i].bias = c.take<float>(e.cout);
+    }
+}
+
+// One walk over the head and the steps for n images of h x w: the map every step reads, and the bytes of every buffer.
+// The workspace rule: a buffer is as large as the largest tensor the walk puts into it; a block's output counts for A and B
+// alike (which of the two it lands in follows from the number of blocks before it; the size must not); no buffer is empty
+// (D of a BasicBlock network of layer1 alone is never written).
+struct NetPlan {
+    size_t sz[RN_MAX_BUFS];
+    int h[RN_MAX_CONVS], w[RN_MAX_CONVS];  // the map step i reads
+    int sh, sw, oh, ow;                    // the stem's output map, the last block's
+};
+NetPlan plan(const Net& net, int n, int h, int w) {
+    NetPlan pl;
+    const size_t es = esize(net.dtype);
+    int bh[RN_MAX_BUFS], bw[RN_MAX_BUFS];  // the map each buffer holds
+    for (int b = 0; b < net.n_bufs; ++b) pl.sz[b] = 0;
+    auto hold = [&](int b, int hh, int ww, int c) {  // buffer b now holds [n, hh, ww, c]
+        bh[b] = hh, bw[b] = ww;
+        const size_t bytes = (size_t)n * hh * ww * c * es;
+        pl.sz[b] = pl.sz[b] > bytes ? pl.sz[b] : bytes;
+        return bytes;
+    };
+    auto conv = [&](const Step& s) {
+        const NetConv& c = net.conv[s.conv];
+        return hold(s.dst, conv_out(bh[s.src], c.k, c.stride, c.pad), conv_out(bw[s.src], c.k, c.stride, c.pad), c.cout);
+    };
+    hold(BUF_T, h, w, net.conv[0].cin);
+    conv(RN_STEM);
+    pl.sh = bh[BUF_A], pl.sw = bw[BUF_A];
+    hold(BUF_B, conv_out(pl.sh, 3, 2, 1), conv_out(pl.sw, 3, 2, 1), net.conv[0].cout);
+    for (int i = 0; i < net.n_steps; ++i) {
+        const Step& s = net.step[i];
+        pl.h[i] = bh[s.src], pl.w[i] = bw[s.src];
+        const size_t bytes = conv(s);
+        if (s.dst <= BUF_B && pl.sz[s.dst ^ 1] < bytes) pl.sz[s.dst ^ 1] = bytes;  // A and B alike
+    }
+    pl.oh = bh[net.cur], pl.ow = bw[net.cur];
+    for (int b = 0; b < net.n_bufs; ++b) pl.sz[b] = al256(pl.sz[b] ? pl.sz[b] : 1);  // no buffer is empty
+    return pl;
+}
+
+void carve_net(Carver& c, const Net& net, const NetPlan& pl, char** buf) {
+    for (int b = 0; b < net.n_bufs; ++b) buf[b] = (char*)c.take(pl.sz[b]);
+}
+
+// ---- the four entry points of a network, on its description ---------------------------------------------------------------
+size_t net_packed_bytes(const Net& net) {
+    ConvImg img[RN_MAX_CONVS];
+    return dry_run([&](Carver& c) { carve_packed(c, net, img); });
+}
+
+int net_pack_weights(const Net& net, const hipt_conv_bn* convs, void* packed, void* stream) {
+    HIPT_CHECK_ARG(packed && ((uintptr_t)packed % 256) == 0, "%s_pack_weights: packed image must be 256-byte aligned", net.name);
+    ConvImg img[RN_MAX_CONVS];
+    Carver c(packed);
+    carve_packed(c, net, img);
+    for (int i = 0; i < net.n_convs; ++i)
+        if (int r = hipt_conv_bn_pack(&convs[i], net.dtype, (void*)img[i].w, (float*)img[i].bias, stream)) return r;
+    return HIPT_OK;
+}
+
+size_t net_workspace_bytes(const Net& net, int n, int h, int w) {
+    char* buf[RN_MAX_BUFS];
+    return dry_run([&](Carver& c) { carve_net(c, net, plan(net, n, h, w), buf); });
+}
+
+int net_forward(const Net& net, const void* packed, const void* x, int input_kind, const float* norm, int n, int h, int w, float* out,
+                void* workspace, size_t ws_bytes, void* stream) {
+    int rc = check_shape(net, n, h, w);
+    if (rc != HIPT_OK) return rc;
+    HIPT_CHECK_ARG(input_kind == HIPT_RESNET_IN_F32 || input_kind == HIPT_RESNET_IN_U8 || input_kind == HIPT_RESNET_IN_U8_HWC,
+                   "%s: bad input kind %d", net.name, input_kind);
+    HIPT_CHECK_ARG(packed && x && out && workspace && ((uintptr_t)packed % 256) == 0 && ((uintptr_t)workspace % 256) == 0 &&
+                       ((uintptr_t)out % 16) == 0,
+                   "%s: null pointer, or packed / workspace not 256-byte aligned", net.name);
+    const int dt = net.dtype;
+    hipStream_t st = (hipStream_t)stream;
+    const NetPlan pl = plan(net, n, h, w);
+    char* buf[RN_MAX_BUFS];
+    Carver ws(workspace, ws_bytes);
+    carve_net(ws, net, pl, buf);
+    char who[32];
+    snprintf(who, sizeof who, "%s_forward", net.name);
+    if ((rc = check_workspace(ws, who)) != HIPT_OK) return rc;
+    ConvImg img[RN_MAX_CONVS];
+    Carver pk((void*)packed);
+    carve_packed(pk, net, img);
+
+    NormArgs nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
+    if (norm)
+        for (int c = 0; c < 3; ++c) nm.mean[c] = norm[c], nm.std[c] = norm[3 + c];
+    const int64_t npx = (int64_t)n * h * w;
+    rc = dt == HIPT_BF16 ? launch_input<bf16_t>(x, input_kind, npx, (int64_t)h * w, nm, (bf16_t*)buf[BUF_T], st)
+                         : launch_input<float>(x, input_kind, npx, (int64_t)h * w, nm, (float*)buf[BUF_T], st);
+    if (rc != HIPT_OK) return rc;
+    auto conv = [&](const Step& s, int hh, int ww) -> int {
+        const NetConv& c = net.conv[s.conv];
+        ConvArgs a = {};
+        a.x = buf[s.src], a.wt = img[s.conv].w, a.bias = img[s.conv].bias, a.resid = s.resid < 0 ? nullptr : buf[s.resid], a.out = buf[s.dst];
+        a.n = n, a.h = hh, a.w = ww, a.cin = c.cin, a.cout = c.cout, a.kh = c.k, a.kw = c.k, a.stride = c.stride, a.pad = c.pad;
+        a.relu = s.relu;
+        return run_conv(a, dt, st, net.rows);
+    };
+    if ((rc = conv(RN_STEM, h, w)) != HIPT_OK) return rc;
+    if ((rc = run_maxpool(buf[BUF_A], n, pl.sh, pl.sw, net.conv[0].cout, buf[BUF_B], dt, st)) != HIPT_OK) return rc;
+    for (int i = 0; i < net.n_steps; ++i)
+        if ((rc = conv(net.step[i], pl.h[i], pl.w[i])) != HIPT_OK) return rc;
+    return run_avgpool(buf[net.cur], n, pl.oh * pl.ow, net.width, out, dt, st);
 }
 
 }  // namespace
@@ -593,14 +646,6 @@ int hipt_conv_bn_pack(const hipt_conv_bn* c, int dtype, void* w_out, float* bias
     return HIPT_OK;
 }
 
-int hipt_conv2d(const void* x, int n, int h, int w, int cin, const void* w_packed, const float* bias, int cout, int kh, int kw,
-                int stride, int pad, const void* resid, int relu, void* out, int dtype, void* stream) {
-    ConvArgs a = {};
-    a.x = x, a.wt = w_packed, a.bias = bias, a.resid = resid, a.out = out;
-    a.n = n, a.h = h, a.w = w, a.cin = cin, a.cout = cout, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.relu = relu ? 1 : 0;
-    return run_conv(a, dtype, (hipStream_t)stream);
-}
-
 int hipt_conv_tile_rows(int64_t m, int cout) {
     return (m > 0 && cout > 0 && cout % 64 == 0) ? tile_rows_rule(m, cout) : 0;
 }
@@ -612,6 +657,12 @@ int hipt_conv2d_ex(const void* x, int n, int h, int w, int cin, const void* w_pa
     a.x = x, a.wt = w_packed, a.bias = bias, a.resid = resid, a.out = out;
     a.n = n, a.h = h, a.w = w, a.cin = cin, a.cout = cout, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.relu = relu ? 1 : 0;
     return run_conv(a, dtype, (hipStream_t)stream, tile_rows);
+}
+
+// 128-row tiles, as every launch of the bottleneck network
+int hipt_conv2d(const void* x, int n, int h, int w, int cin, const void* w_packed, const float* bias, int cout, int kh, int kw,
+                int stride, int pad, const void* resid, int relu, void* out, int dtype, void* stream) {
+    return hipt_conv2d_ex(x, n, h, w, cin, w_packed, bias, cout, kh, kw, stride, pad, resid, relu, out, dtype, RN_BM, stream);
 }
 
 int hipt_resnet_maxpool(const void* x, int n, int h, int w, int c, void* out, int dtype, void* stream) {
@@ -627,200 +678,49 @@ int hipt_resnet_avgpool(const void* x, int n, int hw, int c, float* out, int dty
 }
 
 size_t hipt_resnet_packed_bytes(const hipt_resnet_weights* w) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    if (check_weights(w, nc, &count) != HIPT_OK) return 0;
-    ConvImg img[RN_MAX_CONVS];
-    return dry_run([&](Carver& c) { carve_packed(c, nc, count, w->dtype, img); });
+    Net net;
+    return check_weights(w, net) == HIPT_OK ? net_packed_bytes(net) : 0;
 }
 
 int hipt_resnet_pack_weights(const hipt_resnet_weights* w, void* packed, void* stream) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    const int rc = check_weights(w, nc, &count);
-    if (rc != HIPT_OK) return rc;
-    HIPT_CHECK_ARG(packed && ((uintptr_t)packed % 256) == 0, "resnet_pack_weights: packed image must be 256-byte aligned");
-    ConvImg img[RN_MAX_CONVS];
-    Carver c(packed);
-    carve_packed(c, nc, count, w->dtype, img);
-    for (int i = 0; i < count; ++i)
-        if (int r = hipt_conv_bn_pack(&w->convs[i], w->dtype, (void*)img[i].w, (float*)img[i].bias, stream)) return r;
-    return HIPT_OK;
+    Net net;
+    const int rc = check_weights(w, net);
+    return rc != HIPT_OK ? rc : net_pack_weights(net, w->convs, packed, stream);
 }
 
 size_t hipt_resnet_workspace_bytes(const hipt_resnet_weights* w, int n, int h, int wd) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    if (check_weights(w, nc, &count) != HIPT_OK || n < 1 || h < 1 || wd < 1) return 0;
-    char* buf[5];
-    return dry_run([&](Carver& c) { carve_net(c, plan(w, n, h, wd), buf); });
+    Net net;
+    return check_weights(w, net) == HIPT_OK && n >= 1 && h >= 1 && wd >= 1 ? net_workspace_bytes(net, n, h, wd) : 0;
 }
 
 int hipt_resnet_forward(const hipt_resnet_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
                         int n, int h, int wd, float* out, void* workspace, size_t ws_bytes, void* stream) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    int rc = check_weights(w, nc, &count);
-    if (rc != HIPT_OK) return rc;
-    rc = check_shape(n, h, wd);
-    if (rc != HIPT_OK) return rc;
-    HIPT_CHECK_ARG(input_kind == HIPT_RESNET_IN_F32 || input_kind == HIPT_RESNET_IN_U8 || input_kind == HIPT_RESNET_IN_U8_HWC,
-                   "resnet: bad input kind %d", input_kind);
-    HIPT_CHECK_ARG(packed && x && out && workspace && ((uintptr_t)packed % 256) == 0 && ((uintptr_t)workspace % 256) == 0 &&
-                       ((uintptr_t)out % 16) == 0,
-                   "resnet: null pointer, or packed / workspace not 256-byte aligned");
-    const int dt = w->dtype;
-    hipStream_t st = (hipStream_t)stream;
-    char* buf[5];
-    Carver ws(workspace, ws_bytes);
-    carve_net(ws, plan(w, n, h, wd), buf);
-    if ((rc = check_workspace(ws, "resnet_forward")) != HIPT_OK) return rc;
-    ConvImg img[RN_MAX_CONVS];
-    Carver pk((void*)packed);
-    carve_packed(pk, nc, count, dt, img);
-    char *A = buf[0], *B = buf[1], *T1 = buf[2], *T2 = buf[3], *D = buf[4];
-
-    // input -> NHWC T in T1
-    NormArgs nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
-    if (norm)
-        for (int c = 0; c < 3; ++c) nm.mean[c] = norm[c], nm.std[c] = norm[3 + c];
-    {
-        const int64_t npx = (int64_t)n * h * wd;
-        rc = dt == HIPT_BF16 ? launch_input<bf16_t>(x, input_kind, npx, (int64_t)h * wd, nm, (bf16_t*)T1, st)
-                             : launch_input<float>(x, input_kind, npx, (int64_t)h * wd, nm, (float*)T1, st);
-        if (rc != HIPT_OK) return rc;
-    }
-    auto conv = [&](int i, const void* in, int hh, int ww, const void* resid, int relu, void* o, int* oh, int* ow) -> int {
-        const NetConv& c = nc[i];
-        ConvArgs a = {};
-        a.x = in, a.wt = img[i].w, a.bias = img[i].bias, a.resid = resid, a.out = o;
-        a.n = n, a.h = hh, a.w = ww, a.cin = c.cin, a.cout = c.cout, a.kh = c.k, a.kw = c.k, a.stride = c.stride, a.pad = c.pad;
-        a.relu = relu;
-        const int r = run_conv(a, dt, st);
-        *oh = a.oh, *ow = a.ow;
-        return r;
-    };
-    int hh, ww;
-    if ((rc = conv(0, T1, h, wd, nullptr, 1, A, &hh, &ww)) != HIPT_OK) return rc;
-    if ((rc = run_maxpool(A, n, hh, ww, 64, B, dt, st)) != HIPT_OK) return rc;
-    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
-    char *cur = B, *nxt = A;
-    int ci = 1, C = 64;
-    for (int L = 0; L < 3; ++L) {
-        const int planes = 64 << L;
-        for (int b = 0; b < w->layers[L]; ++b) {
-            const int s = b ? 1 : (L ? 2 : 1);
-            const bool ds = b == 0 && (s != 1 || C != planes * 4);  // the rule of net_convs / _make_layer
-            int h1, w1, h2, w2, h3, w3;
-            if ((rc = conv(ci, cur, hh, ww, nullptr, 1, T1, &h1, &w1)) != HIPT_OK) return rc;
-            if ((rc = conv(ci + 1, T1, h1, w1, nullptr, 1, T2, &h2, &w2)) != HIPT_OK) return rc;
-            if (ds && (rc = conv(ci + 3, cur, hh, ww, nullptr, 0, D, &h3, &w3)) != HIPT_OK) return rc;
-            if ((rc = conv(ci + 2, T2, h2, w2, ds ? (const void*)D : (const void*)cur, 1, nxt, &h3, &w3)) != HIPT_OK) return rc;
-            ci += ds ? 4 : 3;
-            C = planes * 4, hh = h3, ww = w3;
-            char* t = cur;
-            cur = nxt, nxt = t;
-        }
-    }
-    return run_avgpool(cur, n, hh * ww, C, out, dt, st);
+    Net net;
+    const int rc = check_weights(w, net);
+    return rc != HIPT_OK ? rc : net_forward(net, packed, x, input_kind, norm, n, h, wd, out, workspace, ws_bytes, stream);
 }
 
 size_t hipt_resnet_basic_packed_bytes(const hipt_resnet_basic_weights* w) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    if (check_basic_weights(w, nc, &count) != HIPT_OK) return 0;
-    ConvImg img[RN_MAX_CONVS];
-    return dry_run([&](Carver& c) { carve_packed(c, nc, count, w->dtype, img); });
+    Net net;
+    return check_basic_weights(w, net) == HIPT_OK ? net_packed_bytes(net) : 0;
 }
 
 int hipt_resnet_basic_pack_weights(const hipt_resnet_basic_weights* w, void* packed, void* stream) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    const int rc = check_basic_weights(w, nc, &count);
-    if (rc != HIPT_OK) return rc;
-    HIPT_CHECK_ARG(packed && ((uintptr_t)packed % 256) == 0, "resnet_basic_pack_weights: packed image must be 256-byte aligned");
-    ConvImg img[RN_MAX_CONVS];
-    Carver c(packed);
-    carve_packed(c, nc, count, w->dtype, img);
-    for (int i = 0; i < count; ++i)
-        if (int r = hipt_conv_bn_pack(&w->convs[i], w->dtype, (void*)img[i].w, (float*)img[i].bias, stream)) return r;
-    return HIPT_OK;
+    Net net;
+    const int rc = check_basic_weights(w, net);
+    return rc != HIPT_OK ? rc : net_pack_weights(net, w->convs, packed, stream);
 }
 
 size_t hipt_resnet_basic_workspace_bytes(const hipt_resnet_basic_weights* w, int n, int h, int wd) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    if (check_basic_weights(w, nc, &count) != HIPT_OK || check_basic_shape(n, h, wd) != HIPT_OK) return 0;  // what the forward refuses
-    char* buf[4];
-    return dry_run([&](Carver& c) { carve_basic(c, basic_plan(w, n, h, wd), buf); });
+    Net net;  // what the forward refuses has no size
+    return check_basic_weights(w, net) == HIPT_OK && check_shape(net, n, h, wd) == HIPT_OK ? net_workspace_bytes(net, n, h, wd) : 0;
 }
 
 int hipt_resnet_basic_forward(const hipt_resnet_basic_weights* w, const void* packed, const void* x, int input_kind, const float* norm,
                               int n, int h, int wd, float* out, void* workspace, size_t ws_bytes, void* stream) {
-    NetConv nc[RN_MAX_CONVS];
-    int count = 0;
-    int rc = check_basic_weights(w, nc, &count);
-    if (rc != HIPT_OK) return rc;
-    rc = check_basic_shape(n, h, wd);
-    if (rc != HIPT_OK) return rc;
-    HIPT_CHECK_ARG(input_kind == HIPT_RESNET_IN_F32 || input_kind == HIPT_RESNET_IN_U8 || input_kind == HIPT_RESNET_IN_U8_HWC,
-                   "resnet_basic: bad input kind %d", input_kind);
-    HIPT_CHECK_ARG(packed && x && out && workspace && ((uintptr_t)packed % 256) == 0 && ((uintptr_t)workspace % 256) == 0 &&
-                       ((uintptr_t)out % 16) == 0,
-                   "resnet_basic: null pointer, or packed / workspace not 256-byte aligned");
-    const int dt = w->dtype;
-    hipStream_t st = (hipStream_t)stream;
-    char* buf[4];
-    Carver ws(workspace, ws_bytes);
-    carve_basic(ws, basic_plan(w, n, h, wd), buf);
-    if ((rc = check_workspace(ws, "resnet_basic_forward")) != HIPT_OK) return rc;
-    ConvImg img[RN_MAX_CONVS];
-    Carver pk((void*)packed);
-    carve_packed(pk, nc, count, dt, img);
-    char *A = buf[0], *B = buf[1], *T = buf[2], *D = buf[3];
-
-    NormArgs nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
-    if (norm)
-        for (int c = 0; c < 3; ++c) nm.mean[c] = norm[c], nm.std[c] = norm[3 + c];
-    {
-        const int64_t npx = (int64_t)n * h * wd;
-        rc = dt == HIPT_BF16 ? launch_input<bf16_t>(x, input_kind, npx, (int64_t)h * wd, nm, (bf16_t*)T, st)
-                             : launch_input<float>(x, input_kind, npx, (int64_t)h * wd, nm, (float*)T, st);
-        if (rc != HIPT_OK) return rc;
-    }
-    // tile height: the rule (0) or 128 rows on every conv, as the caller's struct says; both give the same bits
-    const int rows = w->tile_rows;
-    auto conv = [&](int i, const void* in, int hh, int ww, const void* resid, int relu, void* o, int* oh, int* ow) -> int {
-        const NetConv& c = nc[i];
-        ConvArgs a = {};
-        a.x = in, a.wt = img[i].w, a.bias = img[i].bias, a.resid = resid, a.out = o;
-        a.n = n, a.h = hh, a.w = ww, a.cin = c.cin, a.cout = c.cout, a.kh = c.k, a.kw = c.k, a.stride = c.stride, a.pad = c.pad;
-        a.relu = relu;
-        const int r = run_conv(a, dt, st, rows);
-        *oh = a.oh, *ow = a.ow;
-        return r;
-    };
-    int hh, ww;
-    if ((rc = conv(0, T, h, wd, nullptr, 1, A, &hh, &ww)) != HIPT_OK) return rc;
-    if ((rc = run_maxpool(A, n, hh, ww, 64, B, dt, st)) != HIPT_OK) return rc;
-    hh = conv_out(hh, 3, 2, 1), ww = conv_out(ww, 3, 2, 1);
-    char *cur = B, *nxt = A;
-    int ci = 1, C = 64;
-    for (int L = 0, nl = basic_layers(w); L < nl; ++L) {
-        const int planes = 64 << L;
-        for (int b = 0; b < w->layers[L]; ++b) {
-            const bool ds = (L && b == 0) || C != planes;  // the rule of basic_convs / _make_layer
-            int h1, w1, h2, w2;
-            if ((rc = conv(ci, cur, hh, ww, nullptr, 1, T, &h1, &w1)) != HIPT_OK) return rc;
-            if (ds && (rc = conv(ci + 2, cur, hh, ww, nullptr, 0, D, &h2, &w2)) != HIPT_OK) return rc;
-            if ((rc = conv(ci + 1, T, h1, w1, ds ? (const void*)D : (const void*)cur, 1, nxt, &h2, &w2)) != HIPT_OK) return rc;
-            ci += ds ? 3 : 2;
-            C = planes, hh = h2, ww = w2;
-            char* t = cur;
-            cur = nxt, nxt = t;
-        }
-    }
-    return run_avgpool(cur, n, hh * ww, C, out, dt, st);
+    Net net;
+    const int rc = check_basic_weights(w, net);
+    return rc != HIPT_OK ? rc : net_forward(net, packed, x, input_kind, norm, n, h, wd, out, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

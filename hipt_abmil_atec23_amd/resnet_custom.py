@@ -72,11 +72,10 @@ def pack_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: int = N.HIPT_F32):
     return w, b
 
 
-def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, kernel_size: int, stride: int = 1, padding: int = 0,
-                resid: torch.Tensor = None, relu: bool = False, dtype: int = N.HIPT_F32) -> torch.Tensor:
-    """``relu?(conv2d(x) + bias (+ resid))`` on NHWC ``x [n, h, w, cin]`` with a packed weight (:func:`pack_conv_bn`); returns
-    ``[n, oh, ow, cout]`` in the compute dtype."""
-    N.require_cuda(x, "conv2d_nhwc")
+def _conv2d(who: str, entry: str, x, w_packed, bias, kernel_size, stride, padding, resid, relu, dtype, *tile_rows):
+    """The one body of :func:`conv2d_nhwc` (``hipt_conv2d``) and :func:`.resnet18.conv2d_nhwc_ex` (``hipt_conv2d_ex``, which
+    takes the tile height before the stream)."""
+    N.require_cuda(x, who)
     x = x.detach().to(Fn.torch_dtype(dtype)).contiguous()
     n, h, w, cin = x.shape
     cout = w_packed.shape[0]
@@ -84,10 +83,17 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, ker
     out = torch.empty((n, oh, ow, cout), dtype=x.dtype, device=x.device)
     r = None if resid is None else resid.detach().to(x.dtype).contiguous()
     if r is not None and tuple(r.shape) != tuple(out.shape):
-        raise ValueError(f"conv2d_nhwc: residual {tuple(r.shape)} does not match the output {tuple(out.shape)}")
-    N.call("hipt_conv2d", N.ptr(x), n, h, w, cin, N.ptr(w_packed), N.ptr(bias), cout, kernel_size, kernel_size, stride, padding,
-           N.ptr(r), int(relu), N.ptr(out), dtype, N.stream_ptr(x.device))
+        raise ValueError(f"{who}: residual {tuple(r.shape)} does not match the output {tuple(out.shape)}")
+    N.call(entry, N.ptr(x), n, h, w, cin, N.ptr(w_packed), N.ptr(bias), cout, kernel_size, kernel_size, stride, padding,
+           N.ptr(r), int(relu), N.ptr(out), dtype, *tile_rows, N.stream_ptr(x.device))
     return out
+
+
+def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, kernel_size: int, stride: int = 1, padding: int = 0,
+                resid: torch.Tensor = None, relu: bool = False, dtype: int = N.HIPT_F32) -> torch.Tensor:
+    """``relu?(conv2d(x) + bias (+ resid))`` on NHWC ``x [n, h, w, cin]`` with a packed weight (:func:`pack_conv_bn`); returns
+    ``[n, oh, ow, cout]`` in the compute dtype."""
+    return _conv2d("conv2d_nhwc", "hipt_conv2d", x, w_packed, bias, kernel_size, stride, padding, resid, relu, dtype)
 
 
 def maxpool_nhwc(x: torch.Tensor, dtype: int = N.HIPT_F32) -> torch.Tensor:
@@ -144,32 +150,31 @@ class Bottleneck_Baseline(nn.Module):
         return conv2d_nhwc(t, w3, b3, 1, resid=r, relu=True).permute(0, 3, 1, 2)
 
 
-class _PackedResnet:
-    """Device-side image of one ResNet_Baseline for one compute dtype: BN-folded weights (``hipt_resnet_pack_weights``) plus
-    the ctypes structs that describe them.  Rebuilt when a parameter or running statistic changes."""
+class _PackedNet:
+    """Device-side image of one extractor for one compute dtype: BN-folded weights (``<entry>_pack_weights``) plus the ctypes
+    structs that describe them.  Rebuilt when a parameter or running statistic changes."""
 
-    def __init__(self, model, code: int, dev):
+    def __init__(self, model, code: int, dev, fields: dict):
         keep = []
+        layers = [getattr(model, name) for name in model._LAYERS]
         convs = [(model.conv1, model.bn1)]
-        for layer in (model.layer1, model.layer2, model.layer3):
-            for blk in layer:
-                convs += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)]
+        for layer in layers:
+            for blk in layer:   # state-dict order: conv1.. of the block, then its downsample
+                convs += [(getattr(blk, f"conv{i}"), getattr(blk, f"bn{i}")) for i in (1, 2, 3) if hasattr(blk, f"conv{i}")]
                 if blk.downsample is not None:
                     convs.append((blk.downsample[0], blk.downsample[1]))
         self.convs = (N.ConvBN * len(convs))(*[_conv_bn_struct(c, b, keep) for c, b in convs])
-        w = N.ResnetWeights()
-        w.dtype = code
-        for i, layer in enumerate((model.layer1, model.layer2, model.layer3)):
+        w = model._WEIGHTS(dtype=code, n_convs=len(convs), **fields)
+        for i, layer in enumerate(layers):
             w.layers[i] = len(layer)
         w.convs = C.cast(self.convs, C.POINTER(N.ConvBN))
-        w.n_convs = len(convs)
         self.w = w
-        nbytes = N.lib().hipt_resnet_packed_bytes(C.byref(w))
+        nbytes = getattr(N.lib(), model._ENTRY + "_packed_bytes")(C.byref(w))
         if not nbytes:
-            raise ValueError("ResNet_Baseline: this layer configuration is outside the library's network "
+            raise ValueError(f"{type(model).__name__}: this layer configuration is outside the library's network "
                              f"({N.lib().hipt_last_error().decode(errors='replace')})")
         self.image = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        N.call("hipt_resnet_pack_weights", C.byref(w), N.ptr(self.image), N.stream_ptr(dev))
+        N.call(model._ENTRY + "_pack_weights", C.byref(w), N.ptr(self.image), N.stream_ptr(dev))
         self.keep = keep  # the fp32 sources stay alive until the packing kernels (enqueued above) have read them
 
     @property
@@ -177,21 +182,28 @@ class _PackedResnet:
         return C.byref(self.w)
 
 
-class ResNet_Baseline(WeightImageCache, nn.Module):
+class _ResNetHost(WeightImageCache, nn.Module):
+    """What the extractors share: the modules that hold the parameters, the settings, the weight image and the one library call
+    that runs stem, maxpool, the layers and the average pool.  A subclass states what differs."""
     _image_buffers = True  # the BN running statistics are folded into the image with the parameters
+    _LAYERS = ()           # attribute names of the layers the network runs
+    _WEIGHTS = None        # ctypes struct the library takes
+    _ENTRY = ""            # entry-point family: <_ENTRY>_packed_bytes / _pack_weights / _workspace_bytes / _forward
+    _SLOT = ""             # workspace slot name
+    FEATURES = 0           # width of the pooled features
 
-    def __init__(self, block, layers):
+    def _build(self, block, layers):
+        """stem, maxpool, one layer per name in ``_LAYERS`` (64, 128, ... planes, stride 2 from the second on), average pool"""
         self.inplanes = 64
-        super(ResNet_Baseline, self).__init__()
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
-        self.layer1 = self._make_layer(block, 64, layers[0])
-        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
-        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
+        for i, name in enumerate(self._LAYERS):
+            setattr(self, name, self._make_layer(block, 64 << i, layers[i], stride=2 if i else 1))
         self.avgpool = nn.AdaptiveAvgPool2d(1)
 
+    def _init_weights(self):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
@@ -232,15 +244,21 @@ class ResNet_Baseline(WeightImageCache, nn.Module):
         return self.conv1.weight.device
 
     def _check_inference_only(self):
+        name = type(self).__name__
         if self.training:
-            raise RuntimeError("ResNet_Baseline HIP forward: BatchNorm in train() mode needs batch statistics (inference kernels "
+            raise RuntimeError(f"{name} HIP forward: BatchNorm in train() mode needs batch statistics (inference kernels "
                                "only); call .eval()")
-        self._warn_no_grad_fn("HIP ResNet_Baseline forward returns tensors without grad_fn: no gradient flows into the extractor "
+        self._warn_no_grad_fn(f"HIP {name} forward returns tensors without grad_fn: no gradient flows into the extractor "
                               "weights (the reference uses it as a frozen feature extractor)")
 
-    def _packed_for(self, dev) -> _PackedResnet:
+    def _struct_fields(self) -> dict:
+        """Fields of ``_WEIGHTS`` beyond dtype, layers and convs; they are part of the image's cache key."""
+        return {}
+
+    def _packed_for(self, dev) -> _PackedNet:
         self._check_inference_only()
-        return self._cached(dev, (), lambda code: _PackedResnet(self, code, dev))
+        fields = self._struct_fields()
+        return self._cached(dev, tuple(fields.values()), lambda code: _PackedNet(self, code, dev, fields))
 
     # ---- forward ------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -249,26 +267,42 @@ class ResNet_Baseline(WeightImageCache, nn.Module):
             return N.RESNET_IN_U8_HWC if (x.dim() == 4 and x.shape[-1] == 3 and x.shape[1] != 3) else N.RESNET_IN_U8
         return N.RESNET_IN_F32
 
-    def forward(self, x):
-        """``[B, 1024]`` fp32 features of ``[B, 3, H, W]`` float (normalised) or uint8 (``[B, 3, H, W]`` / ``[B, H, W, 3]``)."""
-        N.require_cuda(x, type(self).__name__)
+    def _pooled(self, x):
+        """``[B, FEATURES]`` fp32 of ``[B, 3, H, W]`` float (normalised) or uint8 (``[B, 3, H, W]`` / ``[B, H, W, 3]``): the
+        network up to and including the average pool, one library call."""
+        name = type(self).__name__
+        N.require_cuda(x, name)
         kind = self._input_kind(x)
         if x.dim() != 4 or (x.shape[-1] if kind == N.RESNET_IN_U8_HWC else x.shape[1]) != 3:
-            raise ValueError(f"ResNet_Baseline: expected [B,3,H,W] (or uint8 [B,H,W,3]) images, got {tuple(x.shape)}")
+            raise ValueError(f"{name}: expected [B,3,H,W] (or uint8 [B,H,W,3]) images, got {tuple(x.shape)}")
         dev = x.device
-        N.same_device(type(self).__name__, self.weight_device, x)
+        N.same_device(name, self.weight_device, x)
         pk = self._packed_for(dev)
         x = x.detach().contiguous() if kind != N.RESNET_IN_F32 else x.detach().float().contiguous()
         B = x.shape[0]
         H, W = (x.shape[1], x.shape[2]) if kind == N.RESNET_IN_U8_HWC else (x.shape[2], x.shape[3])
-        out = torch.empty((B, 4 * 256), dtype=torch.float32, device=dev)
-        need = N.lib().hipt_resnet_workspace_bytes(pk.ref, B, H, W)
+        out = torch.empty((B, self.FEATURES), dtype=torch.float32, device=dev)
+        need = getattr(N.lib(), self._ENTRY + "_workspace_bytes")(pk.ref, B, H, W)
         # one scratch per stream: two streams driving the model at once never share activations
-        ws = Fn.workspace(dev, need, slot=("resnet", torch.cuda.current_stream(dev).cuda_stream))
+        ws = Fn.workspace(dev, need, slot=(self._SLOT, torch.cuda.current_stream(dev).cuda_stream))
         norm = (C.c_float * 6)(*self._norm)
-        N.call("hipt_resnet_forward", pk.ref, N.ptr(pk.image), N.ptr(x), kind, C.cast(norm, C.c_void_p), B, H, W, N.ptr(out),
+        N.call(self._ENTRY + "_forward", pk.ref, N.ptr(pk.image), N.ptr(x), kind, C.cast(norm, C.c_void_p), B, H, W, N.ptr(out),
                N.ptr(ws), ws.numel(), N.stream_ptr(dev))
         return out
+
+
+class ResNet_Baseline(_ResNetHost):
+    _LAYERS = ("layer1", "layer2", "layer3")   # layers[3] of the reference's call is not built there either
+    _WEIGHTS, _ENTRY, _SLOT, FEATURES = N.ResnetWeights, "hipt_resnet", "resnet", 1024
+
+    def __init__(self, block, layers):
+        super(ResNet_Baseline, self).__init__()
+        self._build(block, layers)
+        self._init_weights()
+
+    def forward(self, x):
+        """``[B, 1024]`` fp32 features of ``[B, 3, H, W]`` float (normalised) or uint8 (``[B, 3, H, W]`` / ``[B, H, W, 3]``)."""
+        return self._pooled(x)
 
 
 def resnet18_baseline(pretrained=False, dataset='ImageNet'):

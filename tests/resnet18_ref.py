@@ -14,6 +14,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from hipt_abmil_atec23_amd import synth
+from resnet_ref import conv_bn as _conv_bn  # noqa: F401  (eval-mode conv + BN in float64; the tests use it as R._conv_bn)
+from resnet_ref import normalized  # noqa: F401  (ToTensor + Normalize of uint8 [B, 3, H, W] in fp32 ops)
 
 LAYERS = (2, 2, 2, 2)
 # (name, batch, H, W, pixel seed): 32 x 32 ends in a 1 x 1 map (the average pool sums one value)
@@ -40,13 +42,6 @@ def state_dict():
 
 def pixels(b, h, w, seed):
     return synth.hash_u8_np((b, 3, h, w), seed)
-
-
-def normalized(u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)) -> torch.Tensor:
-    """ToTensor + Normalize of uint8 [B, 3, H, W] in fp32 ops"""
-    x = torch.as_tensor(u8).float().div(255)
-    return x.sub(torch.tensor(mean, dtype=torch.float32, device=x.device)[:, None, None]).div(
-        torch.tensor(std, dtype=torch.float32, device=x.device)[:, None, None])
 
 
 # ---- statement 1: stock torch.nn modules ---------------------------------------------------------------------------------
@@ -91,12 +86,6 @@ class TorchResNet18(nn.Module):
 
 
 # ---- statement 2: functional, float64 ------------------------------------------------------------------------------------
-def _conv_bn(x, sd, conv, bn, stride=1, pad=0, eps=1e-5):
-    d = lambda k: sd[k].double()
-    y = F.conv2d(x, d(conv + ".weight"), stride=stride, padding=pad)
-    return F.batch_norm(y, d(bn + ".running_mean"), d(bn + ".running_var"), d(bn + ".weight"), d(bn + ".bias"), False, 0.0, eps)
-
-
 def forward_fp64(sd, x, layers=LAYERS) -> torch.Tensor:
     """[B, 512] float64 features (before fc) of x [B, 3, H, W]"""
     x = F.max_pool2d(F.relu(_conv_bn(x.double(), sd, "conv1", "bn1", 2, 3)), 3, 2, 1)

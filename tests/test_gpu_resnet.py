@@ -61,6 +61,35 @@ def _pixels(b, h, w, seed):
     return synth.hash_u8_np((b, 3, h, w), seed)
 
 
+# ---- a layer table whose block input / output parity differs from the default ------------------------------------------------
+ODD_LAYERS = (1, 2, 1)   # a one-block layer flips which of the two buffers is "current" when the next layer starts
+
+
+@pytest.fixture(scope="module")
+def odd_net():
+    """(model, state dict): hash weights and running statistics (means within +-0.1, variances in [0.5, 1.5])"""
+    specs = synth.resnet_param_specs(ODD_LAYERS)
+    for _, bn, cout, _, _ in synth.resnet_conv_bn_names(ODD_LAYERS):
+        specs[bn + ".running_mean"], specs[bn + ".running_var"] = ((cout,), 0.1, 0.0), ((cout,), 0.5, 1.0)
+    sd = synth.make_state_dict(specs)
+    m = rc.ResNet_Baseline(rc.Bottleneck_Baseline, list(ODD_LAYERS))
+    m.load_state_dict(sd, strict=False)
+    return m.eval().to(DEV).set_compute_dtype("fp32"), sd
+
+
+@pytest.mark.parametrize("b,h,w", [(1, 32, 32), (2, 64, 32)], ids=lambda v: str(v))
+def test_other_layer_table_against_the_fp64_restatement(odd_net, b, h, w):
+    m, sd = odd_net
+    x = R.normalized(_pixels(b, h, w, 301 + h))
+    with _Calls(), torch.no_grad():
+        got = m(x.to(DEV)).cpu().numpy()
+    ref = R.forward_fp64(sd, x, ODD_LAYERS).numpy()
+    err = float(np.abs(got - ref).max())
+    print(f"resnet {ODD_LAYERS} fp32 {b}x{h}x{w}: max|d| {err:.3e} (|ref|max {np.abs(ref).max():.3f})")
+    assert got.shape == ref.shape == (b, 1024) and float(np.abs(ref).max()) > 1e-2
+    assert err <= 1e-4 * max(1.0, float(np.abs(ref).max())), err
+
+
 # ---- units -------------------------------------------------------------------------------------------------------------
 def _conv_bn(cin, cout, k, stride, pad, seed):
     conv = torch.nn.Conv2d(cin, cout, k, stride, pad, bias=False)

@@ -198,6 +198,32 @@ def test_network_against_the_restatements(model, refs, dtype, case):
     assert e_ref <= BF16_VS_FP64, e_ref
 
 
+ODD_LAYERS = (1, 2, 1, 2)   # a one-block layer flips which of the two buffers is "current" when the next layer starts
+
+
+@pytest.fixture(scope="module")
+def odd_net():
+    sd = synth.make_state_dict(synth.resnet18_param_specs(ODD_LAYERS))
+    m = r18.ResNet18_Baseline(layers=ODD_LAYERS)
+    m.load_state_dict(sd, strict=False)
+    m.fc = torch.nn.Sequential()
+    return m.eval().to(DEV).set_compute_dtype("fp32"), sd
+
+
+@pytest.mark.parametrize("b,h,w", [(1, 32, 32), (2, 64, 32)], ids=lambda v: str(v))
+def test_other_layer_table_against_the_fp64_restatement(odd_net, b, h, w):
+    """32 x 32 ends in a 1 x 1 map; the non-square input tells h from w in the driver's walk"""
+    m, sd = odd_net
+    x = R.normalized(R.pixels(b, h, w, 311 + h))
+    with _Calls(), torch.no_grad():
+        got = m(x.to(DEV)).cpu().numpy()
+    ref = R.forward_fp64(sd, x, ODD_LAYERS).numpy()
+    err = float(np.abs(got - ref).max())
+    print(f"resnet18 {ODD_LAYERS} fp32 {b}x{h}x{w}: max|d| {err:.3e} (|ref|max {np.abs(ref).max():.3f})")
+    assert got.shape == ref.shape == (b, 512) and float(np.abs(ref).max()) > 1e-2
+    assert err <= 1e-4 * max(1.0, float(np.abs(ref).max())), err
+
+
 def test_fc_is_applied_as_the_module_holds_it(sd, refs):
     name, b, h, w, seed = R.CASES[0]
     x = R.normalized(R.pixels(b, h, w, seed)).to(DEV)

@@ -12,6 +12,7 @@ import torch
 
 from conftest import ROOT
 from hipt_abmil_atec23_amd import _native as N
+from hipt_abmil_atec23_amd import synth
 
 CSRC = os.path.join(ROOT, "hipt_abmil_atec23_amd", "csrc")
 FAKE = 1 << 20            # a non-null, 4 KiB-aligned address that no call dereferences before its workspace check
@@ -120,6 +121,51 @@ def test_clam_train_workspace_is_the_sum_of_its_three_rounded_arrays(n, sizes, n
     assert got == sum(al(p) for p in parts)
     assert got % 256 == 0 and sum(parts) <= got < sum(parts) + 768
     assert f"TR = {TR};" in open(os.path.join(CSRC, "clam_train.hip")).read()
+
+
+# ---- the ResNet drivers, layer tables other than the default ones ------------------------------------------------------------------
+def net_weights(family, layers, dtype):
+    """hipt_resnet_weights ("resnet") / hipt_resnet_basic_weights ("resnet_basic") of a layer table, fake addresses"""
+    names = synth.resnet_conv_bn_names(layers) if family == "resnet" else synth.resnet18_conv_bn_names(layers)
+    arr = (N.ConvBN * len(names))()
+    for c, (_, _, cout, cin, k) in zip(arr, names):
+        c.weight = c.bn_weight = c.bn_bias = c.bn_mean = c.bn_var = FAKE
+        c.cin, c.cout, c.kh, c.kw, c.bn_eps = cin, cout, k, k, 1e-5
+    w = (N.ResnetWeights if family == "resnet" else N.ResnetBasicWeights)(dtype=dtype, n_convs=len(names))
+    w.layers[:] = list(layers) + [0] * (len(w.layers) - len(layers))
+    w.convs = C.cast(arr, C.POINTER(N.ConvBN))
+    w._keep = arr
+    return w
+
+
+NET_SHAPES = ((1, 32, 32), (2, 64, 96), (3, 224, 224))
+# (family, layer table, dtype) -> (packed bytes, workspace bytes at NET_SHAPES), read from a build of the commit before the two
+# drivers became one.  A block's output sizes both block input / output buffers, so the workspace does not follow the parity of the
+# table ((1, 1, 1) needs what (3, 4, 6) needs), and a BasicBlock table without a downsample still carves 256 bytes for it.
+NET_BYTES = {
+    ("resnet", (1, 1, 1), "fp32"): (7890688, (245760, 2949120, 36126720)),
+    ("resnet", (1, 1, 1), "bf16"): (3958528, (122880, 1474560, 18063360)),
+    ("resnet", (2, 1, 3), "fp32"): (17095936, (245760, 2949120, 36126720)),
+    ("resnet", (2, 1, 3), "bf16"): (8568064, (122880, 1474560, 18063360)),
+    ("resnet", (3, 4, 6), "fp32"): (34115328, (245760, 2949120, 36126720)),
+    ("resnet", (3, 4, 6), "bf16"): (17092352, (122880, 1474560, 18063360)),
+    ("resnet_basic", (1,), "fp32"): (336640, (98560, 1179904, 14450944)),
+    ("resnet_basic", (1,), "bf16"): (172800, (49408, 590080, 7225600)),
+    ("resnet_basic", (1, 2, 1, 2), "fp32"): (39674112, (106496, 1277952, 15654912)),
+    ("resnet_basic", (1, 2, 1, 2), "bf16"): (19849472, (53248, 638976, 7827456)),
+    ("resnet_basic", (2, 2, 2), "fp32"): (11125504, (106496, 1277952, 15654912)),
+    ("resnet_basic", (2, 2, 2), "bf16"): (5571328, (53248, 638976, 7827456)),
+    ("resnet_basic", (3, 4, 6, 3), "fp32"): (85107968, (106496, 1277952, 15654912)),
+    ("resnet_basic", (3, 4, 6, 3), "bf16"): (42575104, (53248, 638976, 7827456)),
+}
+
+
+@pytest.mark.parametrize("family,layers,dtype", sorted(NET_BYTES), ids=lambda v: str(v).replace(" ", ""))
+def test_resnet_sizes_of_other_layer_tables_are_those_of_the_two_drivers(family, layers, dtype):
+    lib = N.lib()
+    w = net_weights(family, layers, DTYPES[dtype])
+    packed, workspace = (getattr(lib, f"hipt_{family}_{what}_bytes") for what in ("packed", "workspace"))
+    assert (packed(C.byref(w)), tuple(workspace(C.byref(w), *s) for s in NET_SHAPES)) == NET_BYTES[family, layers, dtype]
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------
