@@ -9,9 +9,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import clam_train_ref as R
 from conftest import golden
 from hipt_abmil_atec23_amd import _native as N
 from hipt_abmil_atec23_amd import synth
+from test_clam_train_ref import BARS
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,6 +34,25 @@ def md(a, b):
     a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     b = b.detach().float().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)
     return float(np.max(np.abs(a.astype(np.float64) - b.astype(np.float64)))) if a.size else 0.0
+
+
+def assert_rel_l2(grads, ref, size, base, ncls, multi, k, subtyping, inst, h_cpu, label, masks=None):
+    """Every gradient within the relative bars of tests/test_clam_train_ref.py (8 x the fp32 noise floor; `ref` is fp32 autograd, which
+    sits at that floor): rel-L2 per tensor, and max |g| under the absolute bar where the true gradient is zero (attention_c.bias under
+    this plain loss, the instance classifiers of classes the step does not evaluate).  grads / ref: name -> tensor / array."""
+    n = h_cpu.shape[0]
+    case = R.Case("test_gpu_train", tuple(size), n, multi, ncls, k, subtyping, inst, "std", masks is not None, False)
+    pn = synth.make_params_np(synth.clam_param_specs(size, n_classes=ncls, multi=multi, dropout=masks is not None), base)
+    inp = R.Inputs(case, pn, h_cpu, masks, None, None, label)
+    bars, zero_bar = BARS[R.group_of(case)], R.abs_bar(R.truth(inp)[2])
+    for key, g in grads.items():
+        g64 = g.detach().double().cpu().numpy()
+        if R.zero_truth(inp, key):
+            assert float(np.abs(g64).max()) < zero_bar, (key, float(np.abs(g64).max()), zero_bar)
+        else:
+            r64 = np.asarray(ref[key].detach().cpu().numpy() if torch.is_tensor(ref[key]) else ref[key], np.float64)
+            e = float(np.linalg.norm(g64 - r64) / np.linalg.norm(r64))
+            assert e < bars[R.kind_of(key)], (key, e, bars[R.kind_of(key)])
 
 
 def make(size, base, ncls, multi, k, subtyping, dropout=0.0):
@@ -73,6 +94,8 @@ def test_train_step_vs_reference_gradients(name, size, base, shape, seed, label,
         worst = max(worst, e)
         assert gr.shape == p.shape and e < TOL, (key, e)
     print(f"{name}: max |grad - reference| = {worst:.1e}")
+    assert_rel_l2({key: (p.grad if p.grad is not None else torch.zeros_like(p)) for key, p in m.named_parameters()},
+                  {key: g["grad." + key] for key, _ in m.named_parameters()}, size, base, ncls, multi, k, subtyping, inst, h.cpu(), label)
 
 
 def _oracle_step(size, base, ncls, multi, h_cpu, label, k, inst, subtyping, masks=None, dropout=False):
@@ -98,6 +121,9 @@ def test_train_step_with_dropout_masks_and_bag_gradient():
     for key, p in m.named_parameters():
         assert md(p.grad if p.grad is not None else torch.zeros_like(p), grads[key]) < TOL, key
     assert h.grad is not None and md(h.grad, grads["bag"]) < TOL  # d loss / d bag
+    got = {key: (p.grad if p.grad is not None else torch.zeros_like(p)) for key, p in m.named_parameters()}
+    got["bag"] = h.grad
+    assert_rel_l2(got, grads, size, 192, 2, False, 8, False, True, h.detach().cpu(), 1, masks=[t.cpu() for t in masks])
     m.eval()  # eval: no masks, the inference kernels again
     with torch.no_grad():
         lg2 = m(h.detach())[0]
@@ -119,6 +145,8 @@ def test_train_step_vs_oracle_other_shapes(size, base, n, ncls, multi, k):
         gr = p.grad if p.grad is not None else torch.zeros_like(p)
         ref = grads[key]
         assert md(gr, ref) < max(TOL, 1e-5 * float(ref.abs().max())), (key, md(gr, ref))
+    assert_rel_l2({key: (p.grad if p.grad is not None else torch.zeros_like(p)) for key, p in m.named_parameters()}, grads,
+                  size, base, ncls, multi, k, True, True, h.cpu(), ncls - 1)
 
 
 def rel_l2(a, b):
