@@ -1159,6 +1159,55 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
     return HIPT_OK;
 }
 
+// ---- B bags in one call (abmil_bags.hip): unit table | tile_start | one partial per unit; no state ----
+int hipt_clam_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && w->s0 > 0 && hipt_clam_fused_supported(w) ? 1 : 0; }
+
+// units of a call: sum_b ceil(N_b / 128) <= total_rows / 128 + B, known without reading the offsets back
+static int64_t clam_bags_max_units(int B, int64_t total_rows) { return (total_rows + 127) / 128 + B; }
+struct ClamBagsWs { void* units; int* tile_start; float* partials; };
+static ClamBagsWs carve_clam_bags(Carver& c, const hipt_clam_weights* w, int B, int64_t total_rows) {
+    const size_t nu = (size_t)clam_bags_max_units(B, total_rows);
+    ClamBagsWs k;
+    k.units = c.take(nu * hipt_clam_bags_unit_bytes());
+    k.tile_start = c.take<int>((size_t)B + 1);
+    k.partials = c.take<float>(nu * (2 + (size_t)w->s1));
+    return k;
+}
+
+size_t hipt_clam_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows) {
+    if (!hipt_clam_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
+    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows); });
+}
+
+int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                              int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat, void* workspace,
+                              size_t ws_bytes, void* stream) {
+    int rc = check_clam(w);
+    if (rc) return rc;
+    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "clam_sb_forward_bags: null argument");
+    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "clam_sb_forward_bags: null output");
+    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "clam_sb_forward_bags: bags must be 16-byte aligned");
+    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "clam_sb_forward_bags: B = %d bags need at least one row each (total_rows = %lld)", B,
+                   (long long)total_rows);
+    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "clam_sb_forward_bags: %lld rows in %d bags exceed 2^31 tiles",
+                   (long long)total_rows, B);
+    if (!hipt_clam_bags_supported(w)) {
+        hipt_set_error("clam_sb_forward_bags: no multi-bag form for [%d,%d,%d] in this dtype: call hipt_clam_sb_forward per bag", w->s0, w->s1,
+                       w->s2);
+        return HIPT_E_UNSUPPORTED;
+    }
+    Carver c(workspace, ws_bytes);
+    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows);
+    if (check_workspace(c, "clam_sb_forward_bags")) return HIPT_E_BADARG;  // this entry point's contract: a short buffer is a bad argument
+    hipStream_t st = S(stream);
+    const int nu = (int)clam_bags_max_units(B, total_rows);
+    PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
+    PROF(PC_ABMIL, hipt_clam_bags_tiles_launch(w, bags, k.units, nu, attention_only, A_raw, k.partials, st));
+    if (attention_only) return HIPT_OK;
+    PROF(PC_COMBINE, hipt_clam_bags_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
+    return HIPT_OK;
+}
+
 int hipt_clam_mb_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_mb_stream_supported(w) ? 1 : 0; }
 
 // ticket | partials of <= 128 workgroups x 4 branches | h1 as a bf16 image

@@ -127,7 +127,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 // host side -------------------------------------------------------------------------------
 void hipt_set_error(const char* fmt, ...);
 
-// The library reads SEVEN environment switches, all for debugging / A-B runs (README.md):
+// The library reads EIGHT environment switches, all for debugging / A-B runs (README.md):
 //   HIPT_GENERIC=1        every operator takes its generic kernel (no streaming / packed-weight kernels)
 //   HIPT_NO_IMG=1         no activation images / head-major qkv between the streaming kernels
 //   HIPT_NO_PRUNE=1       the last ViT-256 block runs in full instead of for the [CLS] rows only
@@ -135,6 +135,7 @@ void hipt_set_error(const char* fmt, ...);
 //   HIPT_NO_PROJ_FOLD=1   the attention block's output projection runs as its own kernel instead of at the head of the fused MLP's tiles
 //   HIPT_NO_CLS_ABSORB=1  the [CLS]-pruned last block projects K and V for every token (the fused kernel's CLSONLY form) instead of absorbing them
 //   HIPT_NO_EMBED_LN=1    the patch embedding writes row-major tokens only; the first block applies its own LayerNorm-1 (LN-in-GEMM + two-kernel attention)
+//   HIPT_BAGS_MAX_WG=n    the multi-bag CLAM tile pass launches at most n workgroups (abmil_bags.hip; the results do not depend on it)
 // read per call (cheap: host side, a handful of calls per forward), so a test may flip them inside one process.
 #include <stdlib.h>
 inline bool hipt_env_on(const char* name) {

@@ -218,6 +218,16 @@ int hipt_pool_launch(const float* A, const float* h1, int N, int S1, float* gmax
                      hipStream_t st);
 int hipt_gather_h1_launch(const hipt_clam_weights* w, const void* bag, const int64_t* idx, int n_idx, float* out,
                           hipStream_t st);
+// ragged multi-bag CLAM_SB (abmil_bags.hip): offsets -> unit table (one unit = one 128-row tile of one bag; `units` holds max_units entries of
+// hipt_clam_bags_unit_bytes(), tile_start B+1 ints), the tile pass over the units, the per-bag combine.  Widths: hipt_clam_fused_supported.
+size_t hipt_clam_bags_unit_bytes();
+int hipt_clam_bags_units_launch(const int64_t* offsets, int B, int64_t total_rows, int max_units, int* tile_start, void* units,
+                                hipStream_t st);
+int hipt_clam_bags_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
+                                int attention_only, float* A_raw, float* partials, hipStream_t st);
+int hipt_clam_bags_combine_launch(const float* partials, const int* tile_start, int max_units, int B,
+                                  const hipt_clam_weights* w, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                  hipStream_t st);
 
 // ---- bootstrapped evaluation metrics (bootstrap.hip) ----
 size_t hipt_bootstrap_lds_bytes(int n);

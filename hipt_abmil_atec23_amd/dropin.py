@@ -136,6 +136,42 @@ def _uninstall_heatmaps():
         cls.visHeatmap = prev
 
 
+_EVAL_MOD = "utils.eval_utils"
+
+
+def _install_evaluation(verbose: bool) -> bool:
+    """Bind ``evaluate.summary_like`` as ``utils.eval_utils.summary`` (opt-in): the split goes through ``forward_bags`` in a few
+    calls instead of one forward per slide.  False, and nothing done, where the reference's module does not import (its AUC, data
+    frame and logger come from that module's own imports)."""
+    from . import evaluate
+    if _EVAL_MOD in _saved:
+        return True
+    try:
+        if _EVAL_MOD not in sys.modules and importlib.util.find_spec(_EVAL_MOD) is None:
+            return False
+        mod = importlib.import_module(_EVAL_MOD)
+    except Exception:   # no reference checkout on sys.path, or sklearn / pandas / ... missing
+        return False
+    _saved[_EVAL_MOD] = mod.__dict__.get("summary")
+    mod.summary = evaluate.summary_like(mod)
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_EVAL_MOD}.summary -> {evaluate.__name__}.evaluate_split")
+    return True
+
+
+def _uninstall_evaluation():
+    if _EVAL_MOD not in _saved:
+        return
+    prev = _saved.pop(_EVAL_MOD)
+    mod = sys.modules.get(_EVAL_MOD)
+    if mod is None:
+        return
+    if prev is None:
+        del mod.summary
+    else:
+        mod.summary = prev
+
+
 _RESNET18_MOD, _RESNET18_NAME = "models.resnet_custom", "resnet18_baseline"
 _RESNET18_KEY = _RESNET18_MOD + "." + _RESNET18_NAME
 
@@ -185,13 +221,15 @@ def _uninstall_resnet18():
         setattr(mod, _RESNET18_NAME, prev)
 
 
-def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False):
+def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False,
+            evaluation: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
     ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
     ``heatmaps=True`` also binds ``WholeSlideImage.visHeatmap`` where the reference's ``wsi_core`` imports (else a no-op).
     ``resnet18=True`` also binds ``models.resnet_custom.resnet18_baseline`` to ``resnet18.resnet18_baseline`` (the HistoResNet-18
-    extractor), on the module ``resnet=True`` mapped or on the reference's own."""
+    extractor), on the module ``resnet=True`` mapped or on the reference's own.
+    ``evaluation=True`` also binds ``utils.eval_utils.summary`` to ``evaluate.evaluate_split`` where that module imports (else a no-op)."""
     done = {}
     if heatmaps and _install_heatmaps(verbose):
         done[_WSI_MOD + ".WholeSlideImage.visHeatmap"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.vis_heatmap"
@@ -230,10 +268,13 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False,
             print(f"[hipt_abmil_atec23_amd] {ref_name} -> {mod.__name__}")
     if resnet18 and _install_resnet18(verbose):
         done[_RESNET18_KEY] = f"{pkg}.resnet18.resnet18_baseline"
+    if evaluation and _install_evaluation(verbose):
+        done[_EVAL_MOD + ".summary"] = f"{pkg}.evaluate.evaluate_split"
     return done
 
 
 def uninstall():
+    _uninstall_evaluation()
     _uninstall_resnet18()
     _uninstall_sampling()
     _uninstall_heatmaps()

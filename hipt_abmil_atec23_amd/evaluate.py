@@ -1,0 +1,142 @@
+"""The numeric part of the reference's ``summary()`` (utils/eval_utils.py:115-179) over a whole split, with the model called on
+many slides at once (``CLAM_SB.forward_bags``) instead of once per slide.
+
+``evaluate_split`` returns what ``summary()`` accumulates: the probabilities, labels and predictions of every slide, the mean
+error, the mean loss and the per-class correct / count pairs of ``Accuracy_Logger`` (utils/core_utils.py:17-49).  The AUC stays with
+the caller: its inputs are exactly ``all_labels`` and ``all_probs`` (``bootstrap`` computes it on the device).  Every figure is a
+function of the per-slide logits alone and those do not depend on how the split is cut into calls, so neither do the results.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+DEFAULT_MAX_ROWS = 1 << 16
+
+
+@dataclass
+class SplitResult:
+    all_probs: np.ndarray        # [n, C] float64 (summary(): np.zeros((len(loader), n_classes)))
+    all_labels: np.ndarray       # [n] float64
+    all_preds: np.ndarray        # [n] float64
+    error: float                 # mean of calculate_error(Y_hat, label) (utils/utils.py:202-205)
+    loss: float                  # mean of loss_fn(logits_b, label_b).item()
+    acc: List[dict] = field(default_factory=list)   # Accuracy_Logger.data: [{"count", "correct"}] per class
+
+    def class_accuracy(self, c: int):
+        """``Accuracy_Logger.get_summary(c)``: (accuracy or None, correct, count)."""
+        d = self.acc[c]
+        return (float(d["correct"]) / d["count"] if d["count"] else None), d["correct"], d["count"]
+
+
+def chunk_bags(rows: Sequence[int], max_rows_per_call: int) -> List[range]:
+    """Consecutive runs of bags whose row counts add up to at most ``max_rows_per_call`` (a larger bag is a run of its own)."""
+    if max_rows_per_call < 1:
+        raise ValueError(f"max_rows_per_call must be positive, got {max_rows_per_call}")
+    runs, start, acc = [], 0, 0
+    for i, n in enumerate(rows):
+        if i > start and acc + n > max_rows_per_call:
+            runs.append(range(start, i))
+            start, acc = i, 0
+        acc += n
+    if len(rows) > start:
+        runs.append(range(start, len(rows)))
+    return runs
+
+
+def _split(bags_or_loader, labels):
+    """(list of [N_b, S0] tensors, list of int labels) from a sequence of bags plus labels, or from a loader of (bag, label) pairs."""
+    if labels is None:
+        pairs = list(bags_or_loader)
+        bags, labels = [p[0] for p in pairs], [p[1] for p in pairs]
+    else:
+        bags = list(bags_or_loader)
+    labels = [int(l.reshape(-1)[0]) if isinstance(l, torch.Tensor) else int(l) for l in (labels.tolist() if isinstance(labels, (torch.Tensor, np.ndarray)) else labels)]
+    if len(bags) != len(labels):
+        raise ValueError(f"{len(bags)} bags but {len(labels)} labels")
+    if not bags:
+        raise ValueError("evaluate_split: empty split")
+    return [b.reshape(-1, b.shape[-1]) for b in bags], labels
+
+
+def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS) -> SplitResult:
+    """Evaluate ``model`` on every bag of a split.  ``bags_or_loader``: a sequence of ``[N_b, S0]`` tensors with ``labels``, or an
+    iterable of ``(bag, label)`` pairs (a batch-size-1 loader) with ``labels=None``.  The bags go to the model's device and through
+    ``model.forward_bags`` in runs of at most ``max_rows_per_call`` rows (a model without ``forward_bags`` is called bag by bag);
+    the logits come back to the host once per run.  ``loss_fn(logits [1, C], label [1])`` defaults to cross-entropy."""
+    bags, labels = _split(bags_or_loader, labels)
+    n = len(bags)
+    if any(l < 0 or l >= n_classes for l in labels):
+        raise ValueError(f"labels must lie in [0, {n_classes})")
+    if loss_fn is None:
+        loss_fn = F.cross_entropy
+    params = list(model.parameters()) if hasattr(model, "parameters") else []
+    dev = params[0].device if params else bags[0].device
+    fb = getattr(model, "forward_bags", None)
+    logits = torch.empty((n, n_classes), dtype=torch.float32)
+    probs = torch.empty((n, n_classes), dtype=torch.float32)
+    preds = torch.empty((n,), dtype=torch.int64)
+    with torch.no_grad():
+        for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
+            part = [bags[i].to(dev) for i in run]
+            if fb is not None:
+                lg, yp, yh = fb(part)[:3]
+            else:
+                outs = [model(b) for b in part]
+                lg, yp, yh = (torch.cat([o[k] for o in outs], dim=0) for k in range(3))
+            sl = slice(run.start, run.stop)
+            logits[sl], probs[sl], preds[sl] = lg.float().cpu(), yp.float().cpu(), yh.reshape(-1).cpu()
+        lab = torch.tensor(labels, dtype=torch.int64)
+        loss = sum(float(loss_fn(logits[i:i + 1], lab[i:i + 1])) for i in range(n)) / n
+    acc = [{"count": 0, "correct": 0} for _ in range(n_classes)]
+    wrong = 0.0
+    for i in range(n):
+        hit = int(preds[i]) == labels[i]
+        acc[labels[i]]["count"] += 1
+        acc[labels[i]]["correct"] += int(hit)
+        wrong += 0.0 if hit else 1.0
+    return SplitResult(all_probs=probs.numpy().astype(np.float64), all_labels=np.asarray(labels, dtype=np.float64),
+                       all_preds=preds.numpy().astype(np.float64), error=wrong / n, loss=loss, acc=acc)
+
+
+def summary_like(ref_module, max_rows_per_call: int = DEFAULT_MAX_ROWS) -> Callable:
+    """A function with the signature and the five results of ``ref_module.summary`` (``utils.eval_utils``) whose numbers come from
+    ``evaluate_split``.  The AUC, the data frame and the logger object are made with that module's own imports (sklearn, pandas,
+    ``Accuracy_Logger``), from the arrays ``evaluate_split`` returns."""
+    m = ref_module
+
+    def summary(model, loader, args, loss_fn=None):
+        model.eval()
+        C = args.n_classes
+        r = evaluate_split(model, loader, None, C, loss_fn, max_rows_per_call)
+        logger = m.Accuracy_Logger(n_classes=C)
+        logger.data = [dict(d) for d in r.acc]
+        if len(np.unique(r.all_labels)) == 1:
+            score = -1
+        elif C == 2:
+            score = m.roc_auc_score(r.all_labels, r.all_probs[:, 1])
+        else:
+            onehot = m.label_binarize(r.all_labels, classes=list(range(C)))
+            if args.micro_average:
+                fpr, tpr, _ = m.roc_curve(onehot.ravel(), r.all_probs.ravel())
+                score = m.auc(fpr, tpr)
+            else:
+                per = []
+                for c in range(C):
+                    if c in r.all_labels:
+                        fpr, tpr, _ = m.roc_curve(onehot[:, c], r.all_probs[:, c])
+                        per.append(m.auc(fpr, tpr))
+                    else:
+                        per.append(float("nan"))
+                score = np.nanmean(np.array(per))
+        table = {"slide_id": loader.dataset.slide_data["slide_id"], "Y": r.all_labels, "Y_hat": r.all_preds}
+        table.update({f"p_{c}": r.all_probs[:, c] for c in range(C)})
+        return r.error, score, m.pd.DataFrame(table), logger, r.loss
+
+    summary.__hipt_amd__ = True
+    return summary

@@ -82,3 +82,59 @@ def attention(qkv: torch.Tensor, num_heads: int, scale: float, dtype: int = N.HI
     N.call("hipt_attention", N.ptr(q), N.ptr(out), N.ptr(probs), B, ntok, num_heads, Cc // num_heads, float(scale), dtype,
            N.stream_ptr(qkv.device))
     return out, probs
+
+
+# ---- CLAM_SB over many bags in one call (include/hipt_abmil.h: hipt_clam_sb_forward_bags) ----
+def check_offsets(offsets, rows: int) -> tuple:
+    """The B+1 row offsets of a multi-bag call as a tuple of ints, or ``ValueError``: they start at 0, increase strictly (no
+    empty bag) and end at ``rows``.  The library trusts what it is handed, so every upload goes through here first."""
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.detach().cpu().tolist()
+    off = tuple(int(v) for v in offsets)
+    if len(off) < 2 or off[0] != 0:
+        raise ValueError(f"bag offsets must be B+1 >= 2 numbers starting at 0, got {off[:4]}{'...' if len(off) > 4 else ''}")
+    for b in range(len(off) - 1):
+        if off[b + 1] < off[b]:
+            raise ValueError(f"bag offsets decrease at bag {b}: {off[b]} -> {off[b + 1]}")
+        if off[b + 1] == off[b]:
+            raise ValueError(f"bag {b} is empty (offsets {off[b]} == {off[b + 1]}): every bag needs at least one row")
+    if off[-1] != int(rows):
+        raise ValueError(f"bag offsets end at {off[-1]} but the concatenated bags have {int(rows)} rows")
+    return off
+
+
+class BagOffsets:
+    """Checked offsets of a multi-bag call: ``host`` (tuple of B+1 ints) and ``dev`` (the same, int64 on the device).  Make it
+    once -- outside a graph capture: the upload is a host-to-device copy -- and hand it to every call over bags of these sizes."""
+    __slots__ = ("host", "dev")
+
+    def __init__(self, offsets, rows: int, device):
+        self.host = check_offsets(offsets, rows)
+        self.dev = torch.tensor(self.host, dtype=torch.int64, device=device)
+
+    def __len__(self):
+        return len(self.host) - 1
+
+
+def clam_sb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_sb_forward_bags`` on ``cat [rows, S0]`` (already in the dtype of the weight image ``w``, an ``_native.ClamWeights``).
+    Returns ``(A_raw [rows], M [B, S1], logits [B, C], Y_prob [B, C], Y_hat [B])`` -- the last four ``None`` with ``attention_only``.
+    ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions, sentinels)."""
+    import ctypes as C
+    N.require_cuda(cat, "clam_sb_forward_bags")
+    dev, B, rows = cat.device, len(offsets), cat.shape[0]
+    if cat.dim() != 2 or not cat.is_contiguous() or cat.dtype != _TORCH_DT[w.dtype] or cat.shape[1] != w.s0:
+        raise ValueError(f"expected contiguous [rows, {w.s0}] bags in {_TORCH_DT[w.dtype]}, got {tuple(cat.shape)} {cat.dtype}")
+    if offsets.host[-1] != rows:
+        raise ValueError(f"bag offsets end at {offsets.host[-1]} but the concatenated bags have {rows} rows")
+    N.same_device("clam_sb_forward_bags", dev, offsets.dev)
+    st = N.stream_ptr(dev)
+    if ws is None:
+        ws = workspace(dev, N.lib().hipt_clam_bags_workspace_bytes(C.byref(w), B, rows), ("clam_bags", st.value))
+    if out is None:
+        e = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        out = (e(rows), None, None, None, None) if attention_only else (e(rows), e(B, w.s1), e(B, w.n_classes), e(B, w.n_classes), e(B, dt=torch.int64))
+    A_raw, M, logits, Y_prob, Y_hat = out
+    N.call("hipt_clam_sb_forward_bags", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw),
+           N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
+    return out

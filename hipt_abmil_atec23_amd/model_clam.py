@@ -294,6 +294,7 @@ class CLAM_SB(WeightImageCache, nn.Module):
         self._gate = gate
         self._dropout = dropout
         self._sizes = tuple(size)
+        self._bags_route = None
         self._init_host()
 
     def relocate(self):
@@ -481,6 +482,85 @@ class CLAM_SB(WeightImageCache, nn.Module):
         if return_features:
             results.update({'features': M})
         return logits, Y_prob, Y_hat, A_raw, results
+
+    # ---- many bags in one call ------------------------------------------------------------------------
+    @property
+    def bags_route(self):
+        """Which route the last ``forward_bags`` took: ``'bags'`` (one ``hipt_clam_sb_forward_bags`` call), ``'per_bag'`` (the loop
+        over ``forward``) or None before the first call."""
+        return self._bags_route
+
+    def _bags_input(self, bags):
+        """``(cat [rows, S0], offsets)`` from a sequence of ``[N_b, S0]`` tensors or from a pair ``(cat, offsets)``; offsets checked on the host."""
+        S0 = self._sizes[0]
+        pair = (isinstance(bags, (tuple, list)) and len(bags) == 2 and isinstance(bags[0], torch.Tensor) and
+                (isinstance(bags[1], Fn.BagOffsets) or not isinstance(bags[1], torch.Tensor) or bags[1].dim() == 1))
+        if pair:
+            cat, off = bags
+            if cat.dim() != 2 or cat.shape[1] != S0:
+                raise ValueError(f"expected concatenated bags [rows, {S0}], got {tuple(cat.shape)}")
+            if isinstance(off, Fn.BagOffsets):
+                if off.host[-1] != cat.shape[0]:
+                    raise ValueError(f"bag offsets end at {off.host[-1]} but the concatenated bags have {cat.shape[0]} rows")
+                return cat, off
+            if isinstance(off, torch.Tensor) and off.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("forward_bags: device offsets cannot be checked inside a graph capture; make a functional.BagOffsets before it")
+            return cat, (Fn.BagOffsets(off, cat.shape[0], cat.device) if cat.is_cuda else Fn.check_offsets(off, cat.shape[0]))
+        bags = list(bags)
+        if not bags:
+            raise ValueError("forward_bags: no bags")
+        for b, t in enumerate(bags):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] == 0 or t.shape[1] != S0:
+                raise ValueError(f"bag {b}: expected a non-empty [N, {S0}] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        host, acc = [0], 0
+        for t in bags:
+            acc += t.shape[0]
+            host.append(acc)
+        cat = torch.cat(bags, dim=0)  # ONE concatenation, on the bags' device
+        return cat, (Fn.BagOffsets(host, acc, cat.device) if cat.is_cuda else tuple(host))
+
+    def forward_bags(self, bags, attention_only=False, return_features=False):
+        """``forward`` over B bags at once, inference only (no autograd; dropout inactive as in ``eval()``).
+
+        ``bags``: a sequence of ``[N_b, S0]`` tensors, or ``(cat [sum N_b, S0], offsets)`` with the B+1 row offsets as a list, a
+        tensor or a ``functional.BagOffsets``.  Returns ``logits [B, C]``, ``Y_prob [B, C]``, ``Y_hat [B, 1]``, ``A_raw`` as a
+        list of ``[1, N_b]`` views of one buffer and ``{'features': M [B, S1]}`` when asked (``attention_only``: the list alone).
+        Where the library has the multi-bag form (``hipt_clam_bags_supported``) this is ONE native call whose per-bag results do
+        not depend on the other bags; elsewhere -- other widths, ``CLAM_MB``, the ungated head, CPU tensors -- it loops over
+        ``forward`` and returns the same structure.  ``bags_route`` tells which."""
+        cat, off = self._bags_input(bags)
+        if self.training and _needs_autograd(self, cat):
+            raise RuntimeError("forward_bags is inference only: in training mode, with gradients asked for, call forward(h) bag by bag")
+        with torch.no_grad():
+            w = None
+            if self._gate and not self._multi and cat.is_cuda:
+                w = self._pack(cat.device)
+                if not N.lib().hipt_clam_bags_supported(C_.byref(w)):
+                    w = None
+            if w is None:
+                return self._forward_bags_loop(cat, off.host if isinstance(off, Fn.BagOffsets) else off, attention_only, return_features)
+            self._bags_route = "bags"
+            A_raw, M, logits, Y_prob, Y_hat = Fn.clam_sb_forward_bags(w, Fn.as_compute(cat, w.dtype), off, attention_only)
+            views = [A_raw[off.host[b]:off.host[b + 1]].view(1, -1) for b in range(len(off))]
+            if attention_only:
+                return views
+            return logits, Y_prob, Y_hat.view(-1, 1), views, ({'features': M} if return_features else {})
+
+    def _forward_bags_loop(self, cat, host, attention_only, return_features):
+        self._bags_route = "per_bag"
+        was_training = self.training
+        self.train(False)
+        try:
+            outs = [self.forward(cat[host[b]:host[b + 1]], attention_only=attention_only, return_features=return_features)
+                    for b in range(len(host) - 1)]
+        finally:
+            self.train(was_training)
+        if attention_only:
+            return outs
+        results = {'features': (torch.stack if self._multi else torch.cat)([o[4]['features'] for o in outs], dim=0)} if return_features else {}
+        return (torch.cat([o[0] for o in outs], dim=0), torch.cat([o[1] for o in outs], dim=0), torch.cat([o[2] for o in outs], dim=0),
+                [o[3] for o in outs], results)
+
 
 
 class CLAM_MB(CLAM_SB):

@@ -86,7 +86,7 @@ class SlideRun:
 def process_slides(model: Callable, clam: Callable, slides: Sequence[SlideSpec], rank: int = 0, world: int = 1, *,
                    device=None, regions_per_call: int = 8, sample_regions: Optional[int] = None,
                    region_source: Optional[Callable] = None, expand_bag: bool = False, feat_dir: Optional[str] = None,
-                   keep_features: bool = False, skip_existing: bool = False) -> SlideRun:
+                   keep_features: bool = False, skip_existing: bool = False, batched_clam: bool = False) -> SlideRun:
     """Run this rank's share of ``slides`` and gather every slide's outputs.
 
     ``model(regions [R, 3, px, px]) -> features [R, d]`` (``HIPT_4K``), ``clam(bag [n, d]) -> (logits, Y_prob, Y_hat,
@@ -96,7 +96,9 @@ def process_slides(model: Callable, clam: Callable, slides: Sequence[SlideSpec],
     TFLOP: SURVEY.md §8d lets the harness time a stated sub-sample); with ``expand_bag`` the slide's bag is then tiled
     back to ``n_regions`` rows so that CLAM_SB and the gather carry their true sizes.  ``feat_dir``: also write
     ``pt_files/{slide}.pt`` through the feature store (and, with ``skip_existing``, skip slides already there, the
-    reference's crude resume, extract_features_fp.py:231-238: such a slide's bag is loaded back instead)."""
+    reference's crude resume, extract_features_fp.py:231-238: such a slide's bag is loaded back instead).
+    ``batched_clam``: keep this rank's bags and run them through ONE ``clam.forward_bags`` call after the extraction loop
+    instead of one ``clam(bag)`` call per slide (same structure of results; the bags stay resident until then)."""
     import os
 
     from .feature_store import FeatureWriter, load_bag
@@ -106,7 +108,7 @@ def process_slides(model: Callable, clam: Callable, slides: Sequence[SlideSpec],
     mine = D.shard_slides(len(slides), rank, world)
     t0 = time.perf_counter()
     run = SlideRun(logits=torch.empty(0), a_raw=[], local_slides=mine)
-    lg, ar = [], []
+    lg, ar, held = [], [], []
     with torch.no_grad():
         for sid in mine:
             spec = slides[sid]
@@ -133,9 +135,15 @@ def process_slides(model: Callable, clam: Callable, slides: Sequence[SlideSpec],
             if expand_bag and feats.shape[0] < spec.n_regions:
                 reps = -(-spec.n_regions // feats.shape[0])
                 bag = feats.repeat(reps, 1)[:spec.n_regions].contiguous()
+            if batched_clam:
+                held.append(bag)
+                continue
             logits, _, _, a_raw, _ = clam(bag)
             lg.append(logits.reshape(-1))
             ar.append(a_raw.reshape(-1))
+        if held:
+            logits, _, _, a_raw, _ = clam.forward_bags(held)
+            lg, ar = [row.reshape(-1) for row in logits], [a.reshape(-1) for a in a_raw]
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize(device)  # (this rank's share is DONE here: what min / max over the ranks compare)
     run.local_seconds = time.perf_counter() - t0

@@ -368,6 +368,25 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
                          float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                          void* workspace, size_t ws_bytes, void* stream);
 
+/* CLAM_SB.forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).
+ * bags: the bags' rows concatenated, [total_rows, S0] in w->dtype, 16-byte aligned; offsets_dev: int64[B + 1] in DEVICE memory, offsets[0] = 0,
+ * increasing, offsets[B] = total_rows: bag b is rows [offsets[b], offsets[b+1]).  Every bag has at least one row.  The CONTENTS of the offsets
+ * are the caller's responsibility (check them on the host before the upload); a bag whose offsets break the rules is left unwritten.
+ * Outputs fp32: A_raw[total_rows], M[B, S1], logits[B, C], Y_prob[B, C]; Y_hat int64[B]; per bag exactly the quantities of hipt_clam_sb_forward.
+ * attention_only != 0: only A_raw is written (M .. Y_hat may be NULL).
+ * Three plain launches on `stream` (unit table from the offsets, 128-row tiles that never span two bags, one combine workgroup per bag): no
+ * atomics, no waiting between workgroups, no host synchronisation or copy -- graph-capturable, and the workspace holds NO state (no ticket
+ * block, nothing to zero).  A bag's five outputs are bit for bit independent of the other bags in the call, of its position and of B.
+ * hipt_clam_bags_supported(w) != 0: the configuration has this form (fp32 S1 in {128, 64, 32}, bf16 S1 in {128, 64}; S2 in {64, 32, 16}; S0 a
+ * multiple of 32 (fp32) / 64 (bf16)); otherwise HIPT_E_UNSUPPORTED and hipt_clam_bags_workspace_bytes = 0: loop over hipt_clam_sb_forward.
+ * HIPT_E_BADARG -- before anything is launched or written -- for a null pointer, a misaligned `bags`, B < 1, total_rows < B, and for a
+ * workspace smaller than hipt_clam_bags_workspace_bytes(w, B, total_rows) or not 256-byte aligned. */
+int hipt_clam_bags_supported(const hipt_clam_weights* w);
+size_t hipt_clam_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
+int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                              int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                              void* workspace, size_t ws_bytes, void* stream);
+
 /* CLAM_MB.forward (model_clam.py:226-264), inference, with ONE pass over the bag for all K = w->n_att attention branches (2 <= K <= 4; W1 and
  * [Wa; Wb] are shared by the branches, only wc / bc / the classifier rows differ):  A_raw[K, N] = the K logits of every row;
  * M[K, S1] = softmax_N(A_raw[k]) h1;  logits[K]: logits[k] = wcls[k] . M[k] + bcls[k] (:248-250; Y_prob / Y_hat are K numbers: the caller's).
