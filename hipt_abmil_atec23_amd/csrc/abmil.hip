@@ -18,7 +18,7 @@
 //            p^T h1 as MFMAs on the h1 image (transposing LDS read in bf16 mode).
 // Each workgroup leaves (max, sum, acc[S1]); a one-workgroup combine kernel merges them and applies
 // the bag classifier, softmax and argmax.
-#include "abmil_tile.h"  // TM, AG<>, h1_off, tanh_f, sigmoid_f: shared with abmil_bags.hip
+#include "abmil_tile.h"  // geometry, LDS carve, tile_max, store_partial, bag_head, width table: shared with abmil_bags.hip
 #include "common.h"
 #include "kernels.h"
 #include "launch.h"
@@ -36,25 +36,15 @@ __global__ __launch_bounds__(256, 2) void abmil_fused_kernel(const T* __restrict
     using G = AG<T, S1, S2>;
     constexpr int EPC = Tr<T>::EPC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* H1s = smem;                     // aliases the stage ring (used after phase 1)
-    char* Wabs = smem + G::H1_BYTES;
-    float* As = (float*)(smem + G::AREA);        // A_raw of the tile
-    float* Ps = As + TM;                          // [2][TM] per-column-wave partial gate sums
-    float* Sc = Ps + 2 * TM;                      // scalars
+    char* H1s = G::h1s(smem);                     // aliases the stage ring (used after phase 1)
+    char* Wabs = G::wabs(smem);
+    float *As = G::as(smem), *Ps = G::ps(smem), *Sc = G::sc(smem);
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int g = lane >> 4, li = lane & 15;
+    const Lanes L;
+    const int tid = L.tid, lane = L.lane, wave = L.wave, wm = L.wm, wn = L.wn, g = L.g, li = L.li, drow = L.drow;
+    const int* foff = L.foff;
     const int ntiles = (N + TM - 1) / TM;
     const int nk = S0 / G::KB;
-
-    int foff[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) foff[ks] = li * 128 + (((g + 4 * ks) ^ ((lane >> 1) & 7)) << 4);
-
-    // per-lane LDS-DMA geometry: row within an 8-row instruction block and logical chunk
-    const int drow = lane >> 3;
 
     float m_run = -INFINITY, l_run = 0.f;
     f32x4 accM[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // c-frags 2*wave, 2*wave+1
@@ -199,12 +189,7 @@ __global__ __launch_bounds__(256, 2) void abmil_fused_kernel(const T* __restrict
         }
         if (attention_only) continue;  // uniform
         // ---------------- pooling: online softmax + p^T h1 ----------------
-        {
-            float mt = wave_max(a_mine);
-            if (lane == 0 && wave < 2) Sc[wave] = mt;
-        }
-        __syncthreads();
-        const float m_new = fmaxf(m_run, fmaxf(Sc[0], Sc[1]));  // finite: every tile has >= 1 valid row
+        const float m_new = fmaxf(m_run, tile_max(L, Sc, a_mine));
         const float resc = exp2f((m_run - m_new) * 1.4426950408889634f);  // 0 on the first tile
         m_run = m_new;
         // p for this lane's K slots (rows of the tile); invalid rows carry -inf -> p = 0
@@ -278,20 +263,7 @@ __global__ __launch_bounds__(256, 2) void abmil_fused_kernel(const T* __restrict
         for (int cf = 0; cf < 2; ++cf) accM[cf] = accM[cf] * resc + o[cf];
     }
     // ---------------- per-workgroup partial: (max, sum, acc[S1]) ----------------
-    if (!attention_only) {
-        float* pw = partials + (int64_t)blockIdx.x * (2 + S1);
-        if (tid == 0) {
-            pw[0] = m_run;
-            pw[1] = l_run;
-        }
-        if (li == 0) {
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-                if ((wave * 2 + cf) * 16 < S1)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pw[2 + (wave * 2 + cf) * 16 + 4 * g + e] = accM[cf][e];
-        }
-    }
+    if (!attention_only) store_partial<S1>(L, partials + (int64_t)blockIdx.x * (2 + S1), m_run, l_run, accM);
 }
 
 // Merge per-workgroup partials; bag classifier, softmax, argmax (model_clam.py:180-183).
@@ -348,29 +320,7 @@ __global__ __launch_bounds__(1024) void abmil_combine_kernel(const float* __rest
         M[c] = a;
     }
     __syncthreads();
-    for (int k = wv; k < C; k += 16) {
-        float a = 0.f;
-        for (int c = ln; c < S1; c += 64) a += Ms[c] * wcls[(int64_t)k * S1 + c];
-        a = wave_sum(a);
-        if (ln == 0) Ls[k] = a + bcls[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float lm = -INFINITY;
-        int arg = 0;
-        for (int k = 0; k < C; ++k)
-            if (Ls[k] > lm) {
-                lm = Ls[k];
-                arg = k;
-            }
-        float se = 0.f;
-        for (int k = 0; k < C; ++k) se += expf(Ls[k] - lm);
-        for (int k = 0; k < C; ++k) {
-            logits[k] = Ls[k];
-            Y_prob[k] = expf(Ls[k] - lm) / se;
-        }
-        Y_hat[0] = arg;
-    }
+    bag_head(Ms, Ls, S1, wcls, bcls, C, logits, Y_prob, Y_hat);
 }
 
 // ---------------- generic (any width) building blocks ----------------
@@ -475,27 +425,18 @@ int launch_fused(const hipt_clam_weights* w, const void* bag, int N, int attenti
 
 bool hipt_clam_fused_supported(const hipt_clam_weights* w) {
     const int kb = w->dtype == HIPT_F32 ? 32 : 64;
-    if (w->s0 % kb) return false;
-    const int s1 = w->s1, s2 = w->s2;
-    if (w->dtype == HIPT_BF16) return (s1 == 128 || s1 == 64) && (s2 == 64 || s2 == 32 || s2 == 16);
-    return (s1 == 128 || s1 == 64 || s1 == 32) && (s2 == 64 || s2 == 32 || s2 == 16);
+    return w->s0 % kb == 0 && visit_width(w->dtype, w->s1, w->s2, [](auto) {});
 }
 
 int hipt_clam_fused_launch(const hipt_clam_weights* w, const void* bag, int N, int attention_only, float* A_raw,
                            float* partials, int* n_partials, hipStream_t st) {
-#define FUSED(TT, A, B) \
-    if (w->s1 == A && w->s2 == B) return launch_fused<TT, A, B>(w, bag, N, attention_only, A_raw, partials, n_partials, st);
-    if (w->dtype == HIPT_BF16) {
-        FUSED(bf16_t, 128, 64) FUSED(bf16_t, 128, 32) FUSED(bf16_t, 128, 16)
-        FUSED(bf16_t, 64, 64) FUSED(bf16_t, 64, 32) FUSED(bf16_t, 64, 16)
-    } else {
-        FUSED(float, 128, 64) FUSED(float, 128, 32) FUSED(float, 128, 16)
-        FUSED(float, 64, 64) FUSED(float, 64, 32) FUSED(float, 64, 16)
-        FUSED(float, 32, 64) FUSED(float, 32, 32) FUSED(float, 32, 16)
-    }
-#undef FUSED
-    hipt_set_error("clam fused: unsupported widths");
-    return HIPT_E_UNSUPPORTED;
+    int rc = HIPT_E_UNSUPPORTED;
+    const bool found = visit_width(w->dtype, w->s1, w->s2, [&](auto wd) {
+        using W = decltype(wd);
+        rc = launch_fused<typename W::T, W::S1, W::S2>(w, bag, N, attention_only, A_raw, partials, n_partials, st);
+    });
+    if (!found) hipt_set_error("clam fused: unsupported widths");
+    return rc;
 }
 
 int hipt_clam_combine_launch(const float* partials, int G, const hipt_clam_weights* w, float* M, float* logits,

@@ -4,11 +4,12 @@
 // after launch on a 256-CU chip.  Here the whole set is three plain launches on one stream:
 //   units    one workgroup turns the offsets into the work-unit table: unit = one 128-row tile of ONE bag (a tile never spans two
 //            bags), units of a bag consecutive and in row order, tile_start[b] = first unit of bag b;
-//   tiles    abmil_fused_kernel's tile arithmetic, instruction for instruction (phase 1 GEMM by LDS-DMA ring, +b1, ReLU, gate GEMM,
-//            tanh * sigmoid * wc, the tile's softmax numerator and p^T h1 on the matrix pipe), but WITHOUT running state from tile
-//            to tile: every unit writes A_raw of its rows and its own partial (max, sum, acc[S1]) to partials[unit].  One
-//            difference, bf16 only: the pooling takes fp32 weights and an fp32 copy of h1 (the fp32 instantiation's code) instead
-//            of the bf16 image, which costs 4 * 128 * S1 bytes of LDS and brings M to the accuracy of the per-bag streaming kernel;
+//   tiles    abmil_fused_kernel's tile arithmetic, statement for statement on the geometry and LDS carve of abmil_tile.h (phase 1
+//            GEMM by LDS-DMA ring, +b1, ReLU, gate GEMM, tanh * sigmoid * wc, the tile's softmax numerator and p^T h1 on the matrix
+//            pipe), but WITHOUT running state from tile to tile: every unit writes A_raw of its rows and its own partial
+//            (max, sum, acc[S1]) to partials[unit].  One difference, bf16 only: the pooling takes fp32 weights and an fp32 copy of h1
+//            (the fp32 instantiation's code) instead of the bf16 image, which costs 4 * 128 * S1 bytes of LDS and brings M to the
+//            accuracy of the per-bag streaming kernel;
 //   combine  one workgroup per bag merges partials[tile_start[b] .. tile_start[b+1]) in a reduction whose shape depends on the
 //            bag's tile count alone, then the bag classifier, softmax and argmax as abmil_combine_kernel.
 // Hence a bag's outputs are bit for bit independent of the other bags of the call, of its position, of B and of the grid size
@@ -85,29 +86,19 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_kernel(const T* __restrict_
     using G = AG<T, S1, S2>;
     constexpr int EPC = Tr<T>::EPC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* H1s = smem;                     // aliases the stage ring (used after phase 1)
-    char* Wabs = smem + G::H1_BYTES;
-    float* As = (float*)(smem + G::AREA);        // A_raw of the tile
-    float* Ps = As + TM;                          // [2][TM] per-column-wave partial gate sums
-    float* Sc = Ps + 2 * TM;                      // scalars
+    char* H1s = G::h1s(smem);                     // aliases the stage ring (used after phase 1)
+    char* Wabs = G::wabs(smem);
+    float *As = G::as(smem), *Ps = G::ps(smem), *Sc = G::sc(smem);
     // bf16 only: h1 once more, UNROUNDED (fp32, the fp32 instantiation's image layout), behind everything else.  The gate GEMM reads the
     // bf16 image as in abmil_fused_kernel; the pooling reads this one, so that M carries no bf16 rounding of h1 or of the softmax weights
     // (the per-bag streaming kernel pools fp32 h1 too; a one-row bag's M is h1 itself).
     constexpr bool POOL32 = sizeof(T) == 2;
-    char* Hp = POOL32 ? smem + G::LDS : H1s;
+    char* Hp = POOL32 ? G::h32(smem) : H1s;
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int g = lane >> 4, li = lane & 15;
+    const Lanes L;
+    const int tid = L.tid, lane = L.lane, wave = L.wave, wm = L.wm, wn = L.wn, g = L.g, li = L.li, drow = L.drow;
+    const int* foff = L.foff;
     const int nk = S0 / G::KB;
-
-    int foff[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) foff[ks] = li * 128 + (((g + 4 * ks) ^ ((lane >> 1) & 7)) << 4);
-
-    // per-lane LDS-DMA geometry: row within an 8-row instruction block and logical chunk
-    const int drow = lane >> 3;
 
     for (int unit = blockIdx.x; unit < max_units; unit += gridDim.x) {
         const BagUnit un = units[unit];
@@ -253,12 +244,7 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_kernel(const T* __restrict_
         }
         if (attention_only) continue;  // uniform
         // ---------------- pooling of THIS tile: softmax numerator against the tile's own maximum + p^T h1 ----------------
-        {
-            float mt = wave_max(a_mine);
-            if (lane == 0 && wave < 2) Sc[wave] = mt;
-        }
-        __syncthreads();
-        const float m_new = fmaxf(Sc[0], Sc[1]);  // finite: every unit has >= 1 valid row
+        const float m_new = tile_max(L, Sc, a_mine);
         // p for this lane's K slots (rows of the tile); invalid rows carry -inf -> p = 0
         float lsum = 0.f;
         f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -289,18 +275,7 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_kernel(const T* __restrict_
         lsum += __shfl_xor(lsum, 16, 64);
         lsum += __shfl_xor(lsum, 32, 64);
         // ---------------- the unit's partial: (max, sum, acc[S1]) ----------------
-        float* pw = partials + (int64_t)unit * (2 + S1);
-        if (tid == 0) {
-            pw[0] = m_new;
-            pw[1] = lsum;
-        }
-        if (li == 0) {
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-                if ((wave * 2 + cf) * 16 < S1)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pw[2 + (wave * 2 + cf) * 16 + 4 * g + e] = o[cf][e];
-        }
+        store_partial<S1>(L, partials + (int64_t)unit * (2 + S1), m_new, lsum, o);
     }
 }
 
@@ -366,29 +341,7 @@ __global__ __launch_bounds__(1024) void abmil_bags_combine_kernel(const float* _
         M[c] = a;
     }
     __syncthreads();
-    for (int k = wv; k < C; k += 16) {
-        float a = 0.f;
-        for (int c = ln; c < S1; c += 64) a += Ms[c] * wcls[(int64_t)k * S1 + c];
-        a = wave_sum(a);
-        if (ln == 0) Ls[k] = a + bcls[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float lm = -INFINITY;
-        int arg = 0;
-        for (int k = 0; k < C; ++k)
-            if (Ls[k] > lm) {
-                lm = Ls[k];
-                arg = k;
-            }
-        float se = 0.f;
-        for (int k = 0; k < C; ++k) se += expf(Ls[k] - lm);
-        for (int k = 0; k < C; ++k) {
-            logits[k] = Ls[k];
-            Y_prob[k] = expf(Ls[k] - lm) / se;
-        }
-        Y_hat[b] = arg;
-    }
+    bag_head(Ms, Ls, S1, wcls, bcls, C, logits, Y_prob, Y_hat + b);
 }
 
 // Workgroups of the tile pass: two per CU fit (launch bounds), four waves of units keep the tail short.  HIPT_BAGS_MAX_WG (1..)
@@ -429,19 +382,13 @@ int hipt_clam_bags_units_launch(const int64_t* offsets, int B, int64_t total_row
 
 int hipt_clam_bags_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
                                 int attention_only, float* A_raw, float* partials, hipStream_t st) {
-#define BAGS(TT, A, B) \
-    if (w->s1 == A && w->s2 == B) return launch_bags<TT, A, B>(w, bags, units, max_units, attention_only, A_raw, partials, st);
-    if (w->dtype == HIPT_BF16) {
-        BAGS(bf16_t, 128, 64) BAGS(bf16_t, 128, 32) BAGS(bf16_t, 128, 16)
-        BAGS(bf16_t, 64, 64) BAGS(bf16_t, 64, 32) BAGS(bf16_t, 64, 16)
-    } else {
-        BAGS(float, 128, 64) BAGS(float, 128, 32) BAGS(float, 128, 16)
-        BAGS(float, 64, 64) BAGS(float, 64, 32) BAGS(float, 64, 16)
-        BAGS(float, 32, 64) BAGS(float, 32, 32) BAGS(float, 32, 16)
-    }
-#undef BAGS
-    hipt_set_error("clam bags: unsupported widths");
-    return HIPT_E_UNSUPPORTED;
+    int rc = HIPT_E_UNSUPPORTED;
+    const bool found = visit_width(w->dtype, w->s1, w->s2, [&](auto wd) {
+        using W = decltype(wd);
+        rc = launch_bags<typename W::T, W::S1, W::S2>(w, bags, units, max_units, attention_only, A_raw, partials, st);
+    });
+    if (!found) hipt_set_error("clam bags: unsupported widths");
+    return rc;
 }
 
 int hipt_clam_bags_combine_launch(const float* partials, const int* tile_start, int max_units, int B,

@@ -1,6 +1,8 @@
-// Geometry and scalar helpers of the fused CLAM_SB / ABMIL row tile, shared by the single-bag kernel (abmil.hip) and the ragged
-// multi-bag kernel (abmil_bags.hip): the tile height, the LDS budget of one [T, S1, S2] instantiation, the swizzled h1 image and the
-// gate's two transcendental functions.  Declarations only move here: both files compile them exactly as abmil.hip did on its own.
+// What the single-bag kernel (abmil.hip) and the ragged multi-bag kernel (abmil_bags.hip) of the fused CLAM_SB / ABMIL row tile share:
+// tile height, LDS budget and carve of one [T, S1, S2] instantiation, lane geometry, the swizzled h1 image, the gate's two
+// transcendental functions, tile_max and store_partial, bag_head (the tail of both combine kernels) and the one table of supported
+// widths (visit_width).  The GEMM phases and the fp32 pooling are still written out in both kernels: lifted into functions here they
+// compiled to different, slower code.
 #pragma once
 #include "common.h"
 
@@ -26,6 +28,30 @@ template <typename T, int S1, int S2> struct AG {
     static constexpr int LDS = AREA + TM * 4 * 3 + 64;  // + A_raw[128], partial[2][128], scalars
     static_assert(S1 % KB == 0 && S1 % 32 == 0 && S1 <= 128, "fused ABMIL: S1 in {32(bf16: 64),64,128}");
     static_assert((2 * S2) % 32 == 0 && 2 * S2 <= 128, "fused ABMIL: S2 in {16,32,64}");
+    // the carve of the kernel's dynamic LDS `s`
+    static __device__ __forceinline__ char* h1s(char* s) { return s; }  // h1 image: aliases the stage ring of phase 1 (used after it)
+    static __device__ __forceinline__ char* wabs(char* s) { return s + H1_BYTES; }
+    static __device__ __forceinline__ float* as(char* s) { return (float*)(s + AREA); }  // A_raw of the tile
+    static __device__ __forceinline__ float* ps(char* s) { return as(s) + TM; }          // [2][TM] per-column-wave partial gate sums
+    static __device__ __forceinline__ float* sc(char* s) { return ps(s) + 2 * TM; }      // scalars
+    // h1 once more, UNROUNDED (fp32 image), behind everything else: only where the launch adds TM * S1 * 4 bytes
+    static __device__ __forceinline__ char* h32(char* s) { return s + LDS; }
+};
+
+// lane geometry of the 256-thread tile kernels, built once per kernel
+struct Lanes {
+    int tid, lane, wave, wm, wn, g, li;
+    int drow;     // LDS-DMA: row within an 8-row instruction block
+    int foff[2];  // byte offset of this lane's operand fragment inside a 16-row block of a swizzled image, per K half
+    __device__ __forceinline__ Lanes() {
+        tid = threadIdx.x, lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        wm = wave >> 1, wn = wave & 1;
+        g = lane >> 4, li = lane & 15;
+        drow = lane >> 3;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) foff[ks] = li * 128 + (((g + 4 * ks) ^ ((lane >> 1) & 7)) << 4);
+    }
 };
 
 // byte offset of element (row, col) inside the slab-major, swizzled A-operand image of h1
@@ -33,6 +59,78 @@ template <typename T> __device__ __forceinline__ int h1_off(int row, int col) {
     constexpr int KB = Tr<T>::KB, EPC = Tr<T>::EPC;
     const int slab = col / KB, c = (col % KB) / EPC, sub = (col % EPC) * (int)sizeof(T);
     return slab * (TM * 128) + row * 128 + ((c ^ ((row >> 1) & 7)) << 4) + sub;
+}
+
+// The tile's largest score, in every thread (finite: a tile has >= 1 valid row).  Its barrier also publishes As to the pooling.
+__device__ __forceinline__ float tile_max(const Lanes& L, float* Sc, float a_mine) {
+    const float mt = wave_max(a_mine);
+    if (L.lane == 0 && L.wave < 2) Sc[L.wave] = mt;
+    __syncthreads();
+    return fmaxf(Sc[0], Sc[1]);
+}
+
+
+// one partial (max, sum, acc[S1]) at pw: wave w holds the c-frags 2w and 2w+1 of acc
+template <int S1>
+__device__ __forceinline__ void store_partial(const Lanes& L, float* __restrict__ pw, float mx, float sum, const f32x4 (&acc)[2]) {
+    if (L.tid == 0) {
+        pw[0] = mx;
+        pw[1] = sum;
+    }
+    if (L.li == 0) {
+#pragma unroll
+        for (int cf = 0; cf < 2; ++cf)
+            if ((L.wave * 2 + cf) * 16 < S1)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pw[2 + (L.wave * 2 + cf) * 16 + 4 * L.g + e] = acc[cf][e];
+    }
+}
+
+// Tail of both combine kernels (1024 threads): bag classifier on Ms[S1] (LDS, written by the caller before a barrier), softmax,
+// argmax (model_clam.py:180-183).  Ls: C floats of LDS.
+__device__ __forceinline__ void bag_head(const float* Ms, float* Ls, int S1, const float* __restrict__ wcls,
+                                         const float* __restrict__ bcls, int C, float* __restrict__ logits,
+                                         float* __restrict__ Y_prob, int64_t* __restrict__ Y_hat) {
+    const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
+    for (int k = wv; k < C; k += 16) {
+        float a = 0.f;
+        for (int c = ln; c < S1; c += 64) a += Ms[c] * wcls[(int64_t)k * S1 + c];
+        a = wave_sum(a);
+        if (ln == 0) Ls[k] = a + bcls[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float lm = -INFINITY;
+        int arg = 0;
+        for (int k = 0; k < C; ++k)
+            if (Ls[k] > lm) {
+                lm = Ls[k];
+                arg = k;
+            }
+        float se = 0.f;
+        for (int k = 0; k < C; ++k) se += expf(Ls[k] - lm);
+        for (int k = 0; k < C; ++k) {
+            logits[k] = Ls[k];
+            Y_prob[k] = expf(Ls[k] - lm) / se;
+        }
+        Y_hat[0] = arg;
+    }
+}
+
+// THE supported [T, S1, S2] set: f(Width<T, S1, S2>{}) for the instantiation of (dtype, s1, s2); false (f not called) if there is none.
+template <typename T_, int S1_, int S2_> struct Width { using T = T_; static constexpr int S1 = S1_, S2 = S2_; };
+template <typename F> bool visit_width(int dtype, int s1, int s2, F&& f) {
+#define HIPT_ABMIL_W(TT, A, B) if (s1 == A && s2 == B) return f(Width<TT, A, B>{}), true;
+    if (dtype == HIPT_BF16) {
+        HIPT_ABMIL_W(bf16_t, 128, 64) HIPT_ABMIL_W(bf16_t, 128, 32) HIPT_ABMIL_W(bf16_t, 128, 16)
+        HIPT_ABMIL_W(bf16_t, 64, 64) HIPT_ABMIL_W(bf16_t, 64, 32) HIPT_ABMIL_W(bf16_t, 64, 16)
+    } else {
+        HIPT_ABMIL_W(float, 128, 64) HIPT_ABMIL_W(float, 128, 32) HIPT_ABMIL_W(float, 128, 16)
+        HIPT_ABMIL_W(float, 64, 64) HIPT_ABMIL_W(float, 64, 32) HIPT_ABMIL_W(float, 64, 16)
+        HIPT_ABMIL_W(float, 32, 64) HIPT_ABMIL_W(float, 32, 32) HIPT_ABMIL_W(float, 32, 16)
+    }
+#undef HIPT_ABMIL_W
+    return false;
 }
 
 }  // namespace abmil_tile

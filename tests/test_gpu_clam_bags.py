@@ -195,6 +195,35 @@ def test_evaluate_split_does_not_depend_on_the_chunking(dtype):
     assert a.error == b.error and a.loss == b.loss and a.acc == b.acc
 
 
+# ---------------------------------------------------------------- 2b. one tile routine for both kernels
+@pytest.mark.parametrize("size,dtype", [((384, 128, 64), "fp32"), ((192, 64, 32), "fp32"), ((192, 64, 32), "bf16")])
+def test_tile_is_the_fused_kernels_tile(size, dtype):
+    """abmil_bags_kernel and abmil_fused_kernel run the same tile arithmetic on the geometry of csrc/abmil_tile.h, so A_raw of
+    ``forward_bags`` is A_raw of per-bag ``forward`` bit for bit.  In fp32 a bag of one tile agrees in every output: the tile's
+    running state is that tile's partial, and both combines then do the same arithmetic on one partial."""
+    m = make(size, dtype)
+    rows = (1, 127, 128, 129, 300)
+    bags = bags_of(size[0], 17, rows)
+    out = run_bags(m, bags)
+    N.profile_enable(True)
+    try:
+        with torch.no_grad():
+            single = [m(b, return_features=True) for b in bags]
+        torch.cuda.synchronize()
+        counts = {k: c for k, (_, c) in N.profile_read().items()}
+    finally:
+        N.profile_enable(False)
+    # the streaming kernel (abmil32) counts as abmil_fused WITHOUT a combine launch; the generic route launches neither
+    if counts.get("abmil_fused") != len(rows) or counts.get("abmil_combine") != len(rows):
+        pytest.skip(f"forward did not take abmil_fused_kernel + abmil_combine_kernel here: {counts}")
+    for b, (n, (logits, y_prob, y_hat, a_raw, res)) in enumerate(zip(rows, single)):
+        got = per_bag(out, b)
+        assert bits(got["A_raw"]) == bits(a_raw), f"A_raw of the {n}-row bag"
+        if dtype == "fp32" and n <= 128:
+            one = {"A_raw": a_raw, "M": res["features"].reshape(got["M"].shape), "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
+            assert_same_bits(got, one, f"{n}-row bag")
+
+
 # ---------------------------------------------------------------- 3. bf16 parity
 def measure_bf16(route, size):
     m = make(size, "bf16")
