@@ -135,6 +135,9 @@ SIGNATURES = {
     "hipt_clam_bags_supported": (_i, [_CW]),
     "hipt_clam_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
     "hipt_clam_sb_forward_bags": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hipt_clam_mb_bags_supported": (_i, [_CW]),
+    "hipt_clam_mb_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
+    "hipt_clam_mb_forward_bags": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hipt_clam_mb_supported": (_i, [_CW]),
     "hipt_clam_mb_workspace_bytes": (_sz, [_CW, _i]),
     "hipt_clam_mb_forward": (_i, [_CW, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -145,6 +148,7 @@ SIGNATURES = {
     "hipt_clam_train_forward": (_i, [_TW, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "hipt_clam_train_backward": (_i, [_TW, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _TG, _p, _sz, _p]),
     "hipt_topk_rows": (_i, [_p, _i, _i, _i, _p, _p]),
+    "hipt_topk_segments": (_i, [_p, _i64, _p, _i, _i, _i, _p, _p, _p]),
     "hipt_augment_workspace_bytes": (_sz, [_i, _i, _i]),
     "hipt_augment_regions": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "hipt_resnet_packed_bytes": (_sz, [_RW]),

@@ -36,6 +36,14 @@ template <typename T, int S1, int S2> struct AG {
     static __device__ __forceinline__ float* sc(char* s) { return ps(s) + 2 * TM; }      // scalars
     // h1 once more, UNROUNDED (fp32 image), behind everything else: only where the launch adds TM * S1 * 4 bytes
     static __device__ __forceinline__ char* h32(char* s) { return s + LDS; }
+    // the carve of the K-branch multi-bag kernel (abmil_bags.hip, KMAX = 4 branches): the same AREA, then A_raw[4][128],
+    // partial[4][2][128], scalars, and the fp32 h1 image behind them
+    static constexpr int KMAX = 4;
+    static constexpr int LDS_MB = AREA + TM * 4 * 3 * KMAX + 64;
+    static __device__ __forceinline__ float* as_mb(char* s) { return (float*)(s + AREA); }   // [KMAX][TM] A_raw of the tile
+    static __device__ __forceinline__ float* ps_mb(char* s) { return as_mb(s) + KMAX * TM; } // [KMAX][2][TM] per-column-wave partial gate sums
+    static __device__ __forceinline__ float* sc_mb(char* s) { return ps_mb(s) + 2 * KMAX * TM; }  // [KMAX][2] wave maxima
+    static __device__ __forceinline__ char* h32_mb(char* s) { return s + LDS_MB; }
 };
 
 // lane geometry of the 256-thread tile kernels, built once per kernel

@@ -1165,12 +1165,12 @@ int hipt_clam_bags_supported(const hipt_clam_weights* w) { return w && check_cla
 // units of a call: sum_b ceil(N_b / 128) <= total_rows / 128 + B, known without reading the offsets back
 static int64_t clam_bags_max_units(int B, int64_t total_rows) { return (total_rows + 127) / 128 + B; }
 struct ClamBagsWs { void* units; int* tile_start; float* partials; };
-static ClamBagsWs carve_clam_bags(Carver& c, const hipt_clam_weights* w, int B, int64_t total_rows) {
+static ClamBagsWs carve_clam_bags(Carver& c, const hipt_clam_weights* w, int B, int64_t total_rows, int branches = 1) {
     const size_t nu = (size_t)clam_bags_max_units(B, total_rows);
     ClamBagsWs k;
     k.units = c.take(nu * hipt_clam_bags_unit_bytes());
     k.tile_start = c.take<int>((size_t)B + 1);
-    k.partials = c.take<float>(nu * (2 + (size_t)w->s1));
+    k.partials = c.take<float>(nu * (size_t)branches * (2 + (size_t)w->s1));  // one partial per unit and attention branch
     return k;
 }
 
@@ -1205,6 +1205,45 @@ int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, cons
     PROF(PC_ABMIL, hipt_clam_bags_tiles_launch(w, bags, k.units, nu, attention_only, A_raw, k.partials, st));
     if (attention_only) return HIPT_OK;
     PROF(PC_COMBINE, hipt_clam_bags_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
+    return HIPT_OK;
+}
+
+// ---- the same for the K = n_att branches of CLAM_MB: K partials per unit ----
+int hipt_clam_mb_bags_supported(const hipt_clam_weights* w) {
+    return hipt_clam_bags_supported(w) && w->n_att >= 2 && w->n_att <= 4 && w->n_att == w->n_classes ? 1 : 0;
+}
+
+size_t hipt_clam_mb_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows) {
+    if (!hipt_clam_mb_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
+    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows, w->n_att); });
+}
+
+int hipt_clam_mb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                              int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat, void* workspace,
+                              size_t ws_bytes, void* stream) {
+    int rc = check_clam(w);
+    if (rc) return rc;
+    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "clam_mb_forward_bags: null argument");
+    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "clam_mb_forward_bags: null output");
+    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "clam_mb_forward_bags: bags must be 16-byte aligned");
+    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "clam_mb_forward_bags: B = %d bags need at least one row each (total_rows = %lld)", B,
+                   (long long)total_rows);
+    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "clam_mb_forward_bags: %lld rows in %d bags exceed 2^31 tiles",
+                   (long long)total_rows, B);
+    if (!hipt_clam_mb_bags_supported(w)) {
+        hipt_set_error("clam_mb_forward_bags: no multi-bag form for [%d,%d,%d] with %d branches / %d classes in this dtype: call "
+                       "hipt_clam_mb_forward or hipt_clam_sb_forward per bag", w->s0, w->s1, w->s2, w->n_att, w->n_classes);
+        return HIPT_E_UNSUPPORTED;
+    }
+    Carver c(workspace, ws_bytes);
+    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows, w->n_att);
+    if (check_workspace(c, "clam_mb_forward_bags")) return HIPT_E_BADARG;  // as hipt_clam_sb_forward_bags: a short buffer is a bad argument
+    hipStream_t st = S(stream);
+    const int nu = (int)clam_bags_max_units(B, total_rows);
+    PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
+    PROF(PC_ABMIL, hipt_clam_bags_mb_tiles_launch(w, bags, k.units, nu, attention_only, total_rows, A_raw, k.partials, st));
+    if (attention_only) return HIPT_OK;
+    PROF(PC_COMBINE, hipt_clam_bags_mb_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
     return HIPT_OK;
 }
 

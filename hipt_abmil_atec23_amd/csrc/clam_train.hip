@@ -631,6 +631,35 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     topk_block(a, N, -1.0f, k_sel, ids + (int64_t)(2 * blockIdx.x + 1) * k_sel, red, redi);
 }
 
+// topk_rows_kernel over the bags of a multi-bag call: workgroup (b, r) takes branch r of bag b, the n = offsets[b+1] - offsets[b] scores at
+// A + r * row_stride + offsets[b].  ids [B, K, 2, k_sel] are bag-local; gids (optional) the same plus offsets[b] = rows of the concatenated
+// matrix.  A bag with fewer than k_sel rows, or whose offsets do not lie inside [0, row_stride], gets -1 everywhere and nothing of A is read.
+__global__ __launch_bounds__(256) void topk_segments_kernel(const float* __restrict__ A, int64_t row_stride, const int64_t* __restrict__ offsets,
+                                                            int K, int k_sel, int64_t* __restrict__ ids, int64_t* __restrict__ gids) {
+    __shared__ float red[8];
+    __shared__ int redi[8];
+    const int b = blockIdx.x / K, r = blockIdx.x - b * K;
+    const int64_t lo = offsets[b], hi = offsets[b + 1];
+    int64_t* out = ids + (int64_t)blockIdx.x * 2 * k_sel;
+    int64_t* gout = gids ? gids + (int64_t)blockIdx.x * 2 * k_sel : nullptr;
+    const bool ok = lo >= 0 && hi > lo && hi <= row_stride && hi - lo >= k_sel && hi - lo <= 0x7fffffff;  // uniform
+    if (!ok) {
+        for (int i = threadIdx.x; i < 2 * k_sel; i += 256) {
+            out[i] = -1;
+            if (gout) gout[i] = -1;
+        }
+        return;
+    }
+    const float* a = A + (int64_t)r * row_stride + lo;
+    const int n = (int)(hi - lo);
+    topk_block(a, n, 1.0f, k_sel, out, red, redi);
+    topk_block(a, n, -1.0f, k_sel, out + k_sel, red, redi);
+    if (gout) {
+        __syncthreads();  // thread 0 wrote the ids
+        for (int i = threadIdx.x; i < 2 * k_sel; i += 256) gout[i] = out[i] + lo;
+    }
+}
+
 TrainDims dims_of(const hipt_clam_train_weights* w, int N) { return TrainDims{N, w->s0, w->s1, w->s2, w->n_att, w->n_classes, w->multi_branch}; }
 TrainW ptrs_of(const hipt_clam_train_weights* w) { return TrainW{w->w1, w->b1, w->wa, w->ba, w->wb, w->bb, w->wc, w->bc, w->wcls, w->bcls}; }
 
@@ -785,6 +814,15 @@ int hipt_topk_rows(const float* A, int rows, int N, int k, int64_t* ids, void* s
         return HIPT_E_BADARG;
     }
     hipLaunchKernelGGL(topk_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, A, N, k, ids);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
+}
+
+int hipt_topk_segments(const float* A, int64_t row_stride, const int64_t* offsets_dev, int B, int K, int k, int64_t* ids,
+                       int64_t* global_ids, void* stream) {
+    HIPT_CHECK_ARG(A && offsets_dev && ids && B > 0 && K > 0 && k > 0 && row_stride > 0, "topk_segments: null/empty argument");
+    HIPT_CHECK_ARG((int64_t)B * K <= 0x7fffffff, "topk_segments: %d bags x %d branches exceed the grid", B, K);
+    hipLaunchKernelGGL(topk_segments_kernel, dim3(B * K), dim3(256), 0, (hipStream_t)stream, A, row_stride, offsets_dev, K, k, ids, global_ids);
     HIPT_CHECK_LAUNCH();
     return HIPT_OK;
 }

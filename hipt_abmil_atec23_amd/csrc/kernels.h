@@ -228,6 +228,12 @@ int hipt_clam_bags_tiles_launch(const hipt_clam_weights* w, const void* bags, co
 int hipt_clam_bags_combine_launch(const float* partials, const int* tile_start, int max_units, int B,
                                   const hipt_clam_weights* w, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                                   hipStream_t st);
+// the same over w->n_att = 2..4 attention branches (CLAM_MB): A_raw [K, a_stride], K partials per unit, M [B, K, S1], logits / Y_prob [B, K]
+int hipt_clam_bags_mb_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
+                                   int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
+int hipt_clam_bags_mb_combine_launch(const float* partials, const int* tile_start, int max_units, int B,
+                                     const hipt_clam_weights* w, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                     hipStream_t st);
 
 // ---- bootstrapped evaluation metrics (bootstrap.hip) ----
 size_t hipt_bootstrap_lds_bytes(int n);

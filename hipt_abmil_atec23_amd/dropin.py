@@ -159,6 +159,41 @@ def _install_evaluation(verbose: bool) -> bool:
     return True
 
 
+_VAL_MOD = "utils.core_utils"
+
+
+def _install_validation(verbose: bool) -> bool:
+    """Bind ``evaluate.validate_clam_like`` as ``utils.core_utils.validate_clam`` (opt-in): the per-epoch validation goes through
+    ``forward_bags(..., instance_eval=True)`` in a few calls.  False, and nothing done, where the reference's module does not import."""
+    from . import evaluate
+    if _VAL_MOD in _saved:
+        return True
+    try:
+        if _VAL_MOD not in sys.modules and importlib.util.find_spec(_VAL_MOD) is None:
+            return False
+        mod = importlib.import_module(_VAL_MOD)
+    except Exception:   # no reference checkout on sys.path, or one of its imports is missing
+        return False
+    _saved[_VAL_MOD] = mod.__dict__.get("validate_clam")
+    mod.validate_clam = evaluate.validate_clam_like(mod)
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_VAL_MOD}.validate_clam -> {evaluate.__name__}.validate_split")
+    return True
+
+
+def _uninstall_validation():
+    if _VAL_MOD not in _saved:
+        return
+    prev = _saved.pop(_VAL_MOD)
+    mod = sys.modules.get(_VAL_MOD)
+    if mod is None:
+        return
+    if prev is None:
+        del mod.validate_clam
+    else:
+        mod.validate_clam = prev
+
+
 def _uninstall_evaluation():
     if _EVAL_MOD not in _saved:
         return
@@ -222,14 +257,15 @@ def _uninstall_resnet18():
 
 
 def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False,
-            evaluation: bool = False):
+            evaluation: bool = False, validation: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
     ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
     ``heatmaps=True`` also binds ``WholeSlideImage.visHeatmap`` where the reference's ``wsi_core`` imports (else a no-op).
     ``resnet18=True`` also binds ``models.resnet_custom.resnet18_baseline`` to ``resnet18.resnet18_baseline`` (the HistoResNet-18
     extractor), on the module ``resnet=True`` mapped or on the reference's own.
-    ``evaluation=True`` also binds ``utils.eval_utils.summary`` to ``evaluate.evaluate_split`` where that module imports (else a no-op)."""
+    ``evaluation=True`` also binds ``utils.eval_utils.summary`` to ``evaluate.evaluate_split`` where that module imports (else a no-op).
+    ``validation=True`` also binds ``utils.core_utils.validate_clam`` to ``evaluate.validate_split`` where that module imports (else a no-op)."""
     done = {}
     if heatmaps and _install_heatmaps(verbose):
         done[_WSI_MOD + ".WholeSlideImage.visHeatmap"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.vis_heatmap"
@@ -270,10 +306,13 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False,
         done[_RESNET18_KEY] = f"{pkg}.resnet18.resnet18_baseline"
     if evaluation and _install_evaluation(verbose):
         done[_EVAL_MOD + ".summary"] = f"{pkg}.evaluate.evaluate_split"
+    if validation and _install_validation(verbose):
+        done[_VAL_MOD + ".validate_clam"] = f"{pkg}.evaluate.validate_split"
     return done
 
 
 def uninstall():
+    _uninstall_validation()
     _uninstall_evaluation()
     _uninstall_resnet18()
     _uninstall_sampling()

@@ -1,5 +1,6 @@
-"""The numeric part of the reference's ``summary()`` (utils/eval_utils.py:115-179) over a whole split, with the model called on
-many slides at once (``CLAM_SB.forward_bags``) instead of once per slide.
+"""The numeric part of the reference's ``summary()`` (utils/eval_utils.py:115-179) and of ``validate_clam``
+(utils/core_utils.py:506-597) over a whole split, with the model called on many slides at once (``CLAM_SB.forward_bags``) instead of
+once per slide.
 
 ``evaluate_split`` returns what ``summary()`` accumulates: the probabilities, labels and predictions of every slide, the mean
 error, the mean loss and the per-class correct / count pairs of ``Accuracy_Logger`` (utils/core_utils.py:17-49).  The AUC stays with
@@ -102,6 +103,125 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
         wrong += 0.0 if hit else 1.0
     return SplitResult(all_probs=probs.numpy().astype(np.float64), all_labels=np.asarray(labels, dtype=np.float64),
                        all_preds=preds.numpy().astype(np.float64), error=wrong / n, loss=loss, acc=acc)
+
+
+@dataclass
+class ValidationResult:
+    """What ``validate_clam`` (utils/core_utils.py:506-597) accumulates over a split."""
+    prob: np.ndarray             # [n, C] float64
+    labels: np.ndarray           # [n] float64
+    val_loss: float              # mean of loss_fn(logits_b, label_b).item()
+    val_error: float             # mean of calculate_error(Y_hat, label)
+    acc: List[dict] = field(default_factory=list)    # acc_logger.data: per bag class
+    val_inst_loss: float = 0.0   # mean over the bags of instance_loss.item()
+    inst_count: int = 0
+    inst: List[dict] = field(default_factory=list)   # inst_logger.data, by the counting rule of Accuracy_Logger.log_batch
+
+
+def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS, mb_one_call: bool = True) -> ValidationResult:
+    """The numbers of ``validate_clam`` for ``model`` on a split, with ``model.forward_bags(..., label=, instance_eval=True)`` called on
+    runs of at most ``max_rows_per_call`` rows (``chunk_bags``) instead of ``model(bag, label=, instance_eval=True)`` once per slide.
+    Arguments as :func:`evaluate_split`.  A ``CLAM_MB`` model runs with ``bags_one_call = mb_one_call`` for the duration of the call.
+    The AUC stays with the caller (``labels`` and ``prob`` are its inputs).  The model is put in eval mode, as ``validate_clam`` does."""
+    bags, labels = _split(bags_or_loader, labels)
+    n = len(bags)
+    if any(l < 0 or l >= n_classes for l in labels):
+        raise ValueError(f"labels must lie in [0, {n_classes})")
+    if loss_fn is None:
+        loss_fn = F.cross_entropy
+    params = list(model.parameters())
+    dev = params[0].device if params else bags[0].device
+    logits = torch.empty((n, n_classes), dtype=torch.float32)
+    probs = torch.empty((n, n_classes), dtype=torch.float32)
+    preds = torch.empty((n,), dtype=torch.int64)
+    inst_loss = torch.empty((n,), dtype=torch.float32)
+    inst = [{"count": 0, "correct": 0} for _ in range(n_classes)]
+    had = hasattr(type(model), "bags_one_call")
+    before = model.__dict__.get("bags_one_call", None)
+    if had:
+        model.bags_one_call = bool(mb_one_call)
+    model.eval()
+    try:
+        with torch.no_grad():
+            for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
+                lg, yp, yh, _, res = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
+                sl = slice(run.start, run.stop)
+                logits[sl], probs[sl], preds[sl] = lg.float().cpu(), yp.float().cpu(), yh.reshape(-1).cpu()
+                inst_loss[sl] = res["instance_loss"].float().cpu()
+                for p, t in zip(res["inst_preds"], res["inst_labels"]):     # Accuracy_Logger.log_batch, one slide at a time
+                    p, t = np.asarray(p).astype(int), np.asarray(t).astype(int)
+                    for c in np.unique(t):
+                        mask = t == c
+                        inst[c]["count"] += int(mask.sum())
+                        inst[c]["correct"] += int((p[mask] == t[mask]).sum())
+            lab = torch.tensor(labels, dtype=torch.int64)
+            loss = sum(float(loss_fn(logits[i:i + 1], lab[i:i + 1])) for i in range(n)) / n
+    finally:
+        if had:
+            if before is None:
+                del model.bags_one_call      # back to the class attribute
+            else:
+                model.bags_one_call = before
+    acc = [{"count": 0, "correct": 0} for _ in range(n_classes)]
+    wrong = 0.0
+    for i in range(n):
+        hit = int(preds[i]) == labels[i]
+        acc[labels[i]]["count"] += 1
+        acc[labels[i]]["correct"] += int(hit)
+        wrong += 0.0 if hit else 1.0
+    return ValidationResult(prob=probs.numpy().astype(np.float64), labels=np.asarray(labels, dtype=np.float64), val_loss=loss,
+                            val_error=wrong / n, acc=acc, val_inst_loss=sum(float(v) for v in inst_loss) / n, inst_count=n, inst=inst)
+
+
+def validate_clam_like(ref_module, max_rows_per_call: int = DEFAULT_MAX_ROWS) -> Callable:
+    """A function with the signature and the four results of ``ref_module.validate_clam`` (``utils.core_utils``) whose numbers come
+    from :func:`validate_split`: the writer scalars and the early-stopping call (checkpoint name, early_stopping file) included;
+    one line is printed per call.  The AUC and the logger
+    objects are made with that module's own imports (sklearn, ``Accuracy_Logger``)."""
+    m = ref_module
+
+    def validate_clam(cur, epoch, model, loader, n_classes, early_stopping=None, writer=None, loss_fn=None, results_dir=None):
+        import os
+        r = validate_split(model, loader, None, n_classes, loss_fn, max_rows_per_call)
+        acc_logger, inst_logger = m.Accuracy_Logger(n_classes=n_classes), m.Accuracy_Logger(n_classes=n_classes)
+        acc_logger.data = [dict(d) for d in r.acc]
+        inst_logger.data = [dict(d) for d in r.inst]
+        if n_classes == 2:
+            auc = m.roc_auc_score(r.labels, r.prob[:, 1])
+        else:
+            onehot = m.label_binarize(r.labels, classes=list(range(n_classes)))
+            per = []
+            for c in range(n_classes):
+                if c in r.labels:
+                    fpr, tpr, _ = m.roc_curve(onehot[:, c], r.prob[:, c])
+                    per.append(m.calc_auc(fpr, tpr))
+                else:
+                    per.append(float("nan"))
+            auc = np.nanmean(np.array(per))
+        scalars = {"val/loss": r.val_loss, "val/auc": auc, "val/error": r.val_error, "val/inst_loss": r.val_inst_loss}
+        for c in range(n_classes):
+            a = acc_logger.get_summary(c)[0]
+            if a is not None:
+                scalars[f"val/class_{c}_acc"] = a
+        print(f"validation {epoch}: loss {r.val_loss:.4f} error {r.val_error:.4f} auc {auc:.4f} instance loss {r.val_inst_loss:.4f}; "
+              "bags " + " ".join(f"{d['correct']}/{d['count']}" for d in r.acc) + "; instances " +
+              " ".join(f"{d['correct']}/{d['count']}" for d in r.inst[:2]))
+        if writer:
+            for name, v in scalars.items():
+                writer.add_scalar(name, v, epoch)
+        if early_stopping:
+            assert results_dir
+            early_stopping(epoch, r.val_loss, model, ckpt_name=os.path.join(results_dir, "s_{}_checkpoint.pt".format(cur)))
+            if early_stopping.early_stop:
+                with open(os.path.join(results_dir, "early_stopping{}.txt".format(cur)), "w") as f:
+                    f.write("Finished at epoch {}".format(epoch))
+                print("Early stopping")
+                return True, r.val_error, r.val_loss, auc
+        return False, r.val_error, r.val_loss, auc
+
+    validate_clam.__hipt_amd__ = True
+    return validate_clam
 
 
 def summary_like(ref_module, max_rows_per_call: int = DEFAULT_MAX_ROWS) -> Callable:

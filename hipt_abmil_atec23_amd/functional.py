@@ -138,3 +138,48 @@ def clam_sb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_on
     N.call("hipt_clam_sb_forward_bags", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw),
            N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
     return out
+
+
+def clam_mb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_mb_forward_bags``: :func:`clam_sb_forward_bags` for the ``K = w.n_att`` branches of a stacked ``CLAM_MB`` weight image.
+    Returns ``(A_raw [K, rows], M [B, K, S1], logits [B, K], Y_prob [B, K], Y_hat [B])``; bag ``b`` is the columns
+    ``[offsets[b], offsets[b+1])`` of ``A_raw``."""
+    import ctypes as C
+    N.require_cuda(cat, "clam_mb_forward_bags")
+    dev, B, rows, K = cat.device, len(offsets), cat.shape[0], w.n_att
+    if cat.dim() != 2 or not cat.is_contiguous() or cat.dtype != _TORCH_DT[w.dtype] or cat.shape[1] != w.s0:
+        raise ValueError(f"expected contiguous [rows, {w.s0}] bags in {_TORCH_DT[w.dtype]}, got {tuple(cat.shape)} {cat.dtype}")
+    if offsets.host[-1] != rows:
+        raise ValueError(f"bag offsets end at {offsets.host[-1]} but the concatenated bags have {rows} rows")
+    N.same_device("clam_mb_forward_bags", dev, offsets.dev)
+    st = N.stream_ptr(dev)
+    if ws is None:
+        ws = workspace(dev, N.lib().hipt_clam_mb_bags_workspace_bytes(C.byref(w), B, rows), ("clam_bags", st.value))
+    if out is None:
+        e = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        out = (e(K, rows), None, None, None, None) if attention_only else (e(K, rows), e(B, K, w.s1), e(B, K), e(B, K), e(B, dt=torch.int64))
+    A_raw, M, logits, Y_prob, Y_hat = out
+    N.call("hipt_clam_mb_forward_bags", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw),
+           N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
+    return out
+
+
+def topk_segments(A: torch.Tensor, offsets: BagOffsets, k: int, want_global: bool = True):
+    """``hipt_topk_segments`` on the scores of a multi-bag call, ``A [rows]`` or ``[K, rows]`` fp32: ``(ids, global_ids)``, int64
+    ``[B, K, 2, k]`` each -- per bag and branch the ids of the k largest and of the k smallest scores (ties: lowest index first),
+    bag-local and as rows of the concatenated matrix (None unless ``want_global``).  A bag with fewer than ``k`` rows raises
+    before anything is launched, with the text of ``torch.topk`` in ``forward``."""
+    N.require_cuda(A, "topk_segments")
+    A2 = A.reshape(1, -1) if A.dim() == 1 else A
+    if A2.dim() != 2 or A2.dtype != torch.float32 or not A2.is_contiguous() or A2.shape[1] != offsets.host[-1]:
+        raise ValueError(f"expected contiguous fp32 scores [K, {offsets.host[-1]}], got {tuple(A.shape)} {A.dtype}")
+    for b in range(len(offsets)):
+        n = offsets.host[b + 1] - offsets.host[b]
+        if k > n:
+            raise RuntimeError(f"selected index k out of range: k_sample={k} > {n} rows (torch.topk, model_clam.py:120)")
+    N.same_device("topk_segments", A.device, offsets.dev)
+    B, K = len(offsets), A2.shape[0]
+    ids = torch.empty((B, K, 2, k), dtype=torch.int64, device=A.device)
+    gids = torch.empty_like(ids) if want_global else None
+    N.call("hipt_topk_segments", N.ptr(A2), A2.shape[1], N.ptr(offsets.dev), B, K, k, N.ptr(ids), N.ptr(gids), N.stream_ptr(A.device))
+    return ids, gids

@@ -64,6 +64,17 @@ def _all_on_cpu(module, x) -> bool:
     return not x.is_cuda and not any(p.is_cuda for p in module.parameters())
 
 
+def _tree_sum(x):
+    """Sum over the last dimension by halving it with elementwise additions: every output is the same sequence of roundings whatever
+    the other dimensions hold."""
+    while x.shape[-1] > 1:
+        n = x.shape[-1]
+        half = (n + 1) // 2
+        lo, hi = x[..., :n // 2] + x[..., half:], x[..., n // 2:half]
+        x = torch.cat([lo, hi], dim=-1) if n % 2 else lo
+    return x[..., 0]
+
+
 def _cast_shared(code, fc1, gated):
     """[Wa; Wb] and W1 in the compute dtype with their fp32 biases: what the K branches of ``CLAM_MB`` share (``fc1`` None: the head alone)."""
     wa, wb = gated.attention_a[0], gated.attention_b[0]
@@ -519,48 +530,176 @@ class CLAM_SB(WeightImageCache, nn.Module):
         cat = torch.cat(bags, dim=0)  # ONE concatenation, on the bags' device
         return cat, (Fn.BagOffsets(host, acc, cat.device) if cat.is_cuda else tuple(host))
 
-    def forward_bags(self, bags, attention_only=False, return_features=False):
+    def forward_bags(self, bags, attention_only=False, return_features=False, label=None, instance_eval=False):
         """``forward`` over B bags at once, inference only (no autograd; dropout inactive as in ``eval()``).
 
         ``bags``: a sequence of ``[N_b, S0]`` tensors, or ``(cat [sum N_b, S0], offsets)`` with the B+1 row offsets as a list, a
         tensor or a ``functional.BagOffsets``.  Returns ``logits [B, C]``, ``Y_prob [B, C]``, ``Y_hat [B, 1]``, ``A_raw`` as a
         list of ``[1, N_b]`` views of one buffer and ``{'features': M [B, S1]}`` when asked (``attention_only``: the list alone).
-        Where the library has the multi-bag form (``hipt_clam_bags_supported``) this is ONE native call whose per-bag results do
-        not depend on the other bags; elsewhere -- other widths, ``CLAM_MB``, the ungated head, CPU tensors -- it loops over
-        ``forward`` and returns the same structure.  ``bags_route`` tells which."""
+        Where the library has the multi-bag form (``hipt_clam_bags_supported``; for ``CLAM_MB`` with ``bags_one_call`` set,
+        ``hipt_clam_mb_bags_supported``: ``A_raw`` is then a list of ``[K, N_b]`` views and the features are ``[B, K, S1]``) this is
+        ONE native call whose per-bag results do not depend on the other bags; elsewhere -- other widths, ``CLAM_MB`` without
+        ``bags_one_call``, the ungated head, CPU tensors -- it loops over ``forward`` and returns the same structure.
+        ``bags_route`` tells which.
+
+        ``instance_eval=True`` with ``label`` (B class ids: a list, a numpy array or a tensor) adds what ``forward(h, label=,
+        instance_eval=True)`` returns per bag (validate_clam, utils/core_utils.py:506-560): ``instance_loss`` (a ``[B]`` tensor),
+        ``inst_preds`` and ``inst_labels`` (lists of B numpy arrays, in the order of ``_instance_branch``: classes ascending).  On
+        the ``'bags'`` route that is one segmented top-k, one gather of the selected h1 rows of the concatenated bags, the instance
+        classifiers over all selected rows and ONE read-back for the call (a ``label`` tensor on the device together with an
+        ``instance_loss_fn`` other than the default ``nn.CrossEntropyLoss`` costs a second one: hand the labels over on the host)."""
         cat, off = self._bags_input(bags)
         if self.training and _needs_autograd(self, cat):
             raise RuntimeError("forward_bags is inference only: in training mode, with gradients asked for, call forward(h) bag by bag")
+        host = off.host if isinstance(off, Fn.BagOffsets) else off
+        inst = instance_eval and not attention_only
+        if inst:
+            lab = self._bag_labels(label, len(host) - 1)
+            for b in range(len(host) - 1):  # before anything is launched, as torch.topk in forward
+                if self.k_sample > host[b + 1] - host[b]:
+                    raise RuntimeError(f"selected index k out of range: k_sample={self.k_sample} > {host[b + 1] - host[b]} rows (torch.topk, model_clam.py:120)")
         with torch.no_grad():
             w = None
-            if self._gate and not self._multi and cat.is_cuda:
-                w = self._pack(cat.device)
-                if not N.lib().hipt_clam_bags_supported(C_.byref(w)):
-                    w = None
+            if self._gate and cat.is_cuda:
+                if not self._multi:
+                    w = self._pack(cat.device)
+                    if not N.lib().hipt_clam_bags_supported(C_.byref(w)):
+                        w = None
+                elif self.bags_one_call:
+                    w = self._pack_stacked(cat.device)
+                    if not N.lib().hipt_clam_mb_bags_supported(C_.byref(w)):
+                        w = None
             if w is None:
-                return self._forward_bags_loop(cat, off.host if isinstance(off, Fn.BagOffsets) else off, attention_only, return_features)
+                return self._forward_bags_loop(cat, host, attention_only, return_features, lab if inst else None)
             self._bags_route = "bags"
-            A_raw, M, logits, Y_prob, Y_hat = Fn.clam_sb_forward_bags(w, Fn.as_compute(cat, w.dtype), off, attention_only)
-            views = [A_raw[off.host[b]:off.host[b + 1]].view(1, -1) for b in range(len(off))]
+            x = Fn.as_compute(cat, w.dtype)
+            B = len(off)
+            if self._multi:
+                A_raw, M, logits, Y_prob, Y_hat = Fn.clam_mb_forward_bags(w, x, off, attention_only)
+                views = [A_raw[:, host[b]:host[b + 1]] for b in range(B)]
+            else:
+                A_raw, M, logits, Y_prob, Y_hat = Fn.clam_sb_forward_bags(w, x, off, attention_only)
+                views = [A_raw[host[b]:host[b + 1]].view(1, -1) for b in range(B)]
             if attention_only:
                 return views
-            return logits, Y_prob, Y_hat.view(-1, 1), views, ({'features': M} if return_features else {})
+            results = self._instance_bags(w, x, off, A_raw, lab) if inst else {}
+            if return_features:
+                results['features'] = M
+            return logits, Y_prob, Y_hat.view(-1, 1), views, results
 
-    def _forward_bags_loop(self, cat, host, attention_only, return_features):
+    def _bag_labels(self, label, B):
+        """``label`` of ``forward_bags`` as (list of B ints or None, int64 [B] tensor or None): the host form where the caller has it there."""
+        if label is None:
+            raise ValueError("forward_bags(instance_eval=True) needs the B class ids in `label`")
+        if isinstance(label, torch.Tensor) and label.is_cuda:
+            lab = label.detach().reshape(-1).long()
+            if lab.numel() != B:
+                raise ValueError(f"{B} bags but {lab.numel()} labels")
+            return None, lab
+        flat = (label.detach().reshape(-1).tolist() if isinstance(label, torch.Tensor) else
+                np.asarray(label).reshape(-1).tolist() if isinstance(label, np.ndarray) else
+                [int(l.reshape(-1)[0]) if isinstance(l, (torch.Tensor, np.ndarray)) else int(l) for l in label])
+        flat = [int(l) for l in flat]
+        if len(flat) != B:
+            raise ValueError(f"{B} bags but {len(flat)} labels")
+        if any(l < 0 or l >= self.n_classes for l in flat):
+            raise ValueError(f"labels must lie in [0, {self.n_classes})")
+        return flat, None
+
+    def _default_instance_loss(self) -> bool:
+        f = self.instance_loss_fn
+        return (type(f) is nn.CrossEntropyLoss and f.weight is None and f.reduction == "mean" and f.ignore_index == -100 and
+                getattr(f, "label_smoothing", 0.0) == 0.0)
+
+    def _instance_bags(self, w, x, off, A_raw, lab):
+        """The instance branch (:156-178 / :234-245) of every bag of a ``'bags'``-route call.  Softmax is monotone, so the top-k ids of
+        A_raw are those of softmax(A_raw); classifier c reads the rows selected by branch c (``CLAM_MB``) or by the one branch."""
+        lab_host, lab_dev = lab
+        dev, B, k, C, S1 = x.device, len(off), self.k_sample, self.n_classes, self._sizes[1]
+        Ka = w.n_att if self._multi else 1
+        _, gids = Fn.topk_segments(A_raw, off, k)
+        rows = torch.empty((B, Ka, 2 * k, S1), dtype=torch.float32, device=dev)
+        N.call("hipt_clam_gather_h1", C_.byref(w), N.ptr(x), N.ptr(gids), B * Ka * 2 * k, N.ptr(rows), N.stream_ptr(dev))
+        # classifier c on the 2k rows of its branch, for every bag: [B, C, 2k, 2]; inst_eval_out reads the first k of them.  Products and
+        # pairwise sums are elementwise kernels, so a bag's numbers do not depend on the other bags of the call (a GEMM's blocking may)
+        Wi = torch.stack([cl.weight for cl in self.instance_classifiers]).float()            # [C, 2, S1]
+        bi = torch.stack([cl.bias for cl in self.instance_classifiers]).float()              # [C, 2]
+        sel = rows if self._multi else rows.expand(B, C, 2 * k, S1)
+        L = _tree_sum(sel.unsqueeze(3) * Wi.view(1, C, 1, 2, S1)) + bi.view(1, C, 1, 2)
+        preds = torch.topk(L, 1, dim=-1)[1].squeeze(-1)                       # [B, C, 2k]
+        t_in = torch.cat([self.create_positive_targets(k, dev), self.create_negative_targets(k, dev)], dim=0)
+        t_out = self.create_negative_targets(k, dev)
+        if lab_dev is None:
+            lab_dev = torch.tensor(lab_host, dtype=torch.int64, device=dev)
+        elif not self._default_instance_loss():
+            lab_host = lab_dev.tolist()
+        total = torch.zeros((B,), dtype=torch.float32, device=dev)
+        if self._default_instance_loss():
+            # cross-entropy of two logits per row, written out: -log softmax = logsumexp - the target's logit
+            l0, l1 = L[..., 0], L[..., 1]
+            mx = torch.maximum(l0, l1)
+            lse = mx + torch.log(torch.exp(l0 - mx) + torch.exp(l1 - mx))
+            ce_in = _tree_sum(torch.cat([(lse - l1)[..., :k], (lse - l0)[..., k:]], dim=-1)) / (2 * k)    # [B, C]: targets 1 x k, 0 x k
+            ce_out = _tree_sum((lse - l0)[..., :k]) / k                                                   # targets 0 x k
+            for c in range(C):   # classes ascending, as _instance_branch accumulates
+                mine = lab_dev == c
+                total = total + torch.where(mine, ce_in[:, c], ce_out[:, c] if self.subtyping else torch.zeros_like(total))
+        else:
+            per = []
+            for b in range(B):
+                acc = 0.0
+                for c in range(C):
+                    if lab_host[b] == c:
+                        acc = acc + self.instance_loss_fn(L[b, c], t_in)
+                    elif self.subtyping:
+                        acc = acc + self.instance_loss_fn(L[b, c, :k], t_out)
+                per.append(acc if isinstance(acc, torch.Tensor) else torch.zeros((), device=dev))
+            total = torch.stack([p.reshape(()).float() for p in per])
+        if self.subtyping:
+            total = total / C
+        back = torch.cat([preds.reshape(-1), lab_dev]).cpu().numpy()         # THE read-back of the call
+        p_host, lab_np = back[:B * C * 2 * k].reshape(B, C, 2 * k), back[B * C * 2 * k:]
+        if lab_host is None and (lab_np.min() < 0 or lab_np.max() >= C):
+            raise ValueError(f"labels must lie in [0, {C})")
+        t_in_np = np.concatenate([np.ones(k, dtype=np.int64), np.zeros(k, dtype=np.int64)])
+        inst_preds, inst_labels = [], []
+        for b in range(B):
+            ps, ts = [], []
+            for c in range(C):
+                if int(lab_np[b]) == c:
+                    ps.append(p_host[b, c])
+                    ts.append(t_in_np)
+                elif self.subtyping:
+                    ps.append(p_host[b, c, :k])
+                    ts.append(t_in_np[k:])
+            inst_preds.append(np.concatenate(ps))
+            inst_labels.append(np.concatenate(ts))
+        return {'instance_loss': total, 'inst_labels': inst_labels, 'inst_preds': inst_preds}
+
+    def _forward_bags_loop(self, cat, host, attention_only, return_features, lab=None):
         self._bags_route = "per_bag"
         was_training = self.training
         self.train(False)
         try:
-            outs = [self.forward(cat[host[b]:host[b + 1]], attention_only=attention_only, return_features=return_features)
-                    for b in range(len(host) - 1)]
+            if lab is None:
+                outs = [self.forward(cat[host[b]:host[b + 1]], attention_only=attention_only, return_features=return_features)
+                        for b in range(len(host) - 1)]
+            else:
+                labels = lab[0] if lab[0] is not None else lab[1].tolist()
+                outs = [self.forward(cat[host[b]:host[b + 1]], label=torch.tensor([labels[b]], dtype=torch.int64, device=cat.device),
+                                     instance_eval=True, return_features=return_features) for b in range(len(host) - 1)]
         finally:
             self.train(was_training)
         if attention_only:
             return outs
         results = {'features': (torch.stack if self._multi else torch.cat)([o[4]['features'] for o in outs], dim=0)} if return_features else {}
+        if lab is not None:
+            results['instance_loss'] = torch.stack([torch.as_tensor(o[4]['instance_loss'], dtype=torch.float32, device=cat.device).reshape(())
+                                                    for o in outs])
+            results['inst_preds'] = [o[4]['inst_preds'] for o in outs]
+            results['inst_labels'] = [o[4]['inst_labels'] for o in outs]
         return (torch.cat([o[0] for o in outs], dim=0), torch.cat([o[1] for o in outs], dim=0), torch.cat([o[2] for o in outs], dim=0),
                 [o[3] for o in outs], results)
-
 
 
 class CLAM_MB(CLAM_SB):
@@ -574,6 +713,7 @@ class CLAM_MB(CLAM_SB):
 
     _multi = True
     one_pass = True  # inference takes hipt_clam_mb_forward (one pass over the bag for all branches) where the library has it; False: branch by branch
+    bags_one_call = False  # forward_bags takes hipt_clam_mb_forward_bags (all bags, all branches in one call) where the library has it; False: the loop over forward
 
     def __init__(self, gate=True, size_arg="small", dropout=0.0, k_sample=8, n_classes=2,
                  instance_loss_fn=nn.CrossEntropyLoss(), subtyping=False):
@@ -590,7 +730,7 @@ class CLAM_MB(CLAM_SB):
             out += [c.weight, c.bias]
         return out
 
-    def _pack_branches(self, device):
+    def _pack_branches(self, device, stacked=False):
         """``(ws, mb)``: one ``hipt_clam_weights`` per attention branch for the inference kernels -- shared W1 / [Wa; Wb] tensors, the
         branch's row of ``attention_c`` and its ``Linear(S1, 1)`` as a one-class bag classifier -- and the stacked struct of the one-pass
         kernel, or None where the library does not take the configuration (cached like ``_pack``)."""
@@ -608,7 +748,13 @@ class CLAM_MB(CLAM_SB):
                                      bound=max(bounds), image=2 <= K <= 4)
             mb = wm if wm.stream_pk and N.lib().hipt_clam_mb_supported(C_.byref(wm)) else None
             return [w for w, _ in made], mb, (made, wm, keep)
-        return self._cached(device, ("mb",), build)[:2]
+        full = self._cached(device, ("mb",), build)
+        return full[2][1] if stacked else full[:2]
+
+    def _pack_stacked(self, device):
+        """The stacked K-branch struct of ``_pack_branches`` (``wm``: wc [K, S2], bc [K], the K one-row classifiers [K, S1]) whatever the
+        one-pass streaming kernel says about it: what ``hipt_clam_mb_forward_bags`` takes.  The same cache entry."""
+        return self._pack_branches(device, stacked=True)
 
     def _multi_infer(self, h, label, instance_eval, return_features, attention_only):
         """model_clam.py:226-264 without autograd: A [K, N] -> softmax over N per branch -> M [K, S1] -> logits[0, c] =

@@ -387,6 +387,23 @@ int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, cons
                               int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                               void* workspace, size_t ws_bytes, void* stream);
 
+/* CLAM_MB.forward (model_clam.py:226-264) over B bags in ONE call: hipt_clam_sb_forward_bags for the K = w->n_att attention branches of a
+ * hipt_clam_weights stacked as hipt_clam_mb_forward takes it (wc [K, S2], bc [K], wcls [K, S1], bcls [K], n_classes = K; stream_pk and
+ * logit_bound are not read).  bags / offsets_dev / B / total_rows / workspace rules, the three plain launches, the absence of atomics,
+ * tickets and workspace state, graph capture and the bit-for-bit independence of a bag from the other bags of the call: as there.
+ * Outputs fp32: A_raw [K, total_rows] -- branch k of row m at A_raw[k * total_rows + m], so bag b is the [K, N_b] window of columns
+ * [offsets[b], offsets[b+1]) with row stride total_rows --, M [B, K, S1], logits [B, K] (logits[b, k] = wcls[k] . M[b, k] + bcls[k],
+ * :248-250), Y_prob [B, K] = softmax over the K logits, Y_hat int64 [B] = their first maximum.  attention_only != 0: A_raw alone.
+ * hipt_clam_mb_bags_supported(w) != 0: hipt_clam_bags_supported(w) and 2 <= n_att <= 4 and n_att == n_classes; otherwise
+ * HIPT_E_UNSUPPORTED and hipt_clam_mb_bags_workspace_bytes = 0.  HIPT_E_BADARG, before anything is launched, for a null pointer, a
+ * misaligned `bags`, B < 1, total_rows < B and a workspace smaller than hipt_clam_mb_bags_workspace_bytes(w, B, total_rows) or not
+ * 256-byte aligned. */
+int hipt_clam_mb_bags_supported(const hipt_clam_weights* w);
+size_t hipt_clam_mb_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
+int hipt_clam_mb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                              int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                              void* workspace, size_t ws_bytes, void* stream);
+
 /* CLAM_MB.forward (model_clam.py:226-264), inference, with ONE pass over the bag for all K = w->n_att attention branches (2 <= K <= 4; W1 and
  * [Wa; Wb] are shared by the branches, only wc / bc / the classifier rows differ):  A_raw[K, N] = the K logits of every row;
  * M[K, S1] = softmax_N(A_raw[k]) h1;  logits[K]: logits[k] = wcls[k] . M[k] + bcls[k] (:248-250; Y_prob / Y_hat are K numbers: the caller's).
@@ -467,6 +484,16 @@ int hipt_clam_train_backward(const hipt_clam_train_weights* w, const float* bag,
 /* torch.topk(A, k) and torch.topk(-A, k) of every row of A [rows, N] on the device (inst_eval, :120-123):
  * ids int64 [rows, 2, k], descending / ascending by value, ties -> lowest index first. */
 int hipt_topk_rows(const float* A, int rows, int N, int k, int64_t* ids, void* stream);
+
+/* hipt_topk_rows over the bags of a multi-bag call (the instance branch of validate_clam, one launch per call instead of one per slide).
+ * A: the scores of hipt_clam_sb_forward_bags (K = 1, row_stride = total_rows) or hipt_clam_mb_forward_bags (K branches, row_stride =
+ * total_rows): branch r of bag b is the offsets[b+1] - offsets[b] numbers at A + r * row_stride + offsets[b]; offsets_dev: int64 [B + 1] in
+ * device memory.  ids int64 [B, K, 2, k]: for every bag and branch what hipt_topk_rows returns on that row alone (bag-local ids, the k
+ * largest then the k smallest, ties -> lowest index first).  global_ids (may be NULL) int64 [B, K, 2, k]: the same ids plus offsets[b],
+ * i.e. rows of the concatenated matrix, ready for hipt_clam_gather_h1.  One workgroup per (bag, branch).  A bag with fewer than k rows is
+ * the caller's error (check the offsets on the host): every access stays in bounds and its ids are -1. */
+int hipt_topk_segments(const float* A, int64_t row_stride, const int64_t* offsets_dev, int B, int K, int k, int64_t* ids,
+                       int64_t* global_ids, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Region augmentation (extract_features_fp.py:89-136, --use_transforms HIPT_*): uint8 RGB in, uint8 out, one parameter

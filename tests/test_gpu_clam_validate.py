@@ -1,0 +1,428 @@
+"""GPU tests (-m gpu) of the validation pass over many bags: the K-branch multi-bag forward (csrc/abmil_bags.hip,
+``CLAM_MB.forward_bags`` with ``bags_one_call``), the segmented top-k (csrc/clam_train.hip), the instance branch batched over the bags
+of a call and ``evaluate.validate_split``.
+
+Forward tests run on ``ROWS`` (1 787 rows, 18 work units): bag boundaries before, on and after tile boundaries, and a last bag of
+1 100 rows = 9 tiles, so that the combine's ``t + 8`` stride adds a second term to its first part.  Instance tests run on ``ROWS_I``
+with ``k_sample = 8``: the 8-row bag selects every row twice.
+
+bf16: worst |error| per output against the fp64 restatement (tests/clam_mb_ref.py) on the bf16-rounded bag and bf16-rounded W1 / Wa /
+Wb, over the seven bags of ROWS (seed 21, K = 2), measured on an MI355X with ``measure_bf16(route, size)``.  The per-bag path is
+``CLAM_MB.forward`` with ``bags_one_call = False`` (code this change does not touch); the bar of the one-call path is TWICE its figure.
+  [384,128,64]: per bag (hipt_clam_mb_forward, the one-pass streaming kernel)    A_raw 9.171e-3  M 3.487e-3  logits 4.959e-4  Y_prob 1.059e-4
+                forward_bags, one call                                          A_raw 9.172e-3  M 6.420e-4  logits 3.198e-4  Y_prob 8.939e-5
+  [192, 64,32]: per bag (hipt_clam_sb_forward per branch, the fused kernel)      A_raw 9.077e-3  M 5.448e-3  logits 1.645e-3  Y_prob 1.666e-4
+                forward_bags, one call                                          A_raw 9.077e-3  M 2.004e-3  logits 8.521e-4  Y_prob 7.673e-5
+The smallest gap between the reference's two largest logits over the bags is 0.206 at [384,128,64] and 0.125 at [192,64,32], far above
+the logit bars, so equality of Y_hat is a statement about the kernels; every Y_hat agrees.  M: both per-bag paths pool a bf16 image
+of h1; the one-call path pools fp32 h1 (section 16's POOL32 path).
+"""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import clam_mb_ref as R
+from hipt_abmil_atec23_amd import CLAM_MB, CLAM_SB, _native as N
+from hipt_abmil_atec23_amd import functional as Fn
+from hipt_abmil_atec23_amd import synth
+from hipt_abmil_atec23_amd.evaluate import validate_split
+from oracle import hipt_oracle as O
+from test_clam_validate_host import per_slide_loop
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROWS = (1, 127, 128, 129, 300, 2, 1100)
+ROWS_I = (8, 9, 127, 128, 129, 300)
+SIZES = [(384, 128, 64), (192, 64, 32)]
+TOL = 1e-4           # the project's fp32 bar
+OUTS = ("A_raw", "M", "logits", "Y_prob")
+FENCE, FILL = 4096, 0xA5
+BF16_SEED = 21
+BF16_PER_BAG = {
+    (384, 128, 64): {"A_raw": 9.172e-3, "M": 3.488e-3, "logits": 4.959e-4, "Y_prob": 1.059e-4},
+    (192, 64, 32): {"A_raw": 9.077e-3, "M": 5.448e-3, "logits": 1.646e-3, "Y_prob": 1.667e-4},
+}
+INST_SEED = {CLAM_SB: 50, CLAM_MB: 50}   # seeds whose reference top-k gaps exceed GAP (checked on the CPU, asserted below)
+GAP = 1e-3           # ten times the A_raw bar
+
+
+def md(a, b):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return float(np.abs(a.astype(np.float64).reshape(-1) - np.asarray(b, dtype=np.float64).reshape(-1)).max())
+
+
+def bits(t):
+    return t.detach().contiguous().cpu().numpy().tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def make(size, dtype="fp32", cls=CLAM_MB, n_classes=2, subtyping=False):
+    m = cls(size_arg=list(size), n_classes=n_classes, subtyping=subtyping)
+    m.load_state_dict(synth.make_state_dict(synth.clam_param_specs(size, n_classes=n_classes, multi=cls is CLAM_MB), size[0]), strict=True)
+    m.relocate()
+    m.bags_one_call = True   # (an instance attribute; CLAM_SB ignores it)
+    return m.eval().set_compute_dtype(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def params64(size, n_classes=2, multi=True, rounded=False):
+    out = {}
+    for k, v in synth.make_params_np(synth.clam_param_specs(size, n_classes=n_classes, multi=multi), size[0]).items():
+        if rounded and k.endswith("weight") and ("attention_net.0." in k or "attention_a" in k or "attention_b" in k):
+            v = torch.from_numpy(np.ascontiguousarray(v)).bfloat16().float().numpy()   # what the kernels read in bf16 mode
+        out[k] = v.astype(np.float64)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def bags_of(s0, seed, rows=ROWS):
+    cat = synth.hash_uniform_torch((sum(rows), s0), seed, device=DEV)
+    return tuple(cat.split(list(rows), dim=0))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(size, seed, n_classes=2, rounded=False, rows=ROWS):
+    """The fp64 restatement on every bag ALONE (``rounded``: on the bf16-rounded bag and weights)."""
+    p = params64(size, n_classes, True, rounded)
+    return [R.clam_mb_forward((b.bfloat16() if rounded else b).double().cpu().numpy(), p) for b in bags_of(size[0], seed, rows)]
+
+
+def run_bags(m, bags, **kw):
+    logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True, **kw)
+    assert m.bags_route == "bags"
+    torch.cuda.synchronize()
+    return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat, "res": res}
+
+
+def run_per_bag(m, bags):
+    m.bags_one_call = False
+    try:
+        with torch.no_grad():
+            outs = [m(b, return_features=True) for b in bags]
+    finally:
+        m.bags_one_call = True
+    torch.cuda.synchronize()
+    return {"A_raw": [o[3] for o in outs], "M": torch.stack([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
+            "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
+
+
+def per_bag(out, b):
+    return {"A_raw": out["A_raw"][b], "M": out["M"][b], "logits": out["logits"][b:b + 1], "Y_prob": out["Y_prob"][b:b + 1],
+            "Y_hat": out["Y_hat"][b:b + 1]}
+
+
+def errors(out, refs):
+    worst, wrong = {k: 0.0 for k in OUTS}, []
+    for b, r in enumerate(refs):
+        got = per_bag(out, b)
+        for k in OUTS:
+            assert tuple(got[k].shape) == r[k].shape, (k, got[k].shape, r[k].shape)
+            worst[k] = max(worst[k], md(got[k], r[k]))
+        if int(got["Y_hat"].reshape(-1)[0]) != int(r["Y_hat"].reshape(-1)[0]):
+            wrong.append(b)
+    return worst, wrong
+
+
+def assert_same_bits(a, b, what):
+    for k in (*OUTS, "Y_hat"):
+        assert a[k].shape == b[k].shape and bits(a[k]) == bits(b[k]), f"{what}: {k} differs"
+
+
+# ---------------------------------------------------------------- 1. fp32 parity
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("K", [2, 3])
+def test_fp32_parity_per_bag(size, K):
+    m = make(size, "fp32", CLAM_MB, K)
+    bags = bags_of(size[0], 3)
+    m.forward_bags(list(bags[:1]))   # the weight image exists
+    before = N.calls
+    out = run_bags(m, bags)
+    assert N.calls == before + 1, "one native call for the whole set"
+    B = len(ROWS)
+    assert out["logits"].shape == (B, K) and out["Y_hat"].shape == (B, 1) and out["Y_hat"].dtype == torch.int64 and out["M"].shape == (B, K, size[1])
+    assert [tuple(a.shape) for a in out["A_raw"]] == [(K, n) for n in ROWS]
+    worst, wrong = errors(out, reference(size, 3, K))
+    print(f"CLAM_MB forward_bags fp32 {size} K={K}: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert all(v <= TOL for v in worst.values()), worst
+    assert wrong == []
+
+
+# ---------------------------------------------------------------- 2. bf16 parity
+def measure_bf16(route, size):
+    m = make(size, "bf16")
+    bags = bags_of(size[0], BF16_SEED)
+    out = run_bags(m, bags) if route == "bags" else run_per_bag(m, bags)
+    refs = reference(size, BF16_SEED, 2, True)
+    worst, wrong = errors(out, refs)
+    return worst, wrong, refs
+
+
+@pytest.mark.parametrize("size", SIZES)
+def test_bf16_parity_per_bag(size):
+    worst, wrong, refs = measure_bf16("bags", size)
+    gaps = [float(np.diff(np.sort(r["logits"].reshape(-1))[-2:])[0]) for r in refs]
+    print(f"CLAM_MB forward_bags bf16 {size}: " + ", ".join(f"{k} {worst[k]:.3e}" for k in OUTS) + f"; smallest top-two logit gap {min(gaps):.3e}")
+    bars = {k: 2.0 * v for k, v in BF16_PER_BAG[size].items()}
+    for k in OUTS:
+        assert worst[k] <= bars[k], (k, worst[k], bars[k])
+    # Y_hat where the reference's two largest logits are further apart than the logit bar; at most one bag is left out
+    decided = [b for b, gap in enumerate(gaps) if gap > bars["logits"]]
+    assert len(decided) >= len(ROWS) - 1, gaps
+    assert [b for b in wrong if b in decided] == []
+
+
+# ---------------------------------------------------------------- 3. a branch is the single-branch call with that branch's weights
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_branch_k_is_the_single_branch_call(size, dtype):
+    m = make(size, dtype)
+    bags = bags_of(size[0], 5)
+    out = run_bags(m, bags)
+    ws, _ = m._pack_branches(torch.device(DEV))
+    cat = Fn.as_compute(torch.cat(bags, dim=0), ws[0].dtype)
+    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), cat.shape[0], cat.device)
+    a_all = torch.cat(out["A_raw"], dim=1)
+    same = True
+    for k, w in enumerate(ws):
+        A_raw, M, logits, _, _ = Fn.clam_sb_forward_bags(w, cat, off)
+        torch.cuda.synchronize()
+        d = (md(a_all[k], A_raw.cpu().numpy()), md(out["M"][:, k], M.cpu().numpy()), md(out["logits"][:, k], logits.cpu().numpy()))
+        same = same and bits(a_all[k]) == bits(A_raw) and bits(out["M"][:, k]) == bits(M) and bits(out["logits"][:, k]) == bits(logits.reshape(-1))
+        assert max(d) <= 1e-5, (k, d)
+    print(f"branch consistency {size} {dtype}: bit for bit equal = {same}")
+
+
+# ---------------------------------------------------------------- 4. independence, attention_only, guards, graph
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_a_bag_does_not_see_its_neighbours(dtype, monkeypatch):
+    m = make((384, 128, 64), dtype)
+    bags = bags_of(384, 9)
+    full = run_bags(m, bags)
+    rev = run_bags(m, bags[::-1])
+    monkeypatch.setenv("HIPT_BAGS_MAX_WG", "3")     # 18 units over 3 workgroups instead of one each
+    few = run_bags(m, bags)
+    monkeypatch.delenv("HIPT_BAGS_MAX_WG")
+    B = len(bags)
+    for b in range(B):
+        assert_same_bits(per_bag(full, b), per_bag(run_bags(m, [bags[b]]), 0), f"bag {b} alone")
+        assert_same_bits(per_bag(full, b), per_bag(rev, B - 1 - b), f"bag {b} reversed order")
+        assert_same_bits(per_bag(full, b), per_bag(few, b), f"bag {b} small grid")
+
+
+def fenced_buffers():
+    fenced = []
+
+    def buf(nbytes, dt=torch.uint8):
+        raw = torch.full((nbytes + 2 * FENCE,), FILL, dtype=torch.uint8, device=DEV)
+        assert raw.data_ptr() % 256 == 0
+        fenced.append((raw, nbytes))
+        return raw[FENCE:FENCE + nbytes].view(dt)
+
+    def check(untouched=()):
+        for i, (raw, n) in enumerate(fenced):
+            assert bool((raw[:FENCE] == FILL).all()) and bool((raw[FENCE + n:] == FILL).all()), "a write outside a buffer"
+            if i in untouched:
+                assert bool((raw == FILL).all()), "attention_only wrote more than A_raw"
+    return buf, check
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("attention_only", [False, True])
+def test_outputs_and_workspace_stay_inside_their_buffers(dtype, attention_only):
+    size, K = (384, 128, 64), 2
+    m = make(size, dtype)
+    w = m._pack_stacked(torch.device(DEV))
+    assert N.lib().hipt_clam_mb_bags_supported(C.byref(w)) == 1
+    bags = bags_of(384, 9)
+    cat = Fn.as_compute(torch.cat(bags, dim=0), w.dtype)
+    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), cat.shape[0], cat.device)
+    B, rows = len(ROWS), cat.shape[0]
+    need = N.lib().hipt_clam_mb_bags_workspace_bytes(C.byref(w), B, rows)
+    assert need > 0 and need % 256 == 0
+    buf, check = fenced_buffers()
+    f32 = torch.float32
+    out = (buf(K * rows * 4, f32).view(K, rows), buf(B * K * 128 * 4, f32).view(B, K, 128), buf(B * K * 4, f32).view(B, K),
+           buf(B * K * 4, f32).view(B, K), buf(B * 8, torch.int64))
+    ws = buf(need)
+    Fn.clam_mb_forward_bags(w, cat, off, attention_only=attention_only, out=out, ws=ws)
+    torch.cuda.synchronize()
+    check(untouched=(1, 2, 3, 4) if attention_only else ())
+    full = run_bags(m, bags)
+    assert bits(out[0]) == bits(torch.cat(full["A_raw"], dim=1))
+    if attention_only:
+        views = m.forward_bags(list(bags), attention_only=True)
+        assert [bits(v) for v in views] == [bits(a) for a in full["A_raw"]]
+    else:
+        assert bits(out[1]) == bits(full["M"]) and bits(out[2]) == bits(full["logits"]) and bits(out[3]) == bits(full["Y_prob"])
+        assert bits(out[4]) == bits(full["Y_hat"])
+    # a short or misaligned workspace is a bad argument, before anything is written
+    for bad in (ws[:need - 256], ws[16:]):
+        with pytest.raises(RuntimeError, match="code -?[0-9]+"):
+            Fn.clam_mb_forward_bags(w, cat, off, attention_only=attention_only, out=out, ws=bad)
+
+
+def test_one_call_is_captured_and_replayed():
+    m = make((384, 128, 64))
+    static = torch.cat(bags_of(384, 9), dim=0).clone()
+    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), static.shape[0], static.device)   # checked and uploaded BEFORE the capture
+    call = lambda: m.forward_bags((static, off), return_features=True)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        call()                                        # weight image, workspace and per-device kernel setup exist before the capture
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        logits, y_prob, y_hat, a_raw, res = call()
+    for seed in (31, 32):
+        static.copy_(torch.cat(bags_of(384, seed), dim=0))
+        g.replay()
+        torch.cuda.synchronize()
+        got = {"A_raw": torch.cat(a_raw, dim=1), "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
+        eager = run_bags(m, bags_of(384, seed))
+        eager["A_raw"] = torch.cat(eager["A_raw"], dim=1)
+        assert_same_bits(got, eager, f"replay on seed {seed}")
+
+
+# ---------------------------------------------------------------- 5. segmented top-k
+@pytest.mark.parametrize("K", [1, 2])
+def test_topk_segments_is_topk_rows_per_bag(K):
+    rows, k = (*ROWS_I, 20), 8
+    A = synth.hash_uniform_torch((K, sum(rows)), 41 + K, device=DEV).contiguous()
+    off = Fn.BagOffsets(np.cumsum([0, *rows]), sum(rows), A.device)
+    A[:, off.host[-2]:] = 0.25                       # one row repeated: every score of the last bag is equal
+    A[:, off.host[2]:off.host[2] + 5] = A[:, off.host[2] + 9:off.host[2] + 10]   # and a run of ties inside another
+    ids, gids = Fn.topk_segments(A if K > 1 else A[0], off, k)
+    torch.cuda.synchronize()
+    assert ids.shape == (len(rows), K, 2, k) and ids.dtype == torch.int64
+    for b, n in enumerate(rows):
+        seg = A[:, off.host[b]:off.host[b + 1]].contiguous()
+        one = torch.empty((K, 2, k), dtype=torch.int64, device=DEV)
+        N.call("hipt_topk_rows", N.ptr(seg), K, n, k, N.ptr(one), N.stream_ptr(seg.device))
+        torch.cuda.synchronize()
+        assert bits(ids[b]) == bits(one), f"bag {b} ({n} rows)"
+        assert bits(gids[b]) == bits(one + off.host[b])
+    assert ids[-1, :, 0].tolist() == [list(range(k))] * K and ids[-1, :, 1].tolist() == [list(range(k))] * K   # ties: lowest index first
+    assert sorted(ids[0, 0, 0].tolist()) == list(range(8)) and sorted(ids[0, 0, 1].tolist()) == list(range(8))   # the 8-row bag
+    with pytest.raises(RuntimeError, match="selected index k out of range"):
+        Fn.topk_segments(A, off, 9)
+
+
+# ---------------------------------------------------------------- 6. the instance branch on the 'bags' route
+def inst_labels(cls, n_classes=2):
+    return [b % n_classes for b in range(len(ROWS_I))]
+
+
+@pytest.mark.parametrize("cls", [CLAM_SB, CLAM_MB])
+@pytest.mark.parametrize("subtyping", [False, True])
+def test_instance_branch_is_the_per_bag_chain(cls, subtyping):
+    size, k = (384, 128, 64), 8
+    m = make(size, "fp32", cls, 2, subtyping)
+    bags = bags_of(384, 23, ROWS_I)
+    labels = inst_labels(cls)
+    m.forward_bags(list(bags[:1]))   # the weight image exists
+    before = N.calls
+    out = run_bags(m, bags, label=labels, instance_eval=True)
+    assert N.calls == before + 3, "forward, segmented top-k, gather"
+    res = out["res"]
+    w = m._pack_stacked(torch.device(DEV)) if cls is CLAM_MB else m._pack(torch.device(DEV))
+    Ka = 2 if cls is CLAM_MB else 1
+    st = N.stream_ptr(torch.device(DEV))
+    cat = torch.cat(bags, dim=0).contiguous()
+    off = np.cumsum([0, *ROWS_I])
+    for b, bag in enumerate(bags):
+        a = out["A_raw"][b].contiguous()
+        ids = torch.empty((Ka, 2, k), dtype=torch.int64, device=DEV)
+        N.call("hipt_topk_rows", N.ptr(a), Ka, bag.shape[0], k, N.ptr(ids), st)
+        rows = torch.empty((Ka, 2, k, size[1]), dtype=torch.float32, device=DEV)
+        x = bag.contiguous()
+        N.call("hipt_clam_gather_h1", C.byref(w), N.ptr(x), N.ptr(ids), Ka * 2 * k, N.ptr(rows), st)
+        grows = torch.empty_like(rows)
+        gids = (ids + int(off[b])).contiguous()
+        N.call("hipt_clam_gather_h1", C.byref(w), N.ptr(cat), N.ptr(gids), Ka * 2 * k, N.ptr(grows), st)
+        torch.cuda.synchronize()
+        assert bits(rows) == bits(grows), f"bag {b}: gathered rows"
+        with torch.no_grad():
+            one = m._instance_branch(lambda r: (rows[r, 0], rows[r, 1]), torch.tensor([labels[b]], device=DEV))
+        assert np.array_equal(res["inst_preds"][b], one["inst_preds"]) and np.array_equal(res["inst_labels"][b], one["inst_labels"])
+        want = float(one["instance_loss"])
+        assert abs(float(res["instance_loss"][b]) - want) <= 1e-6 * abs(want), (b, float(res["instance_loss"][b]), want)
+
+
+def inst_reference(cls, subtyping, seed):
+    """fp64 reference of every bag of ROWS_I and the smallest gap at the k-th / (k+1)-th largest and smallest raw score of any branch."""
+    size, k = (384, 128, 64), 8
+    multi = cls is CLAM_MB
+    p = params64(size, 2, multi)
+    refs, gap = [], np.inf
+    for bag, l in zip(bags_of(384, seed, ROWS_I), inst_labels(cls)):
+        h = bag.double().cpu().numpy()
+        if multi:
+            r = R.clam_mb_forward(h, p, k, l, True, subtyping)
+        else:
+            r = O.clam_sb_forward(h, p)
+            h1 = np.maximum(O.linear(h, p["attention_net.0.weight"], p["attention_net.0.bias"]), 0)
+            r.update(R.instance_branch(O.softmax(r["A_raw"], axis=1), h1, p, l, k, subtyping, False))
+        for a in r["A_raw"]:
+            if a.shape[0] > k:
+                s = np.sort(a)
+                gap = min(gap, s[-k] - s[-k - 1], s[k] - s[k - 1])
+        refs.append(r)
+    return refs, float(gap)
+
+
+@pytest.mark.parametrize("cls", [CLAM_SB, CLAM_MB])
+@pytest.mark.parametrize("subtyping", [False, True])
+def test_instance_branch_against_the_reference(cls, subtyping):
+    seed = INST_SEED[cls]
+    refs, gap = inst_reference(cls, subtyping, seed)
+    assert gap > GAP, f"seed {seed}: the reference's own top-k is decided by {gap:.2e} only"
+    m = make((384, 128, 64), "fp32", cls, 2, subtyping)
+    bags = bags_of(384, seed, ROWS_I)
+    out = run_bags(m, bags, label=inst_labels(cls), instance_eval=True)
+    ids, _ = Fn.topk_segments(torch.cat(out["A_raw"], dim=1).contiguous(), Fn.BagOffsets(np.cumsum([0, *ROWS_I]), sum(ROWS_I), torch.device(DEV)), 8)
+    ids = ids.cpu().numpy()
+    for b, (r, l) in enumerate(zip(refs, inst_labels(cls))):
+        assert md(out["A_raw"][b], r["A_raw"]) <= TOL
+        j = 0
+        for c in range(2):
+            br = c if cls is CLAM_MB else 0
+            if l == c:
+                got = [set(ids[b, br, 0]), set(ids[b, br, 1])]
+                want = [set(r["inst_ids"][j][:8]), set(r["inst_ids"][j][8:])]
+            elif subtyping:
+                got, want = [set(ids[b, br, 0])], [set(r["inst_ids"][j])]
+            else:
+                continue
+            assert got == want, (b, c)
+            j += 1
+        assert np.array_equal(out["res"]["inst_labels"][b], r["inst_labels"])
+        assert abs(float(out["res"]["instance_loss"][b]) - r["instance_loss"]) <= TOL
+
+
+# ---------------------------------------------------------------- 7. validate_split on the device
+@pytest.mark.parametrize("cls", [CLAM_SB, CLAM_MB])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_validate_split_on_the_device(cls, dtype):
+    m = make((384, 128, 64), dtype, cls, 2, True)
+    bags = bags_of(384, 23, ROWS_I)
+    labels = inst_labels(cls)
+    a = validate_split(m, bags, labels, 2, max_rows_per_call=1 << 16)
+    assert m.bags_route == "bags"
+    b = validate_split(m, bags, labels, 2, max_rows_per_call=300)
+    for x, y in ((a.prob, b.prob), (a.labels, b.labels)):
+        assert x.tobytes() == y.tobytes()
+    assert (a.val_loss, a.val_error, a.val_inst_loss, a.inst_count, a.acc, a.inst) == (b.val_loss, b.val_error, b.val_inst_loss, b.inst_count, b.acc, b.inst)
+    if dtype == "fp32":
+        m.bags_one_call = False
+        try:
+            loop = per_slide_loop(m, bags, labels, 2)
+        finally:
+            m.bags_one_call = True
+        assert md(a.prob, loop.prob) <= TOL and a.labels.tobytes() == loop.labels.tobytes()
+        assert a.acc == loop.acc and a.inst == loop.inst and a.inst_count == loop.inst_count
+        assert abs(a.val_loss - loop.val_loss) <= TOL and abs(a.val_inst_loss - loop.val_inst_loss) <= TOL
