@@ -141,4 +141,17 @@ template <typename F> bool visit_width(int dtype, int s1, int s2, F&& f) {
     return false;
 }
 
+// The NARROW set of the ragged multi-bag tile kernel of abmil_narrow.hip (hipt_smallest [., 8, 4], hipt_smaller [., 16, 8], [., 32, 8],
+// [., 32, 16]), each in both dtypes: a table of its own, so that visit_width keeps answering as it does.  fp32 (32, 16) is in both.
+template <typename F> bool visit_narrow(int dtype, int s1, int s2, F&& f) {
+#define HIPT_ABMIL_N(TT, A, B) if (s1 == A && s2 == B) return f(Width<TT, A, B>{}), true;
+    if (dtype == HIPT_BF16) {
+        HIPT_ABMIL_N(bf16_t, 8, 4) HIPT_ABMIL_N(bf16_t, 16, 8) HIPT_ABMIL_N(bf16_t, 32, 8) HIPT_ABMIL_N(bf16_t, 32, 16)
+    } else if (dtype == HIPT_F32) {
+        HIPT_ABMIL_N(float, 8, 4) HIPT_ABMIL_N(float, 16, 8) HIPT_ABMIL_N(float, 32, 8) HIPT_ABMIL_N(float, 32, 16)
+    }
+#undef HIPT_ABMIL_N
+    return false;
+}
+
 }  // namespace abmil_tile

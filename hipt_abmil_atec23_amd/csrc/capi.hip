@@ -1208,6 +1208,43 @@ int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, cons
     return HIPT_OK;
 }
 
+// ---- the same call for the narrow heads (abmil_narrow.hip): its own envelope and tile kernel; units, carve and combine shared ----
+int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_narrow_supported(w) ? 1 : 0; }
+
+size_t hipt_clam_narrow_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows) {
+    if (!hipt_clam_narrow_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
+    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows); });
+}
+
+int hipt_clam_sb_forward_bags_narrow(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                                     int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                     void* workspace, size_t ws_bytes, void* stream) {
+    int rc = check_clam(w);
+    if (rc) return rc;
+    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "clam_sb_forward_bags_narrow: null argument");
+    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "clam_sb_forward_bags_narrow: null output");
+    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "clam_sb_forward_bags_narrow: bags must be 16-byte aligned");
+    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "clam_sb_forward_bags_narrow: B = %d bags need at least one row each (total_rows = %lld)", B,
+                   (long long)total_rows);
+    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "clam_sb_forward_bags_narrow: %lld rows in %d bags exceed 2^31 tiles",
+                   (long long)total_rows, B);
+    if (!hipt_clam_narrow_bags_supported(w)) {
+        hipt_set_error("clam_sb_forward_bags_narrow: [%d,%d,%d] is not a narrow head: (S1, S2) in {(8,4), (16,8), (32,8), (32,16)}, S0 a "
+                       "multiple of 32 (fp32) / 64 (bf16)", w->s0, w->s1, w->s2);
+        return HIPT_E_UNSUPPORTED;
+    }
+    Carver c(workspace, ws_bytes);
+    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows);
+    if (check_workspace(c, "clam_sb_forward_bags_narrow")) return HIPT_E_BADARG;  // as hipt_clam_sb_forward_bags: a short buffer is a bad argument
+    hipStream_t st = S(stream);
+    const int nu = (int)clam_bags_max_units(B, total_rows);
+    PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
+    PROF(PC_ABMIL, hipt_clam_narrow_tiles_launch(w, bags, k.units, nu, attention_only, A_raw, k.partials, st));
+    if (attention_only) return HIPT_OK;
+    PROF(PC_COMBINE, hipt_clam_bags_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
+    return HIPT_OK;
+}
+
 // ---- the same for the K = n_att branches of CLAM_MB: K partials per unit ----
 int hipt_clam_mb_bags_supported(const hipt_clam_weights* w) {
     return hipt_clam_bags_supported(w) && w->n_att >= 2 && w->n_att <= 4 && w->n_att == w->n_classes ? 1 : 0;

@@ -64,12 +64,40 @@ def _split(bags_or_loader, labels):
     return [b.reshape(-1, b.shape[-1]) for b in bags], labels
 
 
+class _attr_for_call:
+    """``model.<name> = value`` for the length of a ``with`` block where the model's CLASS has that switch; afterwards the instance
+    is as it was (its own value, or none: back to the class attribute), also after an exception."""
+
+    def __init__(self, model, name: str, value: bool):
+        self.model, self.name, self.value = model, name, bool(value)
+        self.had = hasattr(type(model), name)
+
+    def __enter__(self):
+        if self.had:
+            self.before = self.model.__dict__.get(self.name, None)
+            setattr(self.model, self.name, self.value)
+        return self
+
+    def __exit__(self, *exc):
+        if self.had:
+            if self.before is None:
+                delattr(self.model, self.name)
+            else:
+                setattr(self.model, self.name, self.before)
+        return False
+
+
 def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
-                   max_rows_per_call: int = DEFAULT_MAX_ROWS) -> SplitResult:
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True) -> SplitResult:
     """Evaluate ``model`` on every bag of a split.  ``bags_or_loader``: a sequence of ``[N_b, S0]`` tensors with ``labels``, or an
     iterable of ``(bag, label)`` pairs (a batch-size-1 loader) with ``labels=None``.  The bags go to the model's device and through
     ``model.forward_bags`` in runs of at most ``max_rows_per_call`` rows (a model without ``forward_bags`` is called bag by bag);
-    the logits come back to the host once per run.  ``loss_fn(logits [1, C], label [1])`` defaults to cross-entropy."""
+    the logits come back to the host once per run.  ``loss_fn(logits [1, C], label [1])`` defaults to cross-entropy.
+
+    A ``CLAM_SB`` model runs with ``bags_narrow = narrow_one_call`` for the duration of the call: for the narrow heads
+    (``hipt_smaller``, ``hipt_smallest``, ...: ``hipt_clam_narrow_bags_supported``) the numbers then come from the one-call kernel
+    ``hipt_clam_sb_forward_bags_narrow``.  They equal those of the loop over ``forward`` (``narrow_one_call=False``) within the
+    fp32 bar (1e-4); they are not bit-equal to it."""
     bags, labels = _split(bags_or_loader, labels)
     n = len(bags)
     if any(l < 0 or l >= n_classes for l in labels):
@@ -82,7 +110,7 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     logits = torch.empty((n, n_classes), dtype=torch.float32)
     probs = torch.empty((n, n_classes), dtype=torch.float32)
     preds = torch.empty((n,), dtype=torch.int64)
-    with torch.no_grad():
+    with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call):
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             part = [bags[i].to(dev) for i in run]
             if fb is not None:
@@ -119,10 +147,12 @@ class ValidationResult:
 
 
 def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
-                   max_rows_per_call: int = DEFAULT_MAX_ROWS, mb_one_call: bool = True) -> ValidationResult:
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS, mb_one_call: bool = True, narrow_one_call: bool = True) -> ValidationResult:
     """The numbers of ``validate_clam`` for ``model`` on a split, with ``model.forward_bags(..., label=, instance_eval=True)`` called on
     runs of at most ``max_rows_per_call`` rows (``chunk_bags``) instead of ``model(bag, label=, instance_eval=True)`` once per slide.
-    Arguments as :func:`evaluate_split`.  A ``CLAM_MB`` model runs with ``bags_one_call = mb_one_call`` for the duration of the call.
+    Arguments as :func:`evaluate_split`.  A ``CLAM_MB`` model runs with ``bags_one_call = mb_one_call`` for the duration of the call,
+    a ``CLAM_SB`` with ``bags_narrow = narrow_one_call``: for the narrow heads (``hipt_smaller``, ``hipt_smallest``, ...) the numbers
+    then come from the one-call kernel; they equal the loop's (``narrow_one_call=False``) within the fp32 bar (1e-4), not bit for bit.
     The AUC stays with the caller (``labels`` and ``prob`` are its inputs).  The model is put in eval mode, as ``validate_clam`` does."""
     bags, labels = _split(bags_or_loader, labels)
     n = len(bags)
@@ -143,7 +173,7 @@ def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
         model.bags_one_call = bool(mb_one_call)
     model.eval()
     try:
-        with torch.no_grad():
+        with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call):
             for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
                 lg, yp, yh, _, res = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
                 sl = slice(run.start, run.stop)

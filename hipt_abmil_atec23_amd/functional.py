@@ -140,6 +140,29 @@ def clam_sb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_on
     return out
 
 
+def clam_sb_forward_bags_narrow(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_sb_forward_bags_narrow``: :func:`clam_sb_forward_bags` for the narrow heads (``hipt_clam_narrow_bags_supported``:
+    ``(S1, S2)`` in {(8, 4), (16, 8), (32, 8), (32, 16)}, fp32 and bf16).  Arguments and results as there."""
+    import ctypes as C
+    N.require_cuda(cat, "clam_sb_forward_bags_narrow")
+    dev, B, rows = cat.device, len(offsets), cat.shape[0]
+    if cat.dim() != 2 or not cat.is_contiguous() or cat.dtype != _TORCH_DT[w.dtype] or cat.shape[1] != w.s0:
+        raise ValueError(f"expected contiguous [rows, {w.s0}] bags in {_TORCH_DT[w.dtype]}, got {tuple(cat.shape)} {cat.dtype}")
+    if offsets.host[-1] != rows:
+        raise ValueError(f"bag offsets end at {offsets.host[-1]} but the concatenated bags have {rows} rows")
+    N.same_device("clam_sb_forward_bags_narrow", dev, offsets.dev)
+    st = N.stream_ptr(dev)
+    if ws is None:
+        ws = workspace(dev, N.lib().hipt_clam_narrow_bags_workspace_bytes(C.byref(w), B, rows), ("clam_bags", st.value))
+    if out is None:
+        e = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        out = (e(rows), None, None, None, None) if attention_only else (e(rows), e(B, w.s1), e(B, w.n_classes), e(B, w.n_classes), e(B, dt=torch.int64))
+    A_raw, M, logits, Y_prob, Y_hat = out
+    N.call("hipt_clam_sb_forward_bags_narrow", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0,
+           N.ptr(A_raw), N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
+    return out
+
+
 def clam_mb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
     """``hipt_clam_mb_forward_bags``: :func:`clam_sb_forward_bags` for the ``K = w.n_att`` branches of a stacked ``CLAM_MB`` weight image.
     Returns ``(A_raw [K, rows], M [B, K, S1], logits [B, K], Y_prob [B, K], Y_hat [B])``; bag ``b`` is the columns

@@ -279,6 +279,7 @@ class CLAM_SB(WeightImageCache, nn.Module):
     ``[S0, S1, S2]`` list."""
 
     _multi = False
+    bags_narrow = False  # forward_bags takes hipt_clam_sb_forward_bags_narrow (all bags in one call) for the narrow heads the multi-bag kernel does not have; False: the loop over forward
 
     def __init__(self, gate=True, size_arg="small", dropout=0.0, k_sample=8, n_classes=2,
                  instance_loss_fn=nn.CrossEntropyLoss(), subtyping=False):
@@ -540,7 +541,10 @@ class CLAM_SB(WeightImageCache, nn.Module):
         ``hipt_clam_mb_bags_supported``: ``A_raw`` is then a list of ``[K, N_b]`` views and the features are ``[B, K, S1]``) this is
         ONE native call whose per-bag results do not depend on the other bags; elsewhere -- other widths, ``CLAM_MB`` without
         ``bags_one_call``, the ungated head, CPU tensors -- it loops over ``forward`` and returns the same structure.
-        ``bags_route`` tells which.
+        ``bags_route`` tells which.  The narrow heads (``hipt_smaller`` [192, 16, 8], ``hipt_smallest`` [192, 8, 4], (32, 8), bf16
+        (32, 16): ``hipt_clam_narrow_bags_supported``) have a one-call kernel of their own, ``hipt_clam_sb_forward_bags_narrow``, taken
+        by a ``CLAM_SB`` with ``bags_narrow`` set (default False: the loop, with the bits of ``forward``); its numbers equal the
+        loop's within the fp32 bar (1e-4), not bit for bit.  A width both kernels have keeps the first.
 
         ``instance_eval=True`` with ``label`` (B class ids: a list, a numpy array or a tensor) adds what ``forward(h, label=,
         instance_eval=True)`` returns per bag (validate_clam, utils/core_utils.py:506-560): ``instance_loss`` (a ``[B]`` tensor),
@@ -559,12 +563,15 @@ class CLAM_SB(WeightImageCache, nn.Module):
                 if self.k_sample > host[b + 1] - host[b]:
                     raise RuntimeError(f"selected index k out of range: k_sample={self.k_sample} > {host[b + 1] - host[b]} rows (torch.topk, model_clam.py:120)")
         with torch.no_grad():
-            w = None
+            w, narrow = None, False
             if self._gate and cat.is_cuda:
                 if not self._multi:
                     w = self._pack(cat.device)
                     if not N.lib().hipt_clam_bags_supported(C_.byref(w)):
-                        w = None
+                        # a narrow head (hipt_smaller, hipt_smallest, ...): its own one-call kernel, where asked for
+                        narrow = self.bags_narrow and N.lib().hipt_clam_narrow_bags_supported(C_.byref(w))
+                        if not narrow:
+                            w = None
                 elif self.bags_one_call:
                     w = self._pack_stacked(cat.device)
                     if not N.lib().hipt_clam_mb_bags_supported(C_.byref(w)):
@@ -578,7 +585,8 @@ class CLAM_SB(WeightImageCache, nn.Module):
                 A_raw, M, logits, Y_prob, Y_hat = Fn.clam_mb_forward_bags(w, x, off, attention_only)
                 views = [A_raw[:, host[b]:host[b + 1]] for b in range(B)]
             else:
-                A_raw, M, logits, Y_prob, Y_hat = Fn.clam_sb_forward_bags(w, x, off, attention_only)
+                call = Fn.clam_sb_forward_bags_narrow if narrow else Fn.clam_sb_forward_bags
+                A_raw, M, logits, Y_prob, Y_hat = call(w, x, off, attention_only)
                 views = [A_raw[host[b]:host[b + 1]].view(1, -1) for b in range(B)]
             if attention_only:
                 return views

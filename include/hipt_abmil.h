@@ -387,6 +387,21 @@ int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, cons
                               int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                               void* workspace, size_t ws_bytes, void* stream);
 
+/* hipt_clam_sb_forward_bags for the NARROW gated heads, which that call does not take: (S1, S2) in {(8, 4), (16, 8), (32, 8), (32, 16)} in fp32
+ * and in bf16, S0 a multiple of 32 (fp32) / 64 (bf16) -- the reference's hipt_smallest [192, 8, 4] and hipt_smaller [192, 16, 8] among them.
+ * Arguments, outputs, the three plain launches (the same unit table and the same per-bag combine; the tile pass is a kernel of its own), the
+ * absence of atomics, tickets and workspace state, graph capture and the bit-for-bit independence of a bag from the other bags of the
+ * call: as there.  Rounding in bf16: the bag, W1, Wa and Wb are bf16; h1, the gate and the pooling are fp32 (the model of hipt_clam_sb_forward
+ * for these widths).  fp32 (32, 16) is taken by both calls; their results agree within fp32 rounding, not bit for bit.
+ * hipt_clam_narrow_bags_supported(w) != 0: the configuration has this form; otherwise HIPT_E_UNSUPPORTED and
+ * hipt_clam_narrow_bags_workspace_bytes = 0.  HIPT_E_BADARG, before anything is launched, for a null pointer, a misaligned `bags`, B < 1,
+ * total_rows < B and a workspace smaller than hipt_clam_narrow_bags_workspace_bytes(w, B, total_rows) or not 256-byte aligned. */
+int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w);
+size_t hipt_clam_narrow_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
+int hipt_clam_sb_forward_bags_narrow(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                                     int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                     void* workspace, size_t ws_bytes, void* stream);
+
 /* CLAM_MB.forward (model_clam.py:226-264) over B bags in ONE call: hipt_clam_sb_forward_bags for the K = w->n_att attention branches of a
  * hipt_clam_weights stacked as hipt_clam_mb_forward takes it (wc [K, S2], bc [K], wcls [K, S1], bcls [K], n_classes = K; stream_pk and
  * logit_bound are not read).  bags / offsets_dev / B / total_rows / workspace rules, the three plain launches, the absence of atomics,
