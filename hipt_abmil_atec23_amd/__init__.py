@@ -37,6 +37,10 @@ _LAZY = {
     # attention heat-maps (WholeSlideImage.visHeatmap)
     "heatmap_overlay": ("heatmap", "heatmap_overlay"), "render_heatmap": ("heatmap", "render_heatmap"),
     "vis_heatmap": ("heatmap", "vis_heatmap"),
+    # heat-map scores on the device: percentile ranks, reference percentiles, ROI sampling, the patch-scoring loop body
+    "score_counts": ("heatmap", "score_counts"), "to_percentiles": ("heatmap", "to_percentiles"),
+    "score2percentile": ("heatmap", "score2percentile"), "sample_rois": ("heatmap", "sample_rois"),
+    "compute_from_batches": ("heatmap", "compute_from_batches"),
 }
 
 

@@ -14,8 +14,10 @@ The reference imports the hot-path classes by module path:
   where it does not, a module is registered whose plotting names raise.  ``install(heatmaps=True)`` binds this package's
   ``vis_heatmap`` as ``wsi_core.WholeSlideImage.WholeSlideImage.visHeatmap`` (what create_heatmaps.py draws with) where the
   reference's ``wsi_core`` imports (it needs openslide and cv2); elsewhere it does nothing.  ``install(resnet18=True)`` binds
-  ``models.resnet_custom.resnet18_baseline`` to this package's HistoResNet-18 (``resnet18.resnet18_baseline``).  The alternative is
-  the overlay files under ``shims/``.
+  ``models.resnet_custom.resnet18_baseline`` to this package's HistoResNet-18 (``resnet18.resnet18_baseline``).
+  ``install(heatmap_scores=True)`` binds ``wsi_core.wsi_utils.to_percentiles`` and ``sample_rois`` to ``heatmap``'s where the
+  reference's module imports (it needs h5py and cv2); elsewhere it does nothing.  The alternative is the overlay files under
+  ``shims/``.
 """
 from __future__ import annotations
 
@@ -134,6 +136,44 @@ def _uninstall_heatmaps():
         del cls.visHeatmap
     else:
         cls.visHeatmap = prev
+
+
+_WSI_UTILS_MOD = "wsi_core.wsi_utils"
+_WSI_UTILS_NAMES = ("to_percentiles", "sample_rois")
+
+
+def _install_heatmap_scores(verbose: bool) -> bool:
+    """Bind ``heatmap.to_percentiles`` and ``heatmap.sample_rois`` on the reference's ``wsi_core.wsi_utils`` (opt-in).  False, and
+    nothing done, where that module does not import."""
+    from . import heatmap
+    if _WSI_UTILS_MOD in _saved:
+        return True
+    try:
+        if _WSI_UTILS_MOD not in sys.modules and importlib.util.find_spec(_WSI_UTILS_MOD) is None:
+            return False
+        mod = importlib.import_module(_WSI_UTILS_MOD)
+    except Exception:   # no reference checkout on sys.path, or h5py / cv2 missing
+        return False
+    _saved[_WSI_UTILS_MOD] = {n: mod.__dict__.get(n) for n in _WSI_UTILS_NAMES}
+    for n in _WSI_UTILS_NAMES:
+        setattr(mod, n, getattr(heatmap, n))
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_WSI_UTILS_MOD}.{{{', '.join(_WSI_UTILS_NAMES)}}} -> {heatmap.__name__}")
+    return True
+
+
+def _uninstall_heatmap_scores():
+    if _WSI_UTILS_MOD not in _saved:
+        return
+    prev = _saved.pop(_WSI_UTILS_MOD)
+    mod = sys.modules.get(_WSI_UTILS_MOD)
+    if mod is None:
+        return
+    for n, fn in prev.items():
+        if fn is None:
+            delattr(mod, n)
+        else:
+            setattr(mod, n, fn)
 
 
 _EVAL_MOD = "utils.eval_utils"
@@ -257,7 +297,7 @@ def _uninstall_resnet18():
 
 
 def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False,
-            evaluation: bool = False, validation: bool = False):
+            evaluation: bool = False, validation: bool = False, heatmap_scores: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
     ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
@@ -265,8 +305,13 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False,
     ``resnet18=True`` also binds ``models.resnet_custom.resnet18_baseline`` to ``resnet18.resnet18_baseline`` (the HistoResNet-18
     extractor), on the module ``resnet=True`` mapped or on the reference's own.
     ``evaluation=True`` also binds ``utils.eval_utils.summary`` to ``evaluate.evaluate_split`` where that module imports (else a no-op).
-    ``validation=True`` also binds ``utils.core_utils.validate_clam`` to ``evaluate.validate_split`` where that module imports (else a no-op)."""
+    ``validation=True`` also binds ``utils.core_utils.validate_clam`` to ``evaluate.validate_split`` where that module imports (else a no-op).
+    ``heatmap_scores=True`` also binds ``wsi_core.wsi_utils.to_percentiles`` / ``sample_rois`` to ``heatmap``'s where that module imports
+    (else a no-op)."""
     done = {}
+    if heatmap_scores and _install_heatmap_scores(verbose):
+        for n in _WSI_UTILS_NAMES:
+            done[f"{_WSI_UTILS_MOD}.{n}"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.{n}"
     if heatmaps and _install_heatmaps(verbose):
         done[_WSI_MOD + ".WholeSlideImage.visHeatmap"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.vis_heatmap"
     if sampling:
@@ -317,6 +362,7 @@ def uninstall():
     _uninstall_resnet18()
     _uninstall_sampling()
     _uninstall_heatmaps()
+    _uninstall_heatmap_scores()
     for ref_name in _MAP:
         sys.modules.pop(ref_name, None)
     for ref_name in _RESNET_MAP:

@@ -6,13 +6,19 @@ Here the pixel work is ``hipt_heatmap_overlay`` / ``hipt_heatmap_render`` (csrc/
 its covering patches from per-tile lists in ascending patch index, so the float64 overlay is bit for bit numpy's, and the mask,
 the colour lookup and the blend happen in the same pass.
 
-Host work, by design: scaling the coordinates (float64 ``ceil``, as numpy), percentile ranks, the threshold, the 258-entry colour
-table from matplotlib, and everything that touches the slide (``vis_heatmap``: level choice, bounding-box screening, one
-``read_region`` for the canvas, the tissue mask, PIL's final ``resize``).  ``blur=True`` is not supported (cv2's fixed-point uint8
-Gaussian cannot be reproduced without cv2).
+Host work, by design: scaling the coordinates (float64 ``ceil``, as numpy), the threshold, the 258-entry colour table from
+matplotlib, and everything that touches the slide (``vis_heatmap``: level choice, bounding-box screening, one ``read_region`` for
+the canvas, the tissue mask, PIL's final ``resize``).  ``blur=True`` is not supported (cv2's fixed-point uint8 Gaussian cannot be
+reproduced without cv2).
+
+The scores in front of the picture rank on the device too: ``hipt_score_counts`` (csrc/percentile.hip) counts, for
+every score, the reference values below it and those not above it, and forms the percentile in the reference's order of operations.
+``to_percentiles`` of a device tensor (``rankdata / len * 100``), ``score2percentile`` (``percentileofscore`` against the block
+map's scores, vectorised), ``sample_rois`` and ``compute_from_batches`` (the loop body of ``compute_from_patches``) are built on it.
+Numpy scores handed to ``render_heatmap`` / ``heatmap_overlay`` are still ranked by numpy on their way to the device.
 
 Inputs may be numpy arrays (copied to the device, result returned as numpy) or torch tensors already on the device (result
-returned as a tensor; nothing is copied to the host).  With device tensors the one thing that needs the VALUES -- refusing
+returned as a tensor; nothing is copied to the host, with ``convert_to_percentiles`` or without).  With device tensors the one thing that needs the VALUES -- refusing
 negative coordinates and non-finite scores -- costs one synchronisation, which is left out while the stream is being captured
 into a graph; the kernels clip such patches at the canvas edge and read nothing out of bounds either way.
 """
@@ -54,8 +60,13 @@ def table_index(overlay) -> np.ndarray:
     return np.where(t < 0, 256, np.where(t == 256, 255, np.where(t > 256, 257, inner)))
 
 
-def to_percentiles(scores: np.ndarray) -> np.ndarray:
-    """``scipy.stats.rankdata(scores, 'average') / len(scores) * 100`` (wsi_core/wsi_utils.py:124-127) in numpy."""
+def to_percentiles(scores):
+    """``scipy.stats.rankdata(scores, 'average') / len(scores) * 100`` (wsi_core/wsi_utils.py:124-127): in numpy for numpy
+    scores; a device tensor is ranked on the device (``hipt_score_counts``) and a float64 device tensor comes back, the same bits."""
+    if _is_tensor(scores):
+        _check_no_nan("to_percentiles", scores=scores)
+        s = _as_f64(scores, _resolve_device(None, (scores,)))
+        return _counts_call(s, s, N.PCT_RANKDATA, pct=True)[2]
     s = np.asarray(scores, dtype=np.float64).reshape(-1)
     n = len(s)
     if n == 0:
@@ -172,6 +183,98 @@ def _resolve_device(device, tensors):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# score ranks on the device (csrc/percentile.hip)
+# ------------------------------------------------------------------------------------------------------------------------------
+def _check_one_device(what, arrays):
+    devs = sorted({str(a.device) for a in arrays if _is_tensor(a)})
+    if len(devs) > 1:
+        raise ValueError(f"{what}: scores and reference scores are on different devices ({', '.join(devs)})")
+
+
+def _as_f64(a, dev):
+    """A flat, contiguous float64 tensor on ``dev`` (float32 scores widen exactly, as numpy's comparison promotes them)."""
+    import torch
+    t = a if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.detach().to(dev, torch.float64).reshape(-1).contiguous()
+
+
+def _check_no_nan(what, **named):
+    """``ValueError`` on a NaN; numpy arrays are looked at on the host, device tensors with one synchronisation, which is left
+    out while the stream is being captured into a graph (the kernel then counts a NaN as neither below nor above anything)."""
+    import torch
+    for name, a in named.items():
+        if a is None:
+            continue
+        if _is_tensor(a):
+            if a.is_cuda and torch.cuda.is_current_stream_capturing():
+                continue
+            bad = bool(torch.isnan(a).any()) if a.numel() else False
+        else:
+            bad = bool(np.isnan(np.asarray(a, dtype=np.float64)).any())
+        if bad:
+            raise ValueError(f"{what}: {name} contain NaN")
+
+
+def _counts_call(q, ref, mode, *, counts=False, pct=False):
+    """``(less, leq, pct)`` of flat float64 device tensors ``q`` against ``ref``; what was not asked for is None."""
+    import torch
+    dev, nq = q.device, q.numel()
+    less = torch.empty(nq, dtype=torch.int32, device=dev) if counts else None
+    leq = torch.empty(nq, dtype=torch.int32, device=dev) if counts else None
+    out = torch.empty(nq, dtype=torch.float64, device=dev) if pct else None
+    if nq:
+        with torch.cuda.device(dev):
+            N.call("hipt_score_counts", N.ptr(q), nq, N.ptr(ref), ref.numel(), mode, N.ptr(less), N.ptr(leq), N.ptr(out),
+                   N.stream_ptr(dev))
+    return less, leq, out
+
+
+def _check_score_args(what, scores, ref_scores):
+    """The argument checks of ``score_counts`` / ``score2percentile``, all before any native call; returns the device."""
+    nref = int(np.prod(tuple(ref_scores.shape)))
+    if nref == 0:
+        raise ValueError(f"{what}: ref_scores is empty (there is nothing to rank against)")
+    if nref >= 2 ** 31:
+        raise ValueError(f"{what}: {nref} reference scores; the counts are int32")
+    _check_one_device(what, (scores, ref_scores))
+    _check_no_nan(what, scores=scores, ref_scores=ref_scores)
+    return _resolve_device(None, (scores, ref_scores))
+
+
+def score_counts(q, ref):
+    """``(less, leq)``, int32 ``[len(q)]``: how many values of ``ref`` are smaller than each ``q[i]``, and how many are smaller or
+    equal (IEEE comparisons in float64).  Numpy in, numpy out; device tensors in, tensors out."""
+    q, ref = _as_array(q), _as_array(ref)
+    dev = _check_score_args("score_counts", q, ref)
+    less, leq, _ = _counts_call(_as_f64(q, dev), _as_f64(ref, dev), N.PCT_OF_SCORE, counts=True)
+    if _is_tensor(q):
+        return less, leq
+    return less.cpu().numpy(), leq.cpu().numpy()
+
+
+def _torch_dtype(dtype):
+    import torch
+    if dtype is None or isinstance(dtype, torch.dtype):
+        return dtype
+    return getattr(torch, np.dtype(dtype).name)
+
+
+def score2percentile(scores, ref_scores, out_dtype=None):
+    """``scipy.stats.percentileofscore(ref_scores, s)`` (kind 'rank') for every ``s`` of ``scores`` at once: what the reference's
+    ``score2percentile`` (vis_utils/heatmap_utils.py:22-24) gives score by score, in the shape of ``scores``.  float64, or
+    ``out_dtype`` (``torch.float32`` reproduces the reference's storage, which assigns into a float32 array).  ``scores`` as a
+    numpy array: a numpy array comes back (copied from the device, not recomputed); as a device tensor: a tensor.  ``ref_scores``
+    may be either kind."""
+    scores, ref_scores = _as_array(scores), _as_array(ref_scores)
+    dev = _check_score_args("score2percentile", scores, ref_scores)
+    out = _counts_call(_as_f64(scores, dev), _as_f64(ref_scores, dev), N.PCT_OF_SCORE, pct=True)[2].reshape(tuple(scores.shape))
+    dtype = _torch_dtype(out_dtype)
+    if dtype is not None:
+        out = out.to(dtype)
+    return out if _is_tensor(scores) else out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # the device call
 # ------------------------------------------------------------------------------------------------------------------------------
 def _host_inputs(scores, coords, patch_size, scale, *, binarize, thresh, convert_to_percentiles):
@@ -193,7 +296,7 @@ def _device_inputs(host, scores, coords, patch_size, scale, dev, *, binarize, th
     _, pw, ph = scaled_geometry(np.zeros((0, 2), dtype=np.int64), patch_size, scale)
     if host is not None:
         return tuple(torch.from_numpy(a).to(dev) for a in host) + (pw, ph)
-    s = (scores if _is_tensor(scores) else torch.from_numpy(np.asarray(scores))).to(dev, torch.float64).reshape(-1)
+    s = (scores if _is_tensor(scores) else torch.from_numpy(np.asarray(scores))).to(dev, torch.float64).reshape(-1).contiguous()
     c = (coords if _is_tensor(coords) else torch.from_numpy(np.asarray(coords))).to(dev)
     sc = np.broadcast_to(np.asarray(scale, dtype=np.float64), (2,))
     c = c.to(torch.float64)
@@ -202,8 +305,8 @@ def _device_inputs(host, scores, coords, patch_size, scale, dev, *, binarize, th
     if n and not torch.cuda.is_current_stream_capturing():
         bad = torch.stack([(xyf < 0).any(), (xyf >= 2.0 ** 31).any(), ~torch.isfinite(s).all()]).cpu().numpy()   # one synchronisation
         _check_values(-1 if bad[0] else 0, 2 ** 31 if bad[1] else 0, not bad[2])
-    if convert_to_percentiles:   # ranks are host work: the scores make one round trip
-        s = torch.from_numpy(to_percentiles(s.cpu().numpy())).to(dev)
+    if convert_to_percentiles:   # (the finiteness check above has refused a NaN already)
+        s = _counts_call(s, s, N.PCT_RANKDATA, pct=True)[2]
     s = torch.div(s, torch.full_like(s, 100.0))   # tensor / tensor: a true division (by a Python scalar torch multiplies by 1 / 100)
     keep = s >= threshold_of(n, binarize, thresh)
     v = torch.where(keep, torch.ones_like(s) if binarize else s, torch.zeros_like(s))
@@ -317,6 +420,74 @@ def screen_coords(scores, coords, top_left, bot_right):
     """The patches whose corner lies inside the box, both ends included (wsi_core/wsi_utils.py:129-135)."""
     keep = np.logical_and(np.all(coords >= np.array(top_left), axis=1), np.all(coords <= np.array(bot_right), axis=1))
     return scores[keep], coords[keep]
+
+
+def sample_rois(scores, coords, k=5, mode="range_sample", seed=1, score_start=0.45, score_end=0.55, top_left=None, bot_right=None):
+    """``wsi_core.wsi_utils.sample_rois`` (:137-158): the patches ``create_heatmaps.py`` saves beside a heat-map.  The scores become
+    percentiles (device tensors: on the device); the bounding-box screen, the window of ``range_sample`` with ``np.random.seed(seed)``
+    and ``np.random.choice``, and the ``argsort`` behind ``topk`` / ``reverse_topk`` follow on the host in the reference's order, so
+    a seed picks what it picks there.  Returns ``{'sampled_coords', 'sampled_scores'}`` as numpy arrays (k winners), whatever came
+    in.  As in the reference, an empty window of ``range_sample`` yields index -1: the last patch."""
+    if mode not in ("range_sample", "topk", "reverse_topk"):
+        raise NotImplementedError(f"sample_rois: mode {mode!r}")
+    scores, coords = _as_array(scores), _as_array(coords)
+    if scores.ndim == 2:
+        scores = scores.flatten()
+    scores = to_percentiles(scores)
+    if _is_tensor(scores):
+        scores = scores.cpu().numpy()
+    if _is_tensor(coords):
+        coords = coords.cpu().numpy()
+    if top_left is not None and bot_right is not None:
+        scores, coords = screen_coords(scores, coords, top_left, bot_right)
+    if mode == "range_sample":
+        np.random.seed(seed)
+        indices = np.where(np.logical_and(scores >= score_start, scores <= score_end))[0]
+        sampled_ids = -1 if len(indices) < 1 else np.random.choice(indices, min(k, len(indices)), replace=False)
+    elif mode == "topk":
+        sampled_ids = scores.argsort()[::-1][:k]
+    else:
+        sampled_ids = scores.argsort()[:k]
+    return {"sampled_coords": coords[sampled_ids], "sampled_scores": scores[sampled_ids]}
+
+
+def compute_from_batches(model, feature_extractor, batches, clam_pred=None, ref_scores=None, out_dtype="float32", on_batch=None):
+    """The loop body of ``vis_utils.heatmap_utils.compute_from_patches`` (:60-89) over any iterable of ``(roi, coords)``: features
+    = ``feature_extractor(roi)``, A = ``model(features, attention_only=True)``, row ``clam_pred`` of it where the model has more
+    than one branch, as a column ``[n, 1]``; with ``ref_scores`` every score becomes its percentile among them (``score2percentile``,
+    on the device, stored as ``out_dtype``: a torch or numpy dtype or its name; float32 is the dtype of the reference's array).  ``roi`` goes to the
+    extractor as the loader hands it over.  ``on_batch(scores, coords, features)`` is called once per batch, in order, for the
+    caller's writer (the reference appends to an h5 file there).  Returns ``(scores [sum n, 1] tensor, coords [sum n, 2] numpy)``."""
+    import torch
+    out_dtype = _torch_dtype(out_dtype)
+    if ref_scores is not None:
+        ref_scores = _as_array(ref_scores)
+        _check_score_args("compute_from_batches", None, ref_scores)   # (the reference scores are looked at once, not per batch)
+    ref = None
+    all_scores, all_coords = [], []
+    for roi, coords in batches:
+        with torch.no_grad():
+            features = feature_extractor(roi)
+            a = model(features, attention_only=True)
+            if a.size(0) > 1:   # CLAM multi-branch attention
+                if clam_pred is None:
+                    raise ValueError(f"compute_from_batches: the model has {a.size(0)} attention branches; clam_pred says which to take")
+                a = a[clam_pred]
+            a = a.reshape(-1, 1)
+            if ref_scores is not None:
+                if ref is None or ref.device != a.device:
+                    _check_one_device("compute_from_batches", (a, ref_scores))
+                    ref = _as_f64(ref_scores, _resolve_device(None, (a, ref_scores)))
+                _check_no_nan("compute_from_batches", scores=a)
+                a = _counts_call(_as_f64(a, ref.device), ref, N.PCT_OF_SCORE, pct=True)[2].reshape(-1, 1).to(out_dtype)
+        c = coords.cpu().numpy() if _is_tensor(coords) else np.asarray(coords)
+        if on_batch is not None:
+            on_batch(a, c, features)
+        all_scores.append(a)
+        all_coords.append(c)
+    if not all_scores:
+        return torch.zeros((0, 1), dtype=out_dtype), np.zeros((0, 2), dtype=np.int64)
+    return torch.cat(all_scores), np.concatenate(all_coords)
 
 
 def vis_heatmap(wsi_object, scores, coords, vis_level=-1, top_left=None, bot_right=None, patch_size=(256, 256), blank_canvas=False,

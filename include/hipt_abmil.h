@@ -35,7 +35,8 @@ extern "C" {
  * hipt_vit_packed_bytes, never compute the size) and packing it reads blocks[i].proj_w, which must be set first;
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
- * _render) and hipt_vit_cls_block_unit were added later under the same number: additive, nothing existing changed. */
+ * _render), hipt_vit_cls_block_unit and hipt_score_counts were added later under the same number: additive, nothing existing
+ * changed. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -739,6 +740,26 @@ int hipt_heatmap_overlay(const int32_t* xy, const double* v, const uint8_t* pain
 int hipt_heatmap_render(const int32_t* xy, const double* v, const uint8_t* paint, int N, int pw, int ph, int w, int h,
                         int binarize, const uint8_t* mask, const uint8_t* canvas, const uint8_t* lut, double alpha, uint8_t* img,
                         double* overlay, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Heat-map score ranks (wsi_core/wsi_utils.py:124-127 to_percentiles, vis_utils/heatmap_utils.py:22-24 score2percentile;
+ * DESIGN.md 19).  For each of nq queries, against nref reference values (all float64, device pointers):
+ *   less[i] = #{j : ref[j] < q[i]},  leq[i] = #{j : ref[j] <= q[i]}      (int32; IEEE comparisons: -0.0 == +0.0, +-inf order)
+ *   pct[i]  = (0.5 * (less + leq + 1)) / nref * 100                      mode HIPT_PCT_RANKDATA: with q = ref this is
+ *                                                                        scipy.stats.rankdata(ref, 'average') / len(ref) * 100
+ *           = (less + leq + (less < leq)) * (50.0 / nref)                mode HIPT_PCT_OF_SCORE: scipy.stats.percentileofscore(ref, q)
+ * in float64, every operation rounded on its own in the order written, so the values are bit for bit scipy's.  less, leq and
+ * pct may each be NULL (not all three).  The counts come from brute force over the reference -- no sort, no atomic, no
+ * workspace -- so a query's three results depend on q[i] and ref alone: not on nq, its position in q or the launch geometry.
+ * One wave owns HIPT_PCT_QUERIES_PER_WG queries and walks the reference in LDS tiles of HIPT_PCT_REF_TILE values.
+ * NaN in q or ref is a caller error (a NaN compares false both ways; the Python layer refuses it).  nq = 0 or nref = 0 returns
+ * HIPT_OK and touches nothing; nref >= 2^31 (the counts are int32) is HIPT_E_UNSUPPORTED with nothing launched.  q may be ref.
+ * ---------------------------------------------------------------------------------- */
+enum { HIPT_PCT_RANKDATA = 0, HIPT_PCT_OF_SCORE = 1 };
+#define HIPT_PCT_REF_TILE 512
+#define HIPT_PCT_QUERIES_PER_WG 128
+int hipt_score_counts(const double* q, int64_t nq, const double* ref, int64_t nref, int mode, int32_t* less, int32_t* leq,
+                      double* pct, void* stream);
 
 #ifdef __cplusplus
 }
