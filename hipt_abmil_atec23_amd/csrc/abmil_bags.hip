@@ -23,9 +23,6 @@
 namespace {
 using namespace abmil_tile;
 
-// rows [m0, min(m0 + TM, end)) of the concatenated matrix; m0 < 0: no unit (the table is sized from an upper bound)
-struct BagUnit { int64_t m0, end; };
-
 // ---------------- units: offsets -> tile_start[B+1], units[max_units] ----------------
 // One 1024-thread workgroup; thread t owns a contiguous run of ceil(B/1024) bags: count its tiles, exclusive scan over the threads
 // (shuffles inside a wave, 16 wave totals through LDS), then write its bags' entries.  A bag whose offsets are not inside
@@ -662,21 +659,12 @@ __global__ __launch_bounds__(1024) void abmil_bags_mb_combine_kernel(const float
     }
 }
 
-// Workgroups of the tile pass: two per CU fit (launch bounds), four waves of units keep the tail short.  HIPT_BAGS_MAX_WG (1..)
-// lowers the cap for A/B runs and tests: the results do not depend on it.
-constexpr int BAGS_MAX_WG = 2048;
-
 template <typename T, int S1, int S2>
 int launch_bags(const hipt_clam_weights* w, const void* bags, const void* units, int max_units, int attention_only, float* A_raw,
                 float* partials, hipStream_t st) {
     using G = AG<T, S1, S2>;
     constexpr int LDS = G::LDS + (sizeof(T) == 2 ? TM * S1 * 4 : 0);  // bf16: + the fp32 h1 image of the pooling (<= 130 KiB of the CU's 160)
-    int cap = BAGS_MAX_WG;
-    if (const char* e = getenv("HIPT_BAGS_MAX_WG")) {
-        const int v = atoi(e);
-        if (v >= 1 && v < cap) cap = v;
-    }
-    const int grid = max_units < cap ? max_units : cap;
+    const int grid = tile_pass_grid(max_units);
     auto k = abmil_bags_kernel<T, S1, S2>;
     static DeviceSetup setup;
     if (int rc = setup({(const void*)k}, LDS, "abmil_bags")) return rc;
@@ -691,12 +679,7 @@ int launch_bags_mb(const hipt_clam_weights* w, const void* bags, const void* uni
                    int64_t a_stride, float* A_raw, float* partials, hipStream_t st) {
     using G = AG<T, S1, S2>;
     constexpr int LDS = G::LDS_MB + (sizeof(T) == 2 ? TM * S1 * 4 : 0);  // bf16: + the fp32 h1 image of the pooling (<= 135 KiB of the CU's 160)
-    int cap = BAGS_MAX_WG;
-    if (const char* e = getenv("HIPT_BAGS_MAX_WG")) {
-        const int v = atoi(e);
-        if (v >= 1 && v < cap) cap = v;
-    }
-    const int grid = max_units < cap ? max_units : cap;
+    const int grid = tile_pass_grid(max_units);
     auto k = abmil_bags_mb_kernel<T, S1, S2>;
     static DeviceSetup setup;
     if (int rc = setup({(const void*)k}, LDS, "abmil_bags_mb")) return rc;
@@ -745,7 +728,7 @@ int hipt_clam_bags_units_launch(const int64_t* offsets, int B, int64_t total_row
 }
 
 int hipt_clam_bags_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
-                                int attention_only, float* A_raw, float* partials, hipStream_t st) {
+                                int attention_only, int64_t /*a_stride: one branch*/, float* A_raw, float* partials, hipStream_t st) {
     int rc = HIPT_E_UNSUPPORTED;
     const bool found = visit_width(w->dtype, w->s1, w->s2, [&](auto wd) {
         using W = decltype(wd);

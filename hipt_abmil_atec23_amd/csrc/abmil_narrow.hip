@@ -21,8 +21,6 @@
 namespace {
 using namespace abmil_tile;
 
-struct BagUnit { int64_t m0, end; };  // abmil_bags.hip's record (hipt_clam_bags_unit_bytes() is checked against it at launch)
-
 template <typename T, int S1, int S2> struct NG {
     static constexpr int KB = Tr<T>::KB;
     static constexpr int S1P = S1 < 16 ? 16 : S1;    // W1 rows of the operand image (whole 16-row fragments)
@@ -207,18 +205,11 @@ __global__ __launch_bounds__(256, 2) void abmil_narrow_kernel(const T* __restric
     }
 }
 
-constexpr int NARROW_MAX_WG = 2048;  // as abmil_bags.hip's tile pass; HIPT_BAGS_MAX_WG lowers it the same way
-
 template <typename T, int S1, int S2>
 int launch_narrow(const hipt_clam_weights* w, const void* bags, const void* units, int max_units, int attention_only, float* A_raw,
                   float* partials, hipStream_t st) {
     using G = NG<T, S1, S2>;
-    int cap = NARROW_MAX_WG;
-    if (const char* e = getenv("HIPT_BAGS_MAX_WG")) {
-        const int v = atoi(e);
-        if (v >= 1 && v < cap) cap = v;
-    }
-    const int grid = max_units < cap ? max_units : cap;
+    const int grid = tile_pass_grid(max_units);
     auto k = abmil_narrow_kernel<T, S1, S2>;
     static DeviceSetup setup;
     if (int rc = setup({(const void*)k}, G::LDS, "abmil_narrow")) return rc;
@@ -236,11 +227,7 @@ bool hipt_clam_narrow_supported(const hipt_clam_weights* w) {
 }
 
 int hipt_clam_narrow_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
-                                  int attention_only, float* A_raw, float* partials, hipStream_t st) {
-    if (hipt_clam_bags_unit_bytes() != sizeof(BagUnit)) {
-        hipt_set_error("clam narrow bags: unit record of %zu bytes, expected %zu", hipt_clam_bags_unit_bytes(), sizeof(BagUnit));
-        return HIPT_E_LAUNCH;
-    }
+                                  int attention_only, int64_t /*a_stride: one branch*/, float* A_raw, float* partials, hipStream_t st) {
     int rc = HIPT_E_UNSUPPORTED;
     const bool found = visit_narrow(w->dtype, w->s1, w->s2, [&](auto wd) {
         using W = decltype(wd);

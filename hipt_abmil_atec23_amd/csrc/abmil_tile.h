@@ -1,9 +1,11 @@
 // What the single-bag kernel (abmil.hip) and the ragged multi-bag kernel (abmil_bags.hip) of the fused CLAM_SB / ABMIL row tile share:
 // tile height, LDS budget and carve of one [T, S1, S2] instantiation, lane geometry, the swizzled h1 image, the gate's two
 // transcendental functions, tile_max and store_partial, bag_head (the tail of both combine kernels) and the one table of supported
-// widths (visit_width).  The GEMM phases and the fp32 pooling are still written out in both kernels: lifted into functions here they
+// widths (visit_width); and, of the multi-bag tile passes (abmil_bags.hip, abmil_narrow.hip), the unit record and the grid.  The GEMM phases and the fp32 pooling are still written out in both kernels: lifted into functions here they
 // compiled to different, slower code.
 #pragma once
+#include <cstdlib>
+
 #include "common.h"
 
 namespace abmil_tile {
@@ -152,6 +154,21 @@ template <typename F> bool visit_narrow(int dtype, int s1, int s2, F&& f) {
     }
 #undef HIPT_ABMIL_N
     return false;
+}
+
+// ---- the multi-bag tile passes (abmil_bags.hip, abmil_narrow.hip) ----
+// A work unit: rows [m0, min(m0 + TM, end)) of the concatenated matrix; m0 < 0: no unit (the table is sized from an upper bound)
+struct BagUnit { int64_t m0, end; };
+
+// Workgroups of a tile pass over max_units units: two per CU fit (launch bounds), four waves of units keep the tail short.
+// HIPT_BAGS_MAX_WG (1..) lowers the cap for A/B runs and tests: the results do not depend on it.
+inline int tile_pass_grid(int max_units) {
+    int cap = 2048;
+    if (const char* e = getenv("HIPT_BAGS_MAX_WG")) {
+        const int v = atoi(e);
+        if (v >= 1 && v < cap) cap = v;
+    }
+    return max_units < cap ? max_units : cap;
 }
 
 }  // namespace abmil_tile

@@ -1159,13 +1159,41 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
     return HIPT_OK;
 }
 
-// ---- B bags in one call (abmil_bags.hip): unit table | tile_start | one partial per unit; no state ----
+// ---- B bags in one call (abmil_bags.hip, abmil_narrow.hip): unit table | tile_start | one partial per unit and branch; no state ----
+// The call exists in three forms -- the wide single-branch heads, the narrow heads, the K = n_att branches of CLAM_MB -- which share
+// every line of the host side but the four things a ClamBagsForm names.
 int hipt_clam_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && w->s0 > 0 && hipt_clam_fused_supported(w) ? 1 : 0; }
+int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_narrow_supported(w) ? 1 : 0; }
+int hipt_clam_mb_bags_supported(const hipt_clam_weights* w) {
+    return hipt_clam_bags_supported(w) && w->n_att >= 2 && w->n_att <= 4 && w->n_att == w->n_classes ? 1 : 0;
+}
+
+struct ClamBagsForm {
+    const char* name;                                // of the entry point, as every message starts
+    int (*supported)(const hipt_clam_weights*);
+    int (*branches)(const hipt_clam_weights*);       // partials per unit
+    decltype(&hipt_clam_bags_tiles_launch) tiles;
+    decltype(&hipt_clam_bags_combine_launch) combine;
+    const char* why_not;                             // format of the unsupported message: name, S0, S1, S2, n_att, n_classes
+};
+static int one_branch(const hipt_clam_weights*) { return 1; }
+static int att_branches(const hipt_clam_weights* w) { return w->n_att; }
+static const ClamBagsForm BAGS_SB = {"clam_sb_forward_bags", hipt_clam_bags_supported, one_branch, hipt_clam_bags_tiles_launch,
+                                     hipt_clam_bags_combine_launch,
+                                     "%s: no multi-bag form for [%d,%d,%d] in this dtype: call hipt_clam_sb_forward per bag"};
+static const ClamBagsForm BAGS_NARROW = {"clam_sb_forward_bags_narrow", hipt_clam_narrow_bags_supported, one_branch,
+                                         hipt_clam_narrow_tiles_launch, hipt_clam_bags_combine_launch,
+                                         "%s: [%d,%d,%d] is not a narrow head: (S1, S2) in {(8,4), (16,8), (32,8), (32,16)}, S0 a "
+                                         "multiple of 32 (fp32) / 64 (bf16)"};
+static const ClamBagsForm BAGS_MB = {"clam_mb_forward_bags", hipt_clam_mb_bags_supported, att_branches, hipt_clam_bags_mb_tiles_launch,
+                                     hipt_clam_bags_mb_combine_launch,
+                                     "%s: no multi-bag form for [%d,%d,%d] with %d branches / %d classes in this dtype: call "
+                                     "hipt_clam_mb_forward or hipt_clam_sb_forward per bag"};
 
 // units of a call: sum_b ceil(N_b / 128) <= total_rows / 128 + B, known without reading the offsets back
 static int64_t clam_bags_max_units(int B, int64_t total_rows) { return (total_rows + 127) / 128 + B; }
 struct ClamBagsWs { void* units; int* tile_start; float* partials; };
-static ClamBagsWs carve_clam_bags(Carver& c, const hipt_clam_weights* w, int B, int64_t total_rows, int branches = 1) {
+static ClamBagsWs carve_clam_bags(Carver& c, const hipt_clam_weights* w, int B, int64_t total_rows, int branches) {
     const size_t nu = (size_t)clam_bags_max_units(B, total_rows);
     ClamBagsWs k;
     k.units = c.take(nu * hipt_clam_bags_unit_bytes());
@@ -1174,115 +1202,51 @@ static ClamBagsWs carve_clam_bags(Carver& c, const hipt_clam_weights* w, int B, 
     return k;
 }
 
-size_t hipt_clam_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows) {
-    if (!hipt_clam_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
-    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows); });
+static size_t clam_bags_ws_bytes(const ClamBagsForm& f, const hipt_clam_weights* w, int B, int64_t total_rows) {
+    if (!f.supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
+    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows, f.branches(w)); });
 }
 
-int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
-                              int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat, void* workspace,
-                              size_t ws_bytes, void* stream) {
+static int clam_bags_forward(const ClamBagsForm& f, const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B,
+                             int64_t total_rows, int attention_only, float* A_raw, float* M, float* logits, float* Y_prob,
+                             int64_t* Y_hat, void* workspace, size_t ws_bytes, void* stream) {
+    HIPT_CHECK_ARG(w != nullptr, "%s: null weights", f.name);
     int rc = check_clam(w);
     if (rc) return rc;
-    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "clam_sb_forward_bags: null argument");
-    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "clam_sb_forward_bags: null output");
-    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "clam_sb_forward_bags: bags must be 16-byte aligned");
-    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "clam_sb_forward_bags: B = %d bags need at least one row each (total_rows = %lld)", B,
+    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "%s: null argument", f.name);
+    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "%s: null output", f.name);
+    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "%s: bags must be 16-byte aligned", f.name);
+    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "%s: B = %d bags need at least one row each (total_rows = %lld)", f.name, B,
                    (long long)total_rows);
-    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "clam_sb_forward_bags: %lld rows in %d bags exceed 2^31 tiles",
+    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "%s: %lld rows in %d bags exceed 2^31 tiles", f.name,
                    (long long)total_rows, B);
-    if (!hipt_clam_bags_supported(w)) {
-        hipt_set_error("clam_sb_forward_bags: no multi-bag form for [%d,%d,%d] in this dtype: call hipt_clam_sb_forward per bag", w->s0, w->s1,
-                       w->s2);
+    if (!f.supported(w)) {
+        hipt_set_error(f.why_not, f.name, w->s0, w->s1, w->s2, w->n_att, w->n_classes);  // (a format may leave trailing arguments unread)
         return HIPT_E_UNSUPPORTED;
     }
     Carver c(workspace, ws_bytes);
-    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows);
-    if (check_workspace(c, "clam_sb_forward_bags")) return HIPT_E_BADARG;  // this entry point's contract: a short buffer is a bad argument
+    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows, f.branches(w));
+    if (check_workspace(c, f.name)) return HIPT_E_BADARG;  // these entry points' contract: a short buffer is a bad argument
     hipStream_t st = S(stream);
     const int nu = (int)clam_bags_max_units(B, total_rows);
     PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
-    PROF(PC_ABMIL, hipt_clam_bags_tiles_launch(w, bags, k.units, nu, attention_only, A_raw, k.partials, st));
+    PROF(PC_ABMIL, f.tiles(w, bags, k.units, nu, attention_only, total_rows, A_raw, k.partials, st));  // A_raw [branches, total_rows]
     if (attention_only) return HIPT_OK;
-    PROF(PC_COMBINE, hipt_clam_bags_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
+    PROF(PC_COMBINE, f.combine(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
     return HIPT_OK;
 }
 
-// ---- the same call for the narrow heads (abmil_narrow.hip): its own envelope and tile kernel; units, carve and combine shared ----
-int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_narrow_supported(w) ? 1 : 0; }
-
-size_t hipt_clam_narrow_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows) {
-    if (!hipt_clam_narrow_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
-    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows); });
-}
-
-int hipt_clam_sb_forward_bags_narrow(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
-                                     int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
-                                     void* workspace, size_t ws_bytes, void* stream) {
-    int rc = check_clam(w);
-    if (rc) return rc;
-    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "clam_sb_forward_bags_narrow: null argument");
-    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "clam_sb_forward_bags_narrow: null output");
-    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "clam_sb_forward_bags_narrow: bags must be 16-byte aligned");
-    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "clam_sb_forward_bags_narrow: B = %d bags need at least one row each (total_rows = %lld)", B,
-                   (long long)total_rows);
-    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "clam_sb_forward_bags_narrow: %lld rows in %d bags exceed 2^31 tiles",
-                   (long long)total_rows, B);
-    if (!hipt_clam_narrow_bags_supported(w)) {
-        hipt_set_error("clam_sb_forward_bags_narrow: [%d,%d,%d] is not a narrow head: (S1, S2) in {(8,4), (16,8), (32,8), (32,16)}, S0 a "
-                       "multiple of 32 (fp32) / 64 (bf16)", w->s0, w->s1, w->s2);
-        return HIPT_E_UNSUPPORTED;
+#define HIPT_CLAM_BAGS_ENTRY(forward, ws_bytes_fn, form)                                                                                 \
+    size_t ws_bytes_fn(const hipt_clam_weights* w, int B, int64_t total_rows) { return clam_bags_ws_bytes(form, w, B, total_rows); }     \
+    int forward(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows, int attention_only, \
+                float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat, void* workspace, size_t ws_bytes, void* stream) {  \
+        return clam_bags_forward(form, w, bags, offsets_dev, B, total_rows, attention_only, A_raw, M, logits, Y_prob, Y_hat, workspace,  \
+                                 ws_bytes, stream);                                                                                      \
     }
-    Carver c(workspace, ws_bytes);
-    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows);
-    if (check_workspace(c, "clam_sb_forward_bags_narrow")) return HIPT_E_BADARG;  // as hipt_clam_sb_forward_bags: a short buffer is a bad argument
-    hipStream_t st = S(stream);
-    const int nu = (int)clam_bags_max_units(B, total_rows);
-    PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
-    PROF(PC_ABMIL, hipt_clam_narrow_tiles_launch(w, bags, k.units, nu, attention_only, A_raw, k.partials, st));
-    if (attention_only) return HIPT_OK;
-    PROF(PC_COMBINE, hipt_clam_bags_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
-    return HIPT_OK;
-}
-
-// ---- the same for the K = n_att branches of CLAM_MB: K partials per unit ----
-int hipt_clam_mb_bags_supported(const hipt_clam_weights* w) {
-    return hipt_clam_bags_supported(w) && w->n_att >= 2 && w->n_att <= 4 && w->n_att == w->n_classes ? 1 : 0;
-}
-
-size_t hipt_clam_mb_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows) {
-    if (!hipt_clam_mb_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
-    return dry_run([&](Carver& c) { carve_clam_bags(c, w, B, total_rows, w->n_att); });
-}
-
-int hipt_clam_mb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
-                              int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat, void* workspace,
-                              size_t ws_bytes, void* stream) {
-    int rc = check_clam(w);
-    if (rc) return rc;
-    HIPT_CHECK_ARG(bags && offsets_dev && A_raw && workspace, "clam_mb_forward_bags: null argument");
-    HIPT_CHECK_ARG(attention_only || (M && logits && Y_prob && Y_hat), "clam_mb_forward_bags: null output");
-    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0, "clam_mb_forward_bags: bags must be 16-byte aligned");
-    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "clam_mb_forward_bags: B = %d bags need at least one row each (total_rows = %lld)", B,
-                   (long long)total_rows);
-    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "clam_mb_forward_bags: %lld rows in %d bags exceed 2^31 tiles",
-                   (long long)total_rows, B);
-    if (!hipt_clam_mb_bags_supported(w)) {
-        hipt_set_error("clam_mb_forward_bags: no multi-bag form for [%d,%d,%d] with %d branches / %d classes in this dtype: call "
-                       "hipt_clam_mb_forward or hipt_clam_sb_forward per bag", w->s0, w->s1, w->s2, w->n_att, w->n_classes);
-        return HIPT_E_UNSUPPORTED;
-    }
-    Carver c(workspace, ws_bytes);
-    const ClamBagsWs k = carve_clam_bags(c, w, B, total_rows, w->n_att);
-    if (check_workspace(c, "clam_mb_forward_bags")) return HIPT_E_BADARG;  // as hipt_clam_sb_forward_bags: a short buffer is a bad argument
-    hipStream_t st = S(stream);
-    const int nu = (int)clam_bags_max_units(B, total_rows);
-    PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
-    PROF(PC_ABMIL, hipt_clam_bags_mb_tiles_launch(w, bags, k.units, nu, attention_only, total_rows, A_raw, k.partials, st));
-    if (attention_only) return HIPT_OK;
-    PROF(PC_COMBINE, hipt_clam_bags_mb_combine_launch(k.partials, k.tile_start, nu, B, w, M, logits, Y_prob, Y_hat, st));
-    return HIPT_OK;
-}
+HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags, hipt_clam_bags_workspace_bytes, BAGS_SB)
+HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags_narrow, hipt_clam_narrow_bags_workspace_bytes, BAGS_NARROW)
+HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags, hipt_clam_mb_bags_workspace_bytes, BAGS_MB)
+#undef HIPT_CLAM_BAGS_ENTRY
 
 int hipt_clam_mb_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_mb_stream_supported(w) ? 1 : 0; }
 

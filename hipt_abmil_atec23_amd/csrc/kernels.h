@@ -220,11 +220,12 @@ int hipt_gather_h1_launch(const hipt_clam_weights* w, const void* bag, const int
                           hipStream_t st);
 // ragged multi-bag CLAM_SB (abmil_bags.hip): offsets -> unit table (one unit = one 128-row tile of one bag; `units` holds max_units entries of
 // hipt_clam_bags_unit_bytes(), tile_start B+1 ints), the tile pass over the units, the per-bag combine.  Widths: hipt_clam_fused_supported.
+// The three tile launchers share one signature (capi.hip picks one from a table): A_raw is [branches, a_stride]; with one branch a_stride goes unused.
 size_t hipt_clam_bags_unit_bytes();
 int hipt_clam_bags_units_launch(const int64_t* offsets, int B, int64_t total_rows, int max_units, int* tile_start, void* units,
                                 hipStream_t st);
 int hipt_clam_bags_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
-                                int attention_only, float* A_raw, float* partials, hipStream_t st);
+                                int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
 int hipt_clam_bags_combine_launch(const float* partials, const int* tile_start, int max_units, int B,
                                   const hipt_clam_weights* w, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                                   hipStream_t st);
@@ -232,7 +233,7 @@ int hipt_clam_bags_combine_launch(const float* partials, const int* tile_start, 
 // unit table in, the same partials out (one (max, sum, acc[S1]) per unit), so the units and combine launches above serve it unchanged
 bool hipt_clam_narrow_supported(const hipt_clam_weights* w);
 int hipt_clam_narrow_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
-                                  int attention_only, float* A_raw, float* partials, hipStream_t st);
+                                  int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
 // the same over w->n_att = 2..4 attention branches (CLAM_MB): A_raw [K, a_stride], K partials per unit, M [B, K, S1], logits / Y_prob [B, K]
 int hipt_clam_bags_mb_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
                                    int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);

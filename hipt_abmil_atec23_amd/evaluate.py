@@ -87,6 +87,40 @@ class _attr_for_call:
         return False
 
 
+def _prepare(model, bags_or_loader, labels, n_classes, loss_fn):
+    """What both split functions start from: ``(bags, labels, loss_fn, device, (logits [n, C], probs [n, C], preds [n]))`` -- the
+    checked split, the model's device (the bags' for a model without parameters) and the host buffers the runs are copied into."""
+    bags, labels = _split(bags_or_loader, labels)
+    n = len(bags)
+    if any(l < 0 or l >= n_classes for l in labels):
+        raise ValueError(f"labels must lie in [0, {n_classes})")
+    params = list(model.parameters()) if hasattr(model, "parameters") else []
+    dev = params[0].device if params else bags[0].device
+    out = (torch.empty((n, n_classes), dtype=torch.float32), torch.empty((n, n_classes), dtype=torch.float32),
+           torch.empty((n,), dtype=torch.int64))
+    return bags, labels, F.cross_entropy if loss_fn is None else loss_fn, dev, out
+
+
+def _copy_back(run, out, logits, probs, preds):
+    """The one trip to the host of a run: its ``(logits, Y_prob, Y_hat, ...)`` into rows ``run`` of the split's buffers."""
+    sl = slice(run.start, run.stop)
+    logits[sl], probs[sl], preds[sl] = out[0].float().cpu(), out[1].float().cpu(), out[2].reshape(-1).cpu()
+
+
+def _mean_loss(loss_fn, logits, labels):
+    lab = torch.tensor(labels, dtype=torch.int64)
+    return sum(float(loss_fn(logits[i:i + 1], lab[i:i + 1])) for i in range(len(labels))) / len(labels)
+
+
+def _tally(preds, labels, n_classes):
+    """``(acc, error)``: ``Accuracy_Logger.data`` per bag class and the mean of ``calculate_error``."""
+    acc = [{"count": 0, "correct": 0} for _ in range(n_classes)]
+    for p, l in zip(preds.tolist(), labels):
+        acc[l]["count"] += 1
+        acc[l]["correct"] += int(p == l)
+    return acc, sum(d["count"] - d["correct"] for d in acc) / len(labels)
+
+
 def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
                    max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True) -> SplitResult:
     """Evaluate ``model`` on every bag of a split.  ``bags_or_loader``: a sequence of ``[N_b, S0]`` tensors with ``labels``, or an
@@ -98,39 +132,21 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     (``hipt_smaller``, ``hipt_smallest``, ...: ``hipt_clam_narrow_bags_supported``) the numbers then come from the one-call kernel
     ``hipt_clam_sb_forward_bags_narrow``.  They equal those of the loop over ``forward`` (``narrow_one_call=False``) within the
     fp32 bar (1e-4); they are not bit-equal to it."""
-    bags, labels = _split(bags_or_loader, labels)
-    n = len(bags)
-    if any(l < 0 or l >= n_classes for l in labels):
-        raise ValueError(f"labels must lie in [0, {n_classes})")
-    if loss_fn is None:
-        loss_fn = F.cross_entropy
-    params = list(model.parameters()) if hasattr(model, "parameters") else []
-    dev = params[0].device if params else bags[0].device
+    bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     fb = getattr(model, "forward_bags", None)
-    logits = torch.empty((n, n_classes), dtype=torch.float32)
-    probs = torch.empty((n, n_classes), dtype=torch.float32)
-    preds = torch.empty((n,), dtype=torch.int64)
     with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call):
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             part = [bags[i].to(dev) for i in run]
             if fb is not None:
-                lg, yp, yh = fb(part)[:3]
+                out = fb(part)
             else:
                 outs = [model(b) for b in part]
-                lg, yp, yh = (torch.cat([o[k] for o in outs], dim=0) for k in range(3))
-            sl = slice(run.start, run.stop)
-            logits[sl], probs[sl], preds[sl] = lg.float().cpu(), yp.float().cpu(), yh.reshape(-1).cpu()
-        lab = torch.tensor(labels, dtype=torch.int64)
-        loss = sum(float(loss_fn(logits[i:i + 1], lab[i:i + 1])) for i in range(n)) / n
-    acc = [{"count": 0, "correct": 0} for _ in range(n_classes)]
-    wrong = 0.0
-    for i in range(n):
-        hit = int(preds[i]) == labels[i]
-        acc[labels[i]]["count"] += 1
-        acc[labels[i]]["correct"] += int(hit)
-        wrong += 0.0 if hit else 1.0
+                out = [torch.cat([o[k] for o in outs], dim=0) for k in range(3)]
+            _copy_back(run, out, logits, probs, preds)
+        loss = _mean_loss(loss_fn, logits, labels)
+    acc, error = _tally(preds, labels, n_classes)
     return SplitResult(all_probs=probs.numpy().astype(np.float64), all_labels=np.asarray(labels, dtype=np.float64),
-                       all_preds=preds.numpy().astype(np.float64), error=wrong / n, loss=loss, acc=acc)
+                       all_preds=preds.numpy().astype(np.float64), error=error, loss=loss, acc=acc)
 
 
 @dataclass
@@ -154,54 +170,27 @@ def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     a ``CLAM_SB`` with ``bags_narrow = narrow_one_call``: for the narrow heads (``hipt_smaller``, ``hipt_smallest``, ...) the numbers
     then come from the one-call kernel; they equal the loop's (``narrow_one_call=False``) within the fp32 bar (1e-4), not bit for bit.
     The AUC stays with the caller (``labels`` and ``prob`` are its inputs).  The model is put in eval mode, as ``validate_clam`` does."""
-    bags, labels = _split(bags_or_loader, labels)
+    bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     n = len(bags)
-    if any(l < 0 or l >= n_classes for l in labels):
-        raise ValueError(f"labels must lie in [0, {n_classes})")
-    if loss_fn is None:
-        loss_fn = F.cross_entropy
-    params = list(model.parameters())
-    dev = params[0].device if params else bags[0].device
-    logits = torch.empty((n, n_classes), dtype=torch.float32)
-    probs = torch.empty((n, n_classes), dtype=torch.float32)
-    preds = torch.empty((n,), dtype=torch.int64)
     inst_loss = torch.empty((n,), dtype=torch.float32)
     inst = [{"count": 0, "correct": 0} for _ in range(n_classes)]
-    had = hasattr(type(model), "bags_one_call")
-    before = model.__dict__.get("bags_one_call", None)
-    if had:
-        model.bags_one_call = bool(mb_one_call)
     model.eval()
-    try:
-        with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call):
-            for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
-                lg, yp, yh, _, res = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
-                sl = slice(run.start, run.stop)
-                logits[sl], probs[sl], preds[sl] = lg.float().cpu(), yp.float().cpu(), yh.reshape(-1).cpu()
-                inst_loss[sl] = res["instance_loss"].float().cpu()
-                for p, t in zip(res["inst_preds"], res["inst_labels"]):     # Accuracy_Logger.log_batch, one slide at a time
-                    p, t = np.asarray(p).astype(int), np.asarray(t).astype(int)
-                    for c in np.unique(t):
-                        mask = t == c
-                        inst[c]["count"] += int(mask.sum())
-                        inst[c]["correct"] += int((p[mask] == t[mask]).sum())
-            lab = torch.tensor(labels, dtype=torch.int64)
-            loss = sum(float(loss_fn(logits[i:i + 1], lab[i:i + 1])) for i in range(n)) / n
-    finally:
-        if had:
-            if before is None:
-                del model.bags_one_call      # back to the class attribute
-            else:
-                model.bags_one_call = before
-    acc = [{"count": 0, "correct": 0} for _ in range(n_classes)]
-    wrong = 0.0
-    for i in range(n):
-        hit = int(preds[i]) == labels[i]
-        acc[labels[i]]["count"] += 1
-        acc[labels[i]]["correct"] += int(hit)
-        wrong += 0.0 if hit else 1.0
+    with torch.no_grad(), _attr_for_call(model, "bags_one_call", mb_one_call), _attr_for_call(model, "bags_narrow", narrow_one_call):
+        for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
+            out = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
+            _copy_back(run, out, logits, probs, preds)
+            res = out[4]
+            inst_loss[run.start:run.stop] = res["instance_loss"].float().cpu()
+            for p, t in zip(res["inst_preds"], res["inst_labels"]):     # Accuracy_Logger.log_batch, one slide at a time
+                p, t = np.asarray(p).astype(int), np.asarray(t).astype(int)
+                for c in np.unique(t):
+                    mask = t == c
+                    inst[c]["count"] += int(mask.sum())
+                    inst[c]["correct"] += int((p[mask] == t[mask]).sum())
+        loss = _mean_loss(loss_fn, logits, labels)
+    acc, error = _tally(preds, labels, n_classes)
     return ValidationResult(prob=probs.numpy().astype(np.float64), labels=np.asarray(labels, dtype=np.float64), val_loss=loss,
-                            val_error=wrong / n, acc=acc, val_inst_loss=sum(float(v) for v in inst_loss) / n, inst_count=n, inst=inst)
+                            val_error=error, acc=acc, val_inst_loss=sum(float(v) for v in inst_loss) / n, inst_count=n, inst=inst)
 
 
 def validate_clam_like(ref_module, max_rows_per_call: int = DEFAULT_MAX_ROWS) -> Callable:

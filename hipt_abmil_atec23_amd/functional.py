@@ -84,7 +84,7 @@ def attention(qkv: torch.Tensor, num_heads: int, scale: float, dtype: int = N.HI
     return out, probs
 
 
-# ---- CLAM_SB over many bags in one call (include/hipt_abmil.h: hipt_clam_sb_forward_bags) ----
+# ---- CLAM over many bags in one call (include/hipt_abmil.h: hipt_clam_sb_forward_bags and its narrow / CLAM_MB forms) ----
 def check_offsets(offsets, rows: int) -> tuple:
     """The B+1 row offsets of a multi-bag call as a tuple of ints, or ``ValueError``: they start at 0, increase strictly (no
     empty bag) and end at ``rows``.  The library trusts what it is handed, so every upload goes through here first."""
@@ -116,75 +116,60 @@ class BagOffsets:
         return len(self.host) - 1
 
 
-def clam_sb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_sb_forward_bags`` on ``cat [rows, S0]`` (already in the dtype of the weight image ``w``, an ``_native.ClamWeights``).
-    Returns ``(A_raw [rows], M [B, S1], logits [B, C], Y_prob [B, C], Y_hat [B])`` -- the last four ``None`` with ``attention_only``.
-    ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions, sentinels)."""
+# form -> (native call, its workspace size, shapes of (A_raw, M, logits / Y_prob) for B bags of `rows` rows in all); Y_hat is [B]
+_sb_shapes = lambda w, B, rows: ((rows,), (B, w.s1), (B, w.n_classes))
+_BAGS_FORMS = {
+    "sb": ("hipt_clam_sb_forward_bags", "hipt_clam_bags_workspace_bytes", _sb_shapes),
+    "narrow": ("hipt_clam_sb_forward_bags_narrow", "hipt_clam_narrow_bags_workspace_bytes", _sb_shapes),
+    "mb": ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes",
+           lambda w, B, rows: ((w.n_att, rows), (B, w.n_att, w.s1), (B, w.n_att))),
+}
+
+
+def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None, form: str = "sb"):
+    """The multi-bag CLAM forward in the form ``"sb"``, ``"narrow"`` or ``"mb"`` (include/hipt_abmil.h) on ``cat [rows, S0]``, already
+    in the dtype of the weight image ``w`` (an ``_native.ClamWeights``).  Returns ``(A_raw, M, logits, Y_prob, Y_hat)`` -- the last
+    four ``None`` with ``attention_only``.  ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions,
+    sentinels)."""
     import ctypes as C
-    N.require_cuda(cat, "clam_sb_forward_bags")
+    sym, ws_sym, shapes = _BAGS_FORMS[form]
+    what = sym[len("hipt_"):]
+    N.require_cuda(cat, what)
     dev, B, rows = cat.device, len(offsets), cat.shape[0]
     if cat.dim() != 2 or not cat.is_contiguous() or cat.dtype != _TORCH_DT[w.dtype] or cat.shape[1] != w.s0:
         raise ValueError(f"expected contiguous [rows, {w.s0}] bags in {_TORCH_DT[w.dtype]}, got {tuple(cat.shape)} {cat.dtype}")
     if offsets.host[-1] != rows:
         raise ValueError(f"bag offsets end at {offsets.host[-1]} but the concatenated bags have {rows} rows")
-    N.same_device("clam_sb_forward_bags", dev, offsets.dev)
+    N.same_device(what, dev, offsets.dev)
     st = N.stream_ptr(dev)
     if ws is None:
-        ws = workspace(dev, N.lib().hipt_clam_bags_workspace_bytes(C.byref(w), B, rows), ("clam_bags", st.value))
+        ws = workspace(dev, getattr(N.lib(), ws_sym)(C.byref(w), B, rows), ("clam_bags", st.value))
     if out is None:
-        e = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        out = (e(rows), None, None, None, None) if attention_only else (e(rows), e(B, w.s1), e(B, w.n_classes), e(B, w.n_classes), e(B, dt=torch.int64))
+        e = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        a, m, l = shapes(w, B, rows)
+        out = (e(a), None, None, None, None) if attention_only else (e(a), e(m), e(l), e(l), e((B,), torch.int64))
     A_raw, M, logits, Y_prob, Y_hat = out
-    N.call("hipt_clam_sb_forward_bags", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw),
-           N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
+    N.call(sym, C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw), N.ptr(M), N.ptr(logits),
+           N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
     return out
+
+
+def clam_sb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_sb_forward_bags``: returns ``(A_raw [rows], M [B, S1], logits [B, C], Y_prob [B, C], Y_hat [B])``."""
+    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "sb")
 
 
 def clam_sb_forward_bags_narrow(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
     """``hipt_clam_sb_forward_bags_narrow``: :func:`clam_sb_forward_bags` for the narrow heads (``hipt_clam_narrow_bags_supported``:
     ``(S1, S2)`` in {(8, 4), (16, 8), (32, 8), (32, 16)}, fp32 and bf16).  Arguments and results as there."""
-    import ctypes as C
-    N.require_cuda(cat, "clam_sb_forward_bags_narrow")
-    dev, B, rows = cat.device, len(offsets), cat.shape[0]
-    if cat.dim() != 2 or not cat.is_contiguous() or cat.dtype != _TORCH_DT[w.dtype] or cat.shape[1] != w.s0:
-        raise ValueError(f"expected contiguous [rows, {w.s0}] bags in {_TORCH_DT[w.dtype]}, got {tuple(cat.shape)} {cat.dtype}")
-    if offsets.host[-1] != rows:
-        raise ValueError(f"bag offsets end at {offsets.host[-1]} but the concatenated bags have {rows} rows")
-    N.same_device("clam_sb_forward_bags_narrow", dev, offsets.dev)
-    st = N.stream_ptr(dev)
-    if ws is None:
-        ws = workspace(dev, N.lib().hipt_clam_narrow_bags_workspace_bytes(C.byref(w), B, rows), ("clam_bags", st.value))
-    if out is None:
-        e = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        out = (e(rows), None, None, None, None) if attention_only else (e(rows), e(B, w.s1), e(B, w.n_classes), e(B, w.n_classes), e(B, dt=torch.int64))
-    A_raw, M, logits, Y_prob, Y_hat = out
-    N.call("hipt_clam_sb_forward_bags_narrow", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0,
-           N.ptr(A_raw), N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
-    return out
+    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "narrow")
 
 
 def clam_mb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
     """``hipt_clam_mb_forward_bags``: :func:`clam_sb_forward_bags` for the ``K = w.n_att`` branches of a stacked ``CLAM_MB`` weight image.
     Returns ``(A_raw [K, rows], M [B, K, S1], logits [B, K], Y_prob [B, K], Y_hat [B])``; bag ``b`` is the columns
     ``[offsets[b], offsets[b+1])`` of ``A_raw``."""
-    import ctypes as C
-    N.require_cuda(cat, "clam_mb_forward_bags")
-    dev, B, rows, K = cat.device, len(offsets), cat.shape[0], w.n_att
-    if cat.dim() != 2 or not cat.is_contiguous() or cat.dtype != _TORCH_DT[w.dtype] or cat.shape[1] != w.s0:
-        raise ValueError(f"expected contiguous [rows, {w.s0}] bags in {_TORCH_DT[w.dtype]}, got {tuple(cat.shape)} {cat.dtype}")
-    if offsets.host[-1] != rows:
-        raise ValueError(f"bag offsets end at {offsets.host[-1]} but the concatenated bags have {rows} rows")
-    N.same_device("clam_mb_forward_bags", dev, offsets.dev)
-    st = N.stream_ptr(dev)
-    if ws is None:
-        ws = workspace(dev, N.lib().hipt_clam_mb_bags_workspace_bytes(C.byref(w), B, rows), ("clam_bags", st.value))
-    if out is None:
-        e = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        out = (e(K, rows), None, None, None, None) if attention_only else (e(K, rows), e(B, K, w.s1), e(B, K), e(B, K), e(B, dt=torch.int64))
-    A_raw, M, logits, Y_prob, Y_hat = out
-    N.call("hipt_clam_mb_forward_bags", C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw),
-           N.ptr(M), N.ptr(logits), N.ptr(Y_prob), N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
-    return out
+    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb")
 
 
 def topk_segments(A: torch.Tensor, offsets: BagOffsets, k: int, want_global: bool = True):

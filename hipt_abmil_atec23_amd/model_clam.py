@@ -531,6 +531,21 @@ class CLAM_SB(WeightImageCache, nn.Module):
         cat = torch.cat(bags, dim=0)  # ONE concatenation, on the bags' device
         return cat, (Fn.BagOffsets(host, acc, cat.device) if cat.is_cuda else tuple(host))
 
+    def _bags_form(self, device):
+        """``(weight image, form)`` of the one ``functional.clam_forward_bags`` call that serves ``forward_bags`` on ``device``, or
+        None: the loop over ``forward``."""
+        if not self._gate or device.type != "cuda":
+            return None
+        lib = N.lib()
+        if self._multi:
+            w = self._pack_stacked(device) if self.bags_one_call else None
+            return (w, "mb") if w is not None and lib.hipt_clam_mb_bags_supported(C_.byref(w)) else None
+        w = self._pack(device)
+        if lib.hipt_clam_bags_supported(C_.byref(w)):
+            return w, "sb"   # (a width both kernels have keeps the wide one)
+        narrow = self.bags_narrow and lib.hipt_clam_narrow_bags_supported(C_.byref(w))   # hipt_smaller, hipt_smallest, ...: where asked for
+        return (w, "narrow") if narrow else None
+
     def forward_bags(self, bags, attention_only=False, return_features=False, label=None, instance_eval=False):
         """``forward`` over B bags at once, inference only (no autograd; dropout inactive as in ``eval()``).
 
@@ -563,31 +578,15 @@ class CLAM_SB(WeightImageCache, nn.Module):
                 if self.k_sample > host[b + 1] - host[b]:
                     raise RuntimeError(f"selected index k out of range: k_sample={self.k_sample} > {host[b + 1] - host[b]} rows (torch.topk, model_clam.py:120)")
         with torch.no_grad():
-            w, narrow = None, False
-            if self._gate and cat.is_cuda:
-                if not self._multi:
-                    w = self._pack(cat.device)
-                    if not N.lib().hipt_clam_bags_supported(C_.byref(w)):
-                        # a narrow head (hipt_smaller, hipt_smallest, ...): its own one-call kernel, where asked for
-                        narrow = self.bags_narrow and N.lib().hipt_clam_narrow_bags_supported(C_.byref(w))
-                        if not narrow:
-                            w = None
-                elif self.bags_one_call:
-                    w = self._pack_stacked(cat.device)
-                    if not N.lib().hipt_clam_mb_bags_supported(C_.byref(w)):
-                        w = None
-            if w is None:
+            route = self._bags_form(cat.device)
+            if route is None:
                 return self._forward_bags_loop(cat, host, attention_only, return_features, lab if inst else None)
+            w, form = route
             self._bags_route = "bags"
             x = Fn.as_compute(cat, w.dtype)
-            B = len(off)
-            if self._multi:
-                A_raw, M, logits, Y_prob, Y_hat = Fn.clam_mb_forward_bags(w, x, off, attention_only)
-                views = [A_raw[:, host[b]:host[b + 1]] for b in range(B)]
-            else:
-                call = Fn.clam_sb_forward_bags_narrow if narrow else Fn.clam_sb_forward_bags
-                A_raw, M, logits, Y_prob, Y_hat = call(w, x, off, attention_only)
-                views = [A_raw[host[b]:host[b + 1]].view(1, -1) for b in range(B)]
+            A_raw, M, logits, Y_prob, Y_hat = Fn.clam_forward_bags(w, x, off, attention_only, form=form)
+            A2 = A_raw if form == "mb" else A_raw.view(1, -1)          # [K, rows] / [1, rows]
+            views = [A2[:, host[b]:host[b + 1]] for b in range(len(off))]
             if attention_only:
                 return views
             results = self._instance_bags(w, x, off, A_raw, lab) if inst else {}

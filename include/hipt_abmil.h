@@ -369,51 +369,46 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
                          float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                          void* workspace, size_t ws_bytes, void* stream);
 
-/* CLAM_SB.forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).
+/* CLAM forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).  The call exists in three
+ * forms -- the wide gated heads, the narrow ones, the K branches of CLAM_MB -- each with its own <form>_supported, <form>_workspace_bytes and
+ * forward entry point of one signature.  What holds for all three is stated here, once; each form below lists only what differs.
  * bags: the bags' rows concatenated, [total_rows, S0] in w->dtype, 16-byte aligned; offsets_dev: int64[B + 1] in DEVICE memory, offsets[0] = 0,
  * increasing, offsets[B] = total_rows: bag b is rows [offsets[b], offsets[b+1]).  Every bag has at least one row.  The CONTENTS of the offsets
  * are the caller's responsibility (check them on the host before the upload); a bag whose offsets break the rules is left unwritten.
- * Outputs fp32: A_raw[total_rows], M[B, S1], logits[B, C], Y_prob[B, C]; Y_hat int64[B]; per bag exactly the quantities of hipt_clam_sb_forward.
- * attention_only != 0: only A_raw is written (M .. Y_hat may be NULL).
+ * Outputs fp32 and Y_hat int64[B], per bag exactly the quantities of the per-bag call.  attention_only != 0: only A_raw is written (M ..
+ * Y_hat may be NULL).
  * Three plain launches on `stream` (unit table from the offsets, 128-row tiles that never span two bags, one combine workgroup per bag): no
  * atomics, no waiting between workgroups, no host synchronisation or copy -- graph-capturable, and the workspace holds NO state (no ticket
- * block, nothing to zero).  A bag's five outputs are bit for bit independent of the other bags in the call, of its position and of B.
- * hipt_clam_bags_supported(w) != 0: the configuration has this form (fp32 S1 in {128, 64, 32}, bf16 S1 in {128, 64}; S2 in {64, 32, 16}; S0 a
- * multiple of 32 (fp32) / 64 (bf16)); otherwise HIPT_E_UNSUPPORTED and hipt_clam_bags_workspace_bytes = 0: loop over hipt_clam_sb_forward.
- * HIPT_E_BADARG -- before anything is launched or written -- for a null pointer, a misaligned `bags`, B < 1, total_rows < B, and for a
- * workspace smaller than hipt_clam_bags_workspace_bytes(w, B, total_rows) or not 256-byte aligned. */
+ * block, nothing to zero).  A bag's outputs are bit for bit independent of the other bags in the call, of its position and of B.
+ * <form>_supported(w) != 0: the configuration has this form; otherwise HIPT_E_UNSUPPORTED and <form>_workspace_bytes = 0: loop over the
+ * per-bag call.  HIPT_E_BADARG -- before anything is launched or written -- for a null pointer, a misaligned `bags`, B < 1, total_rows < B,
+ * and for a workspace smaller than <form>_workspace_bytes(w, B, total_rows) or not 256-byte aligned.
+ *
+ * The wide heads, CLAM_SB.forward per bag (hipt_clam_sb_forward): fp32 S1 in {128, 64, 32}, bf16 S1 in {128, 64}; S2 in {64, 32, 16}; S0 a
+ * multiple of 32 (fp32) / 64 (bf16).  A_raw[total_rows], M[B, S1], logits[B, C], Y_prob[B, C]. */
 int hipt_clam_bags_supported(const hipt_clam_weights* w);
 size_t hipt_clam_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
 int hipt_clam_sb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
                               int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                               void* workspace, size_t ws_bytes, void* stream);
 
-/* hipt_clam_sb_forward_bags for the NARROW gated heads, which that call does not take: (S1, S2) in {(8, 4), (16, 8), (32, 8), (32, 16)} in fp32
- * and in bf16, S0 a multiple of 32 (fp32) / 64 (bf16) -- the reference's hipt_smallest [192, 8, 4] and hipt_smaller [192, 16, 8] among them.
- * Arguments, outputs, the three plain launches (the same unit table and the same per-bag combine; the tile pass is a kernel of its own), the
- * absence of atomics, tickets and workspace state, graph capture and the bit-for-bit independence of a bag from the other bags of the
- * call: as there.  Rounding in bf16: the bag, W1, Wa and Wb are bf16; h1, the gate and the pooling are fp32 (the model of hipt_clam_sb_forward
- * for these widths).  fp32 (32, 16) is taken by both calls; their results agree within fp32 rounding, not bit for bit.
- * hipt_clam_narrow_bags_supported(w) != 0: the configuration has this form; otherwise HIPT_E_UNSUPPORTED and
- * hipt_clam_narrow_bags_workspace_bytes = 0.  HIPT_E_BADARG, before anything is launched, for a null pointer, a misaligned `bags`, B < 1,
- * total_rows < B and a workspace smaller than hipt_clam_narrow_bags_workspace_bytes(w, B, total_rows) or not 256-byte aligned. */
+/* The NARROW gated heads, which the wide form does not take: (S1, S2) in {(8, 4), (16, 8), (32, 8), (32, 16)} in fp32 and in bf16, S0 a
+ * multiple of 32 (fp32) / 64 (bf16) -- the reference's hipt_smallest [192, 8, 4] and hipt_smaller [192, 16, 8] among them.  Outputs as the
+ * wide form; the same unit table and per-bag combine, the tile pass is a kernel of its own.  Rounding in bf16: the bag, W1, Wa and Wb are
+ * bf16; h1, the gate and the pooling are fp32 (the model of hipt_clam_sb_forward for these widths).  fp32 (32, 16) is taken by both forms;
+ * their results agree within fp32 rounding, not bit for bit. */
 int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w);
 size_t hipt_clam_narrow_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
 int hipt_clam_sb_forward_bags_narrow(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
                                      int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                                      void* workspace, size_t ws_bytes, void* stream);
 
-/* CLAM_MB.forward (model_clam.py:226-264) over B bags in ONE call: hipt_clam_sb_forward_bags for the K = w->n_att attention branches of a
- * hipt_clam_weights stacked as hipt_clam_mb_forward takes it (wc [K, S2], bc [K], wcls [K, S1], bcls [K], n_classes = K; stream_pk and
- * logit_bound are not read).  bags / offsets_dev / B / total_rows / workspace rules, the three plain launches, the absence of atomics,
- * tickets and workspace state, graph capture and the bit-for-bit independence of a bag from the other bags of the call: as there.
- * Outputs fp32: A_raw [K, total_rows] -- branch k of row m at A_raw[k * total_rows + m], so bag b is the [K, N_b] window of columns
+/* CLAM_MB.forward (model_clam.py:226-264): the K = w->n_att attention branches of a hipt_clam_weights stacked as hipt_clam_mb_forward takes
+ * it (wc [K, S2], bc [K], wcls [K, S1], bcls [K], n_classes = K; stream_pk and logit_bound are not read).  Supported: hipt_clam_bags_supported(w)
+ * and 2 <= n_att <= 4 and n_att == n_classes.  K partials per work unit in the workspace.
+ * A_raw [K, total_rows] -- branch k of row m at A_raw[k * total_rows + m], so bag b is the [K, N_b] window of columns
  * [offsets[b], offsets[b+1]) with row stride total_rows --, M [B, K, S1], logits [B, K] (logits[b, k] = wcls[k] . M[b, k] + bcls[k],
- * :248-250), Y_prob [B, K] = softmax over the K logits, Y_hat int64 [B] = their first maximum.  attention_only != 0: A_raw alone.
- * hipt_clam_mb_bags_supported(w) != 0: hipt_clam_bags_supported(w) and 2 <= n_att <= 4 and n_att == n_classes; otherwise
- * HIPT_E_UNSUPPORTED and hipt_clam_mb_bags_workspace_bytes = 0.  HIPT_E_BADARG, before anything is launched, for a null pointer, a
- * misaligned `bags`, B < 1, total_rows < B and a workspace smaller than hipt_clam_mb_bags_workspace_bytes(w, B, total_rows) or not
- * 256-byte aligned. */
+ * :248-250), Y_prob [B, K] = softmax over the K logits, Y_hat int64 [B] = their first maximum. */
 int hipt_clam_mb_bags_supported(const hipt_clam_weights* w);
 size_t hipt_clam_mb_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
 int hipt_clam_mb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,

@@ -187,3 +187,22 @@ def test_validate_split_still_restores_bags_one_call():
     m = CLAM_MB(size_arg="hipt_smaller", k_sample=2).eval()
     validate_split(m, [torch.randn(4, 192), torch.randn(3, 192)], [0, 1], 2)
     assert "bags_one_call" not in m.__dict__ and "bags_narrow" not in m.__dict__
+
+
+@pytest.mark.parametrize("preset", [None, True, False])
+def test_validate_split_restores_bags_one_call_after_an_exception(preset):
+    torch.manual_seed(0)
+    m = CLAM_MB(size_arg="hipt_smaller", k_sample=2).eval()
+    if preset is not None:
+        m.bags_one_call = preset
+    seen = []
+
+    def boom(*a, **kw):
+        seen.append((m.bags_one_call, m.bags_narrow))
+        raise KeyError("inside forward_bags")
+
+    m.forward_bags = boom
+    with pytest.raises(KeyError):
+        validate_split(m, [torch.randn(4, 192), torch.randn(3, 192)], [0, 1], 2, mb_one_call=False, narrow_one_call=True)
+    assert seen == [(False, True)]
+    assert m.__dict__.get("bags_one_call", None) is preset and "bags_narrow" not in m.__dict__

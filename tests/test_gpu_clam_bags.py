@@ -5,25 +5,21 @@ rows between larger ones, a bag that ends one row short of a 128-row tile, one t
 past it, so that bag boundaries fall before, on and after the boundaries a tiling of the concatenated rows would have.  ``B = 1``
 runs with 129 rows (a full tile and a one-row tile)."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
+import clam_bags_util as U
+from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
 from conftest import golden
 from hipt_abmil_atec23_amd import CLAM_MB, CLAM_SB, _native as N
 from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd import synth
 from hipt_abmil_atec23_amd.evaluate import evaluate_split
-from oracle import hipt_oracle as O
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ROWS = [1, 127, 128, 129, 300, 2, 1000]
-TOL = 1e-4           # the project's fp32 bar (tests/test_gpu_parity.py)
-OUTS = ("A_raw", "M", "logits", "Y_prob")
-FENCE, FILL = 4096, 0xA5
 
 # bf16: worst |error| per output of the PER-BAG path (CLAM_SB.forward -> hipt_clam_sb_forward, whose code this change does not touch)
 # against the fp64 oracle on the bf16-rounded bag and bf16-rounded W1 / Wa / Wb, over the seven bags of ROWS (seed 21) -- measured
@@ -41,48 +37,15 @@ BF16_PER_BAG = {
 BF16_SEED = 21
 
 
-def md(a, b):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return float(np.abs(a.astype(np.float64).reshape(-1) - np.asarray(b, dtype=np.float64).reshape(-1)).max())
+make = U.make
 
 
-def bits(t):
-    return t.detach().cpu().numpy().tobytes()
-
-
-@functools.lru_cache(maxsize=None)
-def make(size, dtype="fp32", cls=CLAM_SB, n_classes=2):
-    m = cls(size_arg=list(size), n_classes=n_classes)
-    m.load_state_dict(synth.make_state_dict(synth.clam_param_specs(size, n_classes=n_classes, multi=cls is CLAM_MB), size[0]), strict=True)
-    m.relocate()
-    return m.eval().set_compute_dtype(dtype)
-
-
-def params64(size, rounded=False):
-    p = synth.make_params_np(synth.clam_param_specs(size), size[0])
-    out = {}
-    for k, v in p.items():
-        if rounded and k.endswith("weight") and ("attention_net.0." in k or "attention_a" in k or "attention_b" in k):
-            v = torch.from_numpy(np.ascontiguousarray(v)).bfloat16().float().numpy()   # what the kernels read in bf16 mode
-        out[k] = v.astype(np.float64)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
 def bags_of(s0, seed, rows=tuple(ROWS)):
-    cat = synth.hash_uniform_torch((sum(rows), s0), seed, device=DEV)
-    return tuple(cat.split(list(rows), dim=0))
+    return U.bags_of(s0, seed, rows)
 
 
-@functools.lru_cache(maxsize=None)
 def reference(size, seed, rounded=False, rows=tuple(ROWS)):
-    """The oracle on every bag ALONE (fp64 where ``rounded``: on the bf16-rounded bag and weights)."""
-    p = params64(size, rounded) if rounded else synth.make_params_np(synth.clam_param_specs(size), size[0])
-    refs = []
-    for b in bags_of(size[0], seed, rows):
-        h = (b.bfloat16().double() if rounded else b).cpu().numpy()
-        refs.append(O.clam_sb_forward(h, p))
-    return refs
+    return U.reference(size, seed, rows, rounded)
 
 
 def run_bags(m, bags):
@@ -90,25 +53,6 @@ def run_bags(m, bags):
     assert m.bags_route == "bags"
     torch.cuda.synchronize()
     return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
-
-
-def per_bag(out, b):
-    return {"A_raw": out["A_raw"][b], "M": out["M"][b:b + 1], "logits": out["logits"][b:b + 1], "Y_prob": out["Y_prob"][b:b + 1],
-            "Y_hat": out["Y_hat"][b:b + 1]}
-
-
-def errors(out, refs):
-    """worst |error| per output over the bags, and the bags whose Y_hat differs"""
-    worst = {k: 0.0 for k in OUTS}
-    wrong = []
-    for b, r in enumerate(refs):
-        got = per_bag(out, b)
-        for k in OUTS:
-            assert got[k].shape == r[k].shape, (k, got[k].shape, r[k].shape)
-            worst[k] = max(worst[k], md(got[k], r[k]))
-        if int(got["Y_hat"].reshape(-1)[0]) != int(np.asarray(r["Y_hat"]).reshape(-1)[0]):
-            wrong.append(b)
-    return worst, wrong
 
 
 # ---------------------------------------------------------------- 1. fp32 parity
@@ -160,11 +104,6 @@ def test_fp32_golden_bags_among_others(size, names):
 
 
 # ---------------------------------------------------------------- 2. bitwise batch invariance
-def assert_same_bits(a, b, what):
-    for k in (*OUTS, "Y_hat"):
-        assert a[k].shape == b[k].shape and bits(a[k]) == bits(b[k]), f"{what}: {k} differs"
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_a_bag_does_not_see_its_neighbours(dtype, monkeypatch):
     size = (384, 128, 64)

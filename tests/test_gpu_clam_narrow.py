@@ -5,26 +5,22 @@ Weights and bags are made as in tests/test_gpu_clam_bags.py.  The row counts of 
 bags of one and two rows, bags one row short of and one row past a 32-row wave block, bags that end before, on and after a 128-row
 tile, and a bag of 1 100 rows = 9 tiles, so that the combine's ``t + 8`` stride has a second term."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
+import clam_bags_util as U
+from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
 from conftest import golden
 from hipt_abmil_atec23_amd import CLAM_SB, _native as N
 from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd import synth
 from hipt_abmil_atec23_amd.evaluate import evaluate_split, validate_split
-from oracle import hipt_oracle as O
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ROWS = (1, 2, 31, 33, 127, 128, 129, 300, 1100)
 ROWS_I = (8, 31, 33, 127, 128, 129, 300, 1100)      # the instance branch needs k_sample = 8 rows per bag
-TOL = 1e-4           # the project's fp32 bar (tests/test_gpu_parity.py)
-OUTS = ("A_raw", "M", "logits", "Y_prob")
-FENCE, FILL = 4096, 0xA5
 SHAPES = [(192, 16, 8), (192, 8, 4), (512, 32, 8), (1024, 32, 8)]
 SHAPES_BF16 = SHAPES + [(192, 32, 16)]
 # bf16: the seed of the bags, chosen on the host from the fp64 reference (bf16-rounded bag, W1, Wa, Wb) alone: of seeds 21..28 the
@@ -32,48 +28,16 @@ SHAPES_BF16 = SHAPES + [(192, 32, 16)]
 BF16_SEED = 26
 
 
-def md(a, b):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return float(np.abs(a.astype(np.float64).reshape(-1) - np.asarray(b, dtype=np.float64).reshape(-1)).max())
-
-
-def bits(t):
-    return t.detach().cpu().numpy().tobytes()
-
-
-@functools.lru_cache(maxsize=None)
 def make(size, dtype="fp32", subtyping=False):
-    m = CLAM_SB(size_arg=list(size), n_classes=2, subtyping=subtyping)
-    m.load_state_dict(synth.make_state_dict(synth.clam_param_specs(size), size[0]), strict=True)
-    m.relocate()
-    return m.eval().set_compute_dtype(dtype)
+    return U.make(size, dtype, CLAM_SB, 2, subtyping)
 
 
-def params64(size, rounded=False):
-    p = synth.make_params_np(synth.clam_param_specs(size), size[0])
-    out = {}
-    for k, v in p.items():
-        if rounded and k.endswith("weight") and ("attention_net.0." in k or "attention_a" in k or "attention_b" in k):
-            v = torch.from_numpy(np.ascontiguousarray(v)).bfloat16().float().numpy()   # what the kernels read in bf16 mode
-        out[k] = v.astype(np.float64)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
 def bags_of(s0, seed, rows=ROWS):
-    cat = synth.hash_uniform_torch((sum(rows), s0), seed, device=DEV)
-    return tuple(cat.split(list(rows), dim=0))
+    return U.bags_of(s0, seed, rows)
 
 
-@functools.lru_cache(maxsize=None)
 def reference(size, seed, rounded=False, rows=ROWS):
-    """The oracle on every bag ALONE (fp64 where ``rounded``: on the bf16-rounded bag and weights)."""
-    p = params64(size, rounded) if rounded else synth.make_params_np(synth.clam_param_specs(size), size[0])
-    refs = []
-    for b in bags_of(size[0], seed, rows):
-        h = (b.bfloat16().double() if rounded else b).cpu().numpy()
-        refs.append(O.clam_sb_forward(h, p))
-    return refs
+    return U.reference(size, seed, rows, rounded)
 
 
 def run_narrow(m, bags, **kw):
@@ -94,25 +58,6 @@ def run_loop(m, bags):
     torch.cuda.synchronize()
     return {"A_raw": [o[3] for o in outs], "M": torch.cat([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
             "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
-
-
-def per_bag(out, b):
-    return {"A_raw": out["A_raw"][b], "M": out["M"][b:b + 1], "logits": out["logits"][b:b + 1], "Y_prob": out["Y_prob"][b:b + 1],
-            "Y_hat": out["Y_hat"][b:b + 1]}
-
-
-def errors(out, refs):
-    """worst |error| per output over the bags, and the bags whose Y_hat differs"""
-    worst = {k: 0.0 for k in OUTS}
-    wrong = []
-    for b, r in enumerate(refs):
-        got = per_bag(out, b)
-        for k in OUTS:
-            assert got[k].shape == r[k].shape, (k, got[k].shape, r[k].shape)
-            worst[k] = max(worst[k], md(got[k], r[k]))
-        if int(got["Y_hat"].reshape(-1)[0]) != int(np.asarray(r["Y_hat"]).reshape(-1)[0]):
-            wrong.append(b)
-    return worst, wrong
 
 
 def direct(w, bags, rows, narrow=True, **kw):
@@ -187,11 +132,6 @@ def test_bf16_parity_per_bag(size):
 
 
 # ---------------------------------------------------------------- 4. bitwise independence
-def assert_same_bits(a, b, what):
-    for k in (*OUTS, "Y_hat"):
-        assert a[k].shape == b[k].shape and bits(a[k]) == bits(b[k]), f"{what}: {k} differs"
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("size", [(192, 16, 8), (192, 8, 4), (1024, 32, 8)])
 def test_a_bag_does_not_see_its_neighbours(size, dtype, monkeypatch):

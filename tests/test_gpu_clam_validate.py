@@ -24,7 +24,9 @@ import numpy as np
 import pytest
 import torch
 
+import clam_bags_util as U
 import clam_mb_ref as R
+from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, md
 from hipt_abmil_atec23_amd import CLAM_MB, CLAM_SB, _native as N
 from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd import synth
@@ -33,13 +35,9 @@ from oracle import hipt_oracle as O
 from test_clam_validate_host import per_slide_loop
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ROWS = (1, 127, 128, 129, 300, 2, 1100)
 ROWS_I = (8, 9, 127, 128, 129, 300)
 SIZES = [(384, 128, 64), (192, 64, 32)]
-TOL = 1e-4           # the project's fp32 bar
-OUTS = ("A_raw", "M", "logits", "Y_prob")
-FENCE, FILL = 4096, 0xA5
 BF16_SEED = 21
 BF16_PER_BAG = {
     (384, 128, 64): {"A_raw": 9.172e-3, "M": 3.488e-3, "logits": 4.959e-4, "Y_prob": 1.059e-4},
@@ -49,45 +47,24 @@ INST_SEED = {CLAM_SB: 50, CLAM_MB: 50}   # seeds whose reference top-k gaps exce
 GAP = 1e-3           # ten times the A_raw bar
 
 
-def md(a, b):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return float(np.abs(a.astype(np.float64).reshape(-1) - np.asarray(b, dtype=np.float64).reshape(-1)).max())
-
-
-def bits(t):
-    return t.detach().contiguous().cpu().numpy().tobytes()
-
-
-@functools.lru_cache(maxsize=None)
 def make(size, dtype="fp32", cls=CLAM_MB, n_classes=2, subtyping=False):
-    m = cls(size_arg=list(size), n_classes=n_classes, subtyping=subtyping)
-    m.load_state_dict(synth.make_state_dict(synth.clam_param_specs(size, n_classes=n_classes, multi=cls is CLAM_MB), size[0]), strict=True)
-    m.relocate()
-    m.bags_one_call = True   # (an instance attribute; CLAM_SB ignores it)
-    return m.eval().set_compute_dtype(dtype)
+    return U.make(size, dtype, cls, n_classes, subtyping, True)   # bags_one_call set
 
 
-@functools.lru_cache(maxsize=None)
 def params64(size, n_classes=2, multi=True, rounded=False):
-    out = {}
-    for k, v in synth.make_params_np(synth.clam_param_specs(size, n_classes=n_classes, multi=multi), size[0]).items():
-        if rounded and k.endswith("weight") and ("attention_net.0." in k or "attention_a" in k or "attention_b" in k):
-            v = torch.from_numpy(np.ascontiguousarray(v)).bfloat16().float().numpy()   # what the kernels read in bf16 mode
-        out[k] = v.astype(np.float64)
-    return out
+    return U.params64(size, n_classes, multi, rounded)
 
 
-@functools.lru_cache(maxsize=None)
 def bags_of(s0, seed, rows=ROWS):
-    cat = synth.hash_uniform_torch((sum(rows), s0), seed, device=DEV)
-    return tuple(cat.split(list(rows), dim=0))
+    return U.bags_of(s0, seed, rows)
 
 
-@functools.lru_cache(maxsize=None)
 def reference(size, seed, n_classes=2, rounded=False, rows=ROWS):
-    """The fp64 restatement on every bag ALONE (``rounded``: on the bf16-rounded bag and weights)."""
-    p = params64(size, n_classes, True, rounded)
-    return [R.clam_mb_forward((b.bfloat16() if rounded else b).double().cpu().numpy(), p) for b in bags_of(size[0], seed, rows)]
+    return U.reference(size, seed, rows, rounded, n_classes, True)
+
+
+per_bag = functools.partial(U.per_bag, multi=True)
+errors = functools.partial(U.errors, multi=True)
 
 
 def run_bags(m, bags, **kw):
@@ -107,28 +84,6 @@ def run_per_bag(m, bags):
     torch.cuda.synchronize()
     return {"A_raw": [o[3] for o in outs], "M": torch.stack([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
             "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
-
-
-def per_bag(out, b):
-    return {"A_raw": out["A_raw"][b], "M": out["M"][b], "logits": out["logits"][b:b + 1], "Y_prob": out["Y_prob"][b:b + 1],
-            "Y_hat": out["Y_hat"][b:b + 1]}
-
-
-def errors(out, refs):
-    worst, wrong = {k: 0.0 for k in OUTS}, []
-    for b, r in enumerate(refs):
-        got = per_bag(out, b)
-        for k in OUTS:
-            assert tuple(got[k].shape) == r[k].shape, (k, got[k].shape, r[k].shape)
-            worst[k] = max(worst[k], md(got[k], r[k]))
-        if int(got["Y_hat"].reshape(-1)[0]) != int(r["Y_hat"].reshape(-1)[0]):
-            wrong.append(b)
-    return worst, wrong
-
-
-def assert_same_bits(a, b, what):
-    for k in (*OUTS, "Y_hat"):
-        assert a[k].shape == b[k].shape and bits(a[k]) == bits(b[k]), f"{what}: {k} differs"
 
 
 # ---------------------------------------------------------------- 1. fp32 parity
