@@ -41,6 +41,11 @@ _LAZY = {
     "score_counts": ("heatmap", "score_counts"), "to_percentiles": ("heatmap", "to_percentiles"),
     "score2percentile": ("heatmap", "score2percentile"), "sample_rois": ("heatmap", "sample_rois"),
     "compute_from_batches": ("heatmap", "compute_from_batches"),
+    # hierarchical region attention heat-maps (create_hierarchical_heatmaps_indiv, HIPT_4K.get_region_attention_heatmaps)
+    "hierarchical_heatmaps": ("hier_heatmap", "hierarchical_heatmaps"), "compose_heatmaps": ("hier_heatmap", "compose_heatmaps"),
+    "region_attention_maps": ("hier_heatmap", "region_attention_maps"), "shifted_regions": ("hier_heatmap", "shifted_regions"),
+    "colour_table_n": ("hier_heatmap", "colour_table_n"), "cmap_map": ("hier_heatmap", "cmap_map"),
+    "create_hierarchical_heatmaps_indiv": ("hier_heatmap", "create_hierarchical_heatmaps_indiv"),
 }
 
 

@@ -85,6 +85,7 @@ BOOTSTRAP_DEGENERATE, BOOTSTRAP_BAD_INPUT = 1, 2
 HEATMAP_TILE_W, HEATMAP_TILE_H, HEATMAP_MAX_DIM, HEATMAP_LUT_ENTRIES = 32, 8, 1 << 20, 258
 PCT_RANKDATA, PCT_OF_SCORE = 0, 1
 PCT_REF_TILE, PCT_QUERIES_PER_WG = 512, 128   # HIPT_PCT_REF_TILE, HIPT_PCT_QUERIES_PER_WG
+HIER_MAX_L, HIER_MAX_UPSCALE, HIER_MAX_HEADS, HIER_MAX_LUT = 4096, 256, 8, 4096   # HIPT_HIER_MAX_*
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -180,6 +181,9 @@ SIGNATURES = {
     "hipt_heatmap_overlay": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "hipt_heatmap_render": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, C.c_double, _p, _p, _p, _sz, _p]),
     "hipt_score_counts": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p]),
+    "hipt_hier_ranks": (_i, [_p, _i, _i, _i, _p, _p]),
+    "hipt_hier_render": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, C.c_double, C.c_double, _p, _i, _i, C.c_double, _p, _p, _p, _p,
+                              _p]),
 }
 
 _lib = None

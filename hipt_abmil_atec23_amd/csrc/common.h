@@ -117,6 +117,16 @@ __device__ __forceinline__ void lds_st64(uint32_t a, u32x2 v) { asm volatile("ds
 
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// The heat-maps' blend with the slide (heatmap.hip, hier_heatmap.hip): sat_u8(rint(float32(img) * a + float32(canvas) * b)),
+// a = float32(alpha), b = float32(1 - alpha) -- cv2.addWeighted's formula.  Both files are built with -ffp-contract=off: the two
+// products and their sum are rounded one by one.
+__device__ __forceinline__ uint8_t blend_u8(uint8_t img, uint8_t canvas, float a, float b) {
+    const float p = (float)img * a;
+    const float q = (float)canvas * b;
+    const float s = rintf(p + q);   // half to even
+    return (uint8_t)fminf(fmaxf(s, 0.0f), 255.0f);
+}
+
 // XCD-aware bijective remap of a linear block id: blocks b and b+8 share an XCD (and its L2),
 // so give each XCD a contiguous range of logical tiles (cdna guide T1, bijective form).
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

@@ -205,13 +205,6 @@ struct HmPixelArgs {
     uint8_t* painted;
 };
 
-__device__ __forceinline__ uint8_t hm_blend(uint8_t img, uint8_t canvas, float a, float b) {
-    const float p = (float)img * a;
-    const float q = (float)canvas * b;
-    const float s = rintf(p + q);   // half to even
-    return (uint8_t)fminf(fmaxf(s, 0.0f), 255.0f);
-}
-
 // step 5
 __global__ __launch_bounds__(HM_THREADS) void hm_pixel_kernel(const HmPixelArgs A) {
     __shared__ int4 rect[HM_CHUNK];
@@ -292,7 +285,7 @@ __global__ __launch_bounds__(HM_THREADS) void hm_pixel_kernel(const HmPixelArgs 
         }
         if (A.blend) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) out[ch] = hm_blend(out[ch], base[ch], A.a, A.b);
+            for (int ch = 0; ch < 3; ++ch) out[ch] = blend_u8(out[ch], base[ch], A.a, A.b);
         }
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) stage[row][col * 3 + ch] = out[ch];

@@ -16,8 +16,9 @@ The reference imports the hot-path classes by module path:
   reference's ``wsi_core`` imports (it needs openslide and cv2); elsewhere it does nothing.  ``install(resnet18=True)`` binds
   ``models.resnet_custom.resnet18_baseline`` to this package's HistoResNet-18 (``resnet18.resnet18_baseline``).
   ``install(heatmap_scores=True)`` binds ``wsi_core.wsi_utils.to_percentiles`` and ``sample_rois`` to ``heatmap``'s where the
-  reference's module imports (it needs h5py and cv2); elsewhere it does nothing.  The alternative is the overlay files under
-  ``shims/``.
+  reference's module imports (it needs h5py and cv2); elsewhere it does nothing.  ``install(hier_heatmaps=True)`` binds
+  ``HIPT_4K.hipt_heatmap_utils.create_hierarchical_heatmaps_indiv`` to ``hier_heatmap``'s where the reference's module imports
+  (it needs cv2, h5py and webdataset); elsewhere it does nothing.  The alternative is the overlay files under ``shims/``.
 """
 from __future__ import annotations
 
@@ -176,6 +177,42 @@ def _uninstall_heatmap_scores():
             setattr(mod, n, fn)
 
 
+_HIER_MOD, _HIER_NAME = "HIPT_4K.hipt_heatmap_utils", "create_hierarchical_heatmaps_indiv"
+
+
+def _install_hier_heatmaps(verbose: bool) -> bool:
+    """Bind ``hier_heatmap.create_hierarchical_heatmaps_indiv_like`` (the reference's signature) as
+    ``HIPT_4K.hipt_heatmap_utils.create_hierarchical_heatmaps_indiv`` (opt-in).  False, and nothing done, where the reference's
+    module does not import: the patch-level and concatenated pictures of that module are not this package's."""
+    from . import hier_heatmap
+    if _HIER_MOD in _saved:
+        return True
+    try:
+        if _HIER_MOD not in sys.modules and importlib.util.find_spec(_HIER_MOD) is None:
+            return False
+        mod = importlib.import_module(_HIER_MOD)
+    except Exception:   # no reference checkout on sys.path, or cv2 / h5py / webdataset missing
+        return False
+    _saved[_HIER_MOD] = mod.__dict__.get(_HIER_NAME)
+    setattr(mod, _HIER_NAME, hier_heatmap.create_hierarchical_heatmaps_indiv_like)
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_HIER_MOD}.{_HIER_NAME} -> {hier_heatmap.__name__}")
+    return True
+
+
+def _uninstall_hier_heatmaps():
+    if _HIER_MOD not in _saved:
+        return
+    prev = _saved.pop(_HIER_MOD)
+    mod = sys.modules.get(_HIER_MOD)
+    if mod is None:
+        return
+    if prev is None:
+        delattr(mod, _HIER_NAME)
+    else:
+        setattr(mod, _HIER_NAME, prev)
+
+
 _EVAL_MOD = "utils.eval_utils"
 
 
@@ -297,7 +334,7 @@ def _uninstall_resnet18():
 
 
 def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False,
-            evaluation: bool = False, validation: bool = False, heatmap_scores: bool = False):
+            evaluation: bool = False, validation: bool = False, heatmap_scores: bool = False, hier_heatmaps: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
     ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
@@ -307,8 +344,12 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False,
     ``evaluation=True`` also binds ``utils.eval_utils.summary`` to ``evaluate.evaluate_split`` where that module imports (else a no-op).
     ``validation=True`` also binds ``utils.core_utils.validate_clam`` to ``evaluate.validate_split`` where that module imports (else a no-op).
     ``heatmap_scores=True`` also binds ``wsi_core.wsi_utils.to_percentiles`` / ``sample_rois`` to ``heatmap``'s where that module imports
-    (else a no-op)."""
+    (else a no-op).
+    ``hier_heatmaps=True`` also binds ``HIPT_4K.hipt_heatmap_utils.create_hierarchical_heatmaps_indiv`` to ``hier_heatmap``'s where
+    that module imports (else a no-op)."""
     done = {}
+    if hier_heatmaps and _install_hier_heatmaps(verbose):
+        done[f"{_HIER_MOD}.{_HIER_NAME}"] = f"{__name__.rsplit('.', 1)[0]}.hier_heatmap.create_hierarchical_heatmaps_indiv_like"
     if heatmap_scores and _install_heatmap_scores(verbose):
         for n in _WSI_UTILS_NAMES:
             done[f"{_WSI_UTILS_MOD}.{n}"] = f"{__name__.rsplit('.', 1)[0]}.heatmap.{n}"
@@ -363,6 +404,7 @@ def uninstall():
     _uninstall_sampling()
     _uninstall_heatmaps()
     _uninstall_heatmap_scores()
+    _uninstall_hier_heatmaps()
     for ref_name in _MAP:
         sys.modules.pop(ref_name, None)
     for ref_name in _RESNET_MAP:

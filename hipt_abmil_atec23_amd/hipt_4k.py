@@ -261,6 +261,33 @@ class HIPT_4K(torch.nn.Module):
                 b256 = torch.nn.functional.interpolate(b256, scale_factor=(1 / scale), mode="nearest")  # :159-160
         return tensorbatch2im(b256), np.asarray(a256), np.asarray(a4k)
 
+    def get_region_attention_heatmaps(self, x, offset=128, scale=4, alpha=0.5, cmap=None, threshold=None):
+        """hipt_4k.py:167-303: ``(hm4k, hm256, hm4k_256)``, lists of ``PIL.Image`` -- the ViT-4K heads, the ViT-256 heads and every
+        pair (j major) -- for the normalised region ``x [1, 3, W, H]``, with the method's defaults: the 256 level weighs 1 in the
+        blended score (:295-300) and ``cmap`` is ``cmap_map(lambda x: x / 2 + 0.5, jet)`` (``hier_heatmap.half_jet``, 1024 entries).
+        The pictures are made on the device (``hier_heatmap.hierarchical_heatmaps``).
+
+        Two departures from the reference's text.  It passes the UNSHIFTED region to all four ``_get_region_attention_scores``
+        calls (:195-198), which makes the four layers one map added to itself; here the shifted regions it builds just above are
+        the ones used, as in ``hipt_heatmap_utils.create_hierarchical_heatmaps_indiv``.  And it calls ``concat_scores256`` with
+        ``w_256, h_256`` (:208, :260), arguments its imported definition does not take, so the method cannot run as written; here
+        the patches are laid out as ``hipt_heatmap_utils`` does, generalised to a ``w_256 x h_256`` grid.  ``threshold`` would save
+        files under a directory the method never receives (:225): use ``hier_heatmap.create_hierarchical_heatmaps_indiv``."""
+        from PIL import Image
+
+        from . import hier_heatmap as HH
+        from .hipt_model_utils import tensorbatch2im
+        if threshold is not None:
+            raise NotImplementedError("get_region_attention_heatmaps: the thresholded pictures are files of "
+                                      "hier_heatmap.create_hierarchical_heatmaps_indiv (the method has no output directory)")
+        if x.dim() != 4 or x.shape[0] != 1:
+            raise ValueError("get_region_attention_heatmaps describes ONE region ([1, 3, W, H]), as in the reference (hipt_4k.py:185)")
+        region = tensorbatch2im(x)[0]   # :185
+        res = HH.hierarchical_heatmaps(self, region, offset=offset, scale=scale, alpha=alpha, cmap="half_jet" if cmap is None else cmap,
+                                       w256=1)
+        host = {k: v.cpu().numpy() for k, v in res.items()}
+        return tuple([Image.fromarray(img) for img in host[k]] for k in ("4k", "256", "blend"))
+
     def forward_asset_dict(self, x: torch.Tensor):
         """hipt_4k.py:79-118: intermediate features as numpy arrays."""
         if x.shape[0] != 1:

@@ -35,8 +35,8 @@ extern "C" {
  * hipt_vit_packed_bytes, never compute the size) and packing it reads blocks[i].proj_w, which must be set first;
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
- * _render), hipt_vit_cls_block_unit and hipt_score_counts were added later under the same number: additive, nothing existing
- * changed. */
+ * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) were
+ * added later under the same number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -755,6 +755,49 @@ enum { HIPT_PCT_RANKDATA = 0, HIPT_PCT_OF_SCORE = 1 };
 #define HIPT_PCT_QUERIES_PER_WG 128
 int hipt_score_counts(const double* q, int64_t nq, const double* ref, int64_t nref, int mode, int32_t* less, int32_t* leq,
                       double* pct, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Hierarchical region attention heat-maps (HIPT_4K/hipt_heatmap_utils.py:347-485, HIPT_4K/hipt_4k.py:167-303).
+ *
+ * hipt_hier_ranks: x float32 [V, L] (device), pct float64 [V, L].  The reference upscales a map by f (nearest neighbour: every
+ * value f * f times) and takes scipy.stats.rankdata(u) * 100 / len(u) of the upscaled values u.  With less = #{k : x[v,k] < x[v,i]}
+ * and eq = #{k : x[v,k] == x[v,i]} (float32 comparisons, x[v,i] counts itself, -0.0 == +0.0) that is, at every copy of x[v,i],
+ *   pct[v,i] = (less * f^2 + 0.5 * (eq * f^2 + 1)) * 100 / (L * f^2)
+ * in float64 with the operations in that order: bit for bit scipy's value.  One workgroup per vector, the vector in LDS, brute
+ * force: no sort, no atomic, no workspace.  Envelope 1 <= L <= HIPT_HIER_MAX_L, 1 <= f <= HIPT_HIER_MAX_UPSCALE, else
+ * HIPT_E_UNSUPPORTED with nothing launched; V = 0 returns HIPT_OK.  NaN in x is a caller error.
+ *
+ * hipt_hier_render: every picture of one region in one pass over its pixels.
+ *   pct4k  float64 [4, nh, w_256 * h_256]      the ranks (f = 256 / scale) of the ViT-4K maps of the region and its three shifted copies
+ *   pct256 float64 [2, nh, w_256 * h_256, 256] the ranks (f = 16 / scale) of the ViT-256 maps of the region and its first shifted copy
+ *   scale in {1, 2, 4, 8, 16}: b = 256 / scale pixels per patch, t = 16 / scale per token; the pictures are Hs = w_256 * b rows of
+ *   Ws = h_256 * b pixels (the reference's naming: tensor dimension 2 is "w").  Layer l (offsets 0, off2, off3, off4, output pixels)
+ *   is present at (y, x) iff y >= off_l and x >= off_l; its value is the percentile of token ((y - off_l) % b) / t, ((x - off_l) % b) / t
+ *   (row major in 16) of patch ((y - off_l) / b) * h_256 + (x - off_l) / b; for the 4K level the patch is the token.  In float64,
+ *   every operation rounded on its own:
+ *     overlay4k = 100 * present layers;  score4k  = (v1 + v2 + v3 + v4) / overlay4k     (present layers, left to right)
+ *     ov        = 100 * present of the first two;  score256 = (u1 + u2) / ov
+ *     overlay256 = w256 * ov;  score = (score4k * overlay4k + score256 * overlay256) / (overlay4k + overlay256)
+ *   colour = lut[min(trunc(score * lut_n), lut_n - 1)] (matplotlib's look-up in [0, 1]); pixel = the blend of hipt_heatmap_render,
+ *   sat_u8(rint(float32(colour) * float32(alpha) + float32(base) * float32(1 - alpha))).
+ *   hm4k [nh, Hs, Ws, 3] shows score4k of head j; hm256 [nh, Hs, Ws, 3] score256 of head i; hm_blend [npairs, Hs, Ws, 3] the blended
+ *   score of the pairs (j, i) = pairs[k] (a HOST array int32 [npairs, 2], read before the call returns, each pair at most once;
+ *   NULL: all nh * nh pairs, j major, and npairs is ignored); hm256_thr [nh, Hs, Ws, 3] (needs use_threshold): base where
+ *   score256 < threshold, the blend of entry trunc(0.95 * lut_n) where it is above, and the uint8 wrapping sum of base and the blend
+ *   of the threshold's own entry where it is equal (a threshold of exactly 0.95 counts as above).  Each output may be NULL, not all.
+ * base uint8 [Hs, Ws, 3], lut uint8 [lut_n, 3]; base and the pictures 4-byte aligned, base none of the pictures.
+ * Envelope: 1 <= nh <= HIPT_HIER_MAX_HEADS, 1 <= w_256 * h_256 <= HIPT_HIER_MAX_L, 2 <= lut_n <= HIPT_HIER_MAX_LUT, scale as
+ * above, else HIPT_E_UNSUPPORTED with nothing launched.  One launch on `stream`, no workspace, no atomics, no host read-back.
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_HIER_MAX_L 4096
+#define HIPT_HIER_MAX_UPSCALE 256
+#define HIPT_HIER_MAX_HEADS 8
+#define HIPT_HIER_MAX_LUT 4096
+int hipt_hier_ranks(const float* x, int V, int L, int f, double* pct, void* stream);
+int hipt_hier_render(const double* pct4k, const double* pct256, int nh, int w_256, int h_256, int scale, int off2, int off3, int off4,
+                     const uint8_t* base, const uint8_t* lut, int lut_n, double alpha, double w256, const int32_t* pairs, int npairs,
+                     int use_threshold, double threshold, uint8_t* hm4k, uint8_t* hm256, uint8_t* hm_blend, uint8_t* hm256_thr,
+                     void* stream);
 
 #ifdef __cplusplus
 }
