@@ -46,6 +46,10 @@ _LAZY = {
     "region_attention_maps": ("hier_heatmap", "region_attention_maps"), "shifted_regions": ("hier_heatmap", "shifted_regions"),
     "colour_table_n": ("hier_heatmap", "colour_table_n"), "cmap_map": ("hier_heatmap", "cmap_map"),
     "create_hierarchical_heatmaps_indiv": ("hier_heatmap", "create_hierarchical_heatmaps_indiv"),
+    # patch coordinates from tissue contours (WholeSlideImage.process_contour, the contour checking functions)
+    "point_polygon_test": ("tiling", "point_polygon_test"), "process_contour": ("tiling", "process_contour"),
+    "process_contours": ("tiling", "process_contours"), "process_contours_like": ("tiling", "process_contours_like"),
+    "pack_slide": ("tiling", "pack_slide"), "plan_contours": ("tiling", "plan_contours"),
 }
 
 

@@ -18,7 +18,9 @@ The reference imports the hot-path classes by module path:
   ``install(heatmap_scores=True)`` binds ``wsi_core.wsi_utils.to_percentiles`` and ``sample_rois`` to ``heatmap``'s where the
   reference's module imports (it needs h5py and cv2); elsewhere it does nothing.  ``install(hier_heatmaps=True)`` binds
   ``HIPT_4K.hipt_heatmap_utils.create_hierarchical_heatmaps_indiv`` to ``hier_heatmap``'s where the reference's module imports
-  (it needs cv2, h5py and webdataset); elsewhere it does nothing.  The alternative is the overlay files under ``shims/``.
+  (it needs cv2, h5py and webdataset); elsewhere it does nothing.  ``install(tiling=True)`` binds ``tiling.process_contour_like`` as
+  ``wsi_core.WholeSlideImage.WholeSlideImage.process_contour`` (what ``process_contours`` and ``Wsi_Region`` call per contour) where
+  the reference's ``wsi_core`` imports; elsewhere it does nothing.  The alternative is the overlay files under ``shims/``.
 """
 from __future__ import annotations
 
@@ -137,6 +139,41 @@ def _uninstall_heatmaps():
         del cls.visHeatmap
     else:
         cls.visHeatmap = prev
+
+
+_TILING_KEY = _WSI_MOD + ".process_contour"
+
+
+def _install_tiling(verbose: bool) -> bool:
+    """Bind ``tiling.process_contour_like`` as the reference class's ``process_contour`` (opt-in).  False, and nothing done, where
+    the reference's ``wsi_core.WholeSlideImage`` does not import."""
+    from . import tiling
+    if _TILING_KEY in _saved:
+        return True
+    try:
+        if _WSI_MOD not in sys.modules and importlib.util.find_spec(_WSI_MOD) is None:
+            return False
+        cls = importlib.import_module(_WSI_MOD).WholeSlideImage
+    except Exception:   # no reference checkout on sys.path, or openslide / cv2 missing
+        return False
+    _saved[_TILING_KEY] = cls.__dict__.get("process_contour")
+    cls.process_contour = tiling.process_contour_like
+    if verbose:
+        print(f"[hipt_abmil_atec23_amd] {_WSI_MOD}.WholeSlideImage.process_contour -> {tiling.__name__}.process_contour_like")
+    return True
+
+
+def _uninstall_tiling():
+    if _TILING_KEY not in _saved:
+        return
+    prev = _saved.pop(_TILING_KEY)
+    mod = sys.modules.get(_WSI_MOD)
+    if mod is None:
+        return
+    if prev is None:
+        del mod.WholeSlideImage.process_contour
+    else:
+        mod.WholeSlideImage.process_contour = prev
 
 
 _WSI_UTILS_MOD = "wsi_core.wsi_utils"
@@ -334,7 +371,8 @@ def _uninstall_resnet18():
 
 
 def install(verbose: bool = False, resnet: bool = False, sampling: bool = False, heatmaps: bool = False, resnet18: bool = False,
-            evaluation: bool = False, validation: bool = False, heatmap_scores: bool = False, hier_heatmaps: bool = False):
+            evaluation: bool = False, validation: bool = False, heatmap_scores: bool = False, hier_heatmaps: bool = False,
+            tiling: bool = False):
     """Register the HIP-backed modules under the reference's import paths. Returns the mapping.  ``resnet=True`` also maps
     ``models.resnet_custom`` (ResNet_Baseline / resnet50_baseline); without it the reference's resnet_custom is left alone.
     ``sampling=True`` also binds ``utils.sampling_utils.generate_sample_idxs`` / ``update_sampling_weights`` (eval.py --sampling).
@@ -346,8 +384,12 @@ def install(verbose: bool = False, resnet: bool = False, sampling: bool = False,
     ``heatmap_scores=True`` also binds ``wsi_core.wsi_utils.to_percentiles`` / ``sample_rois`` to ``heatmap``'s where that module imports
     (else a no-op).
     ``hier_heatmaps=True`` also binds ``HIPT_4K.hipt_heatmap_utils.create_hierarchical_heatmaps_indiv`` to ``hier_heatmap``'s where
-    that module imports (else a no-op)."""
+    that module imports (else a no-op).
+    ``tiling=True`` also binds ``WholeSlideImage.process_contour`` to ``tiling.process_contour_like`` where the reference's ``wsi_core``
+    imports (else a no-op)."""
     done = {}
+    if tiling and _install_tiling(verbose):
+        done[_WSI_MOD + ".WholeSlideImage.process_contour"] = f"{__name__.rsplit('.', 1)[0]}.tiling.process_contour_like"
     if hier_heatmaps and _install_hier_heatmaps(verbose):
         done[f"{_HIER_MOD}.{_HIER_NAME}"] = f"{__name__.rsplit('.', 1)[0]}.hier_heatmap.create_hierarchical_heatmaps_indiv_like"
     if heatmap_scores and _install_heatmap_scores(verbose):
@@ -405,6 +447,7 @@ def uninstall():
     _uninstall_heatmaps()
     _uninstall_heatmap_scores()
     _uninstall_hier_heatmaps()
+    _uninstall_tiling()
     for ref_name in _MAP:
         sys.modules.pop(ref_name, None)
     for ref_name in _RESNET_MAP:

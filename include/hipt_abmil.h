@@ -35,8 +35,9 @@ extern "C" {
  * hipt_vit_packed_bytes, never compute the size) and packing it reads blocks[i].proj_w, which must be set first;
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
- * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) were
- * added later under the same number: additive, nothing existing changed. */
+ * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) and the
+ * tiling pair (hipt_point_polygon_test, hipt_tile_contours) were added later under the same number: additive, nothing existing
+ * changed. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -798,6 +799,55 @@ int hipt_hier_render(const double* pct4k, const double* pct256, int nh, int w_25
                      const uint8_t* base, const uint8_t* lut, int lut_n, double alpha, double w256, const int32_t* pairs, int npairs,
                      int use_threshold, double threshold, uint8_t* hm4k, uint8_t* hm256, uint8_t* hm_blend, uint8_t* hm256_thr,
                      void* stream);
+
+/* ----------------------------------------------------------------------------------
+ * Patch coordinates from tissue contours (wsi_core/WholeSlideImage.py:357-372, 415-506; wsi_core/util_classes.py:53-111;
+ * DESIGN.md 21).  Integer geometry only: no floating point, no workspace, no atomics, no state between calls, one launch a call.
+ *
+ * Polygons are packed: verts int32 [V, 2] (x, y), poly_off int32 [P + 1] with polygon p = vertices poly_off[p] .. poly_off[p+1] - 1
+ * (closed: the edge last -> first is part of it).  Points travel DOUBLED (2 * coordinate), so a half integer is an integer here;
+ * the kernels double the vertices themselves.  Every doubled coordinate, vertex or point, must lie strictly inside
+ * +-HIPT_TILING_COORD_BOUND: every difference then fits int32 and the edge function is two 32 x 32 -> 64 bit products.  The arrays
+ * live on the device, so this bound is the CALLER's to keep (the Python layer refuses what breaks it); whatever the arrays hold,
+ * no access leaves verts[0, V), poly_off[0, P], the point / unit / contour arrays or the output.
+ *
+ * The test of a point p against a polygon (cv2.pointPolygonTest(poly, p, False)):
+ *    0   p lies on a closed edge segment;
+ *   +1   otherwise, an odd number of edges cross the ray from p towards +x, an edge (a, b) counting when exactly one of
+ *        a.y <= p.y, b.y <= p.y holds and its point at height p.y lies right of p;
+ *   -1   otherwise.  A polygon of no vertices is -1 everywhere; one of 1 or 2 vertices is 0 on it and -1 elsewhere.
+ *
+ * hipt_point_polygon_test: points2 int32 [Q, 2] doubled, poly_id int32 [Q] in [0, P), out int8 [Q].  A workgroup of 256 points walks
+ * every polygon one of its points names, the edges in chunks of HIPT_TILING_EDGE_CHUNK through LDS: points grouped by polygon
+ * cost one walk a workgroup.  A point whose poly_id is outside [0, P) gets -1.  Q = 0 returns HIPT_OK.
+ *
+ * hipt_tile_contours: the keep-flag of every candidate patch of every contour of a slide.
+ *   contours int32 [C, HIPT_TILING_CONTOUR_INTS]: poly_begin, poly_end (polygon poly_begin is the contour, the others up to
+ *            poly_end - 1 its holes), start_x, start_y, step_x, step_y, nx, ny, keep_off.  Candidate i of the contour, 0 <= i <
+ *            nx * ny, is the patch whose top-left corner is pt = (start_x + (i / ny) * step_x, start_y + (i % ny) * step_y), and
+ *            its flag is keep[keep_off + i];
+ *   units    int32 [U, 2]: (contour, first candidate) of a tile of HIPT_TILING_TILE consecutive candidates, one workgroup each;
+ *            the caller lists the tiles it wants flags for (all of them: ceil(nx * ny / HIPT_TILING_TILE) per contour);
+ *   mode, ref_patch_size (ps), shift: the points tested against the contour and the rule
+ *            HIPT_TILE_BASIC          pt                                               in when the test is >= 0
+ *            HIPT_TILE_CENTER         pt + ps / 2 (integer division)                    in when >= 0
+ *            HIPT_TILE_FOUR_PT        (pt + ps / 2) -+ shift in x and in y: four points  in when ANY is >= 0
+ *            HIPT_TILE_FOUR_PT_HARD   the same four points                             in when ALL are >= 0
+ *            (shift = 0: the single centre point in both four-point modes);
+ *   keep uint8 [keep_len]: 1 when the candidate is in and pt + ps / 2 (TRUE division: doubled, 2 * pt + ps) lies strictly inside
+ *            (test > 0) none of the holes, else 0.  keep[keep_off + i] is written for the candidates of the listed tiles alone.
+ * A contour whose polygon range is empty or whose nx, ny are not positive gets no flag written.  1 <= ps, 0 <= shift, both below
+ * HIPT_TILING_COORD_BOUND / 4, else HIPT_E_UNSUPPORTED with nothing launched; U = 0 returns HIPT_OK.
+ * ---------------------------------------------------------------------------------- */
+enum { HIPT_TILE_BASIC = 0, HIPT_TILE_CENTER = 1, HIPT_TILE_FOUR_PT = 2, HIPT_TILE_FOUR_PT_HARD = 3 };
+#define HIPT_TILING_COORD_BOUND 1073741824
+#define HIPT_TILING_EDGE_CHUNK 1024
+#define HIPT_TILING_TILE 256
+#define HIPT_TILING_CONTOUR_INTS 9
+int hipt_point_polygon_test(const int32_t* verts, int V, const int32_t* poly_off, int P, const int32_t* points2, const int32_t* poly_id,
+                            int Q, int8_t* out, void* stream);
+int hipt_tile_contours(const int32_t* verts, int V, const int32_t* poly_off, int P, const int32_t* contours, int C, const int32_t* units,
+                       int U, int mode, int ref_patch_size, int shift, uint8_t* keep, int64_t keep_len, void* stream);
 
 #ifdef __cplusplus
 }
