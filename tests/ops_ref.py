@@ -1,0 +1,523 @@
+"""CPU side (float64) of the per-launch tests of the three base operators -- hipt_layernorm (misc.hip: ln_kernel), hipt_linear
+(gemm.hip: gemm_small_kernel ring / guarded, gemm_kernel) and hipt_attention (attention.hip: attn_kernel, attention2.hip: the
+64-wide-head kernel) -- DESIGN.md 22.  For each operator: the exact reference on the operands as the kernel reads them (fp32 values,
+or values already rounded to bf16), a per-element bound derived from the kernel's arithmetic, a NumPy emulation of the right kernel
+(fp32 / bf16 rounding where the kernel rounds, its own summation order), wrong kernels written as references, the input families and
+the launch lists.  tests/test_ops_ref.py checks all of this without a GPU; tests/test_gpu_ops_units.py holds the kernels to it."""
+import numpy as np
+import torch
+
+from hipt_abmil_atec23_amd import synth
+
+U = 2.0 ** -23          # one fp32 ulp of a value in [1, 2): every fp32 operation is charged one, rounded or truncated
+BF = 2.0 ** -8          # half a bf16 ulp at the bottom of a binade (8 significand bits), relative
+TINY = 2.0 ** -133      # products below the fp32 normal range
+FLUSH = 2.0 ** -126     # v_exp_f32 does not return denormals
+GELU_LIP = 1.13         # max |gelu'| = 1.1289
+# erff of the device inside 0.5 h (1 + erff(h / sqrt 2)): |gelu_device(h) - gelu(h)| <= C_G 2^-23 max(|h|, |gelu(h)|).  Not derivable
+# here; measured once on the MI355X over the 2^16-point sweep of tests/test_gpu_ops_units.py and set to 2 x that.
+C_G_MEASURED = 0.917
+C_G = 2.0 * C_G_MEASURED
+C_P = 32.0              # exp2 (2), 1 / l (2), e * inv (1), the 4 u |t| term inside the normaliser (4 ln 288 = 23), rounded up
+LN_MAX_E = 32           # misc.hip
+SMALL_M, SMALL_RING = 1088, 6   # gemm.hip
+F32, BF16 = 0, 1        # include/hipt_abmil.h
+EPI_GELU, EPI_RESID, EPI_OUT_F32, EPI_RELU = 1, 2, 4, 16
+E_UNSUPPORTED = -4
+
+
+def bf16_round(x):
+    """round-to-nearest-even to bf16, returned as float32 (inf / NaN pass through)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
+    return np.where(np.isfinite(x), r, x)
+
+
+def rounded(y, out_bf16):
+    """what a kernel stores of a result computed exactly"""
+    return bf16_round(y).astype(np.float64) if out_bf16 else np.asarray(y, np.float32).astype(np.float64)
+
+
+def ratio(got, ref, bound):
+    """|got - ref| / bound per element; a non-finite result counts as infinitely wrong"""
+    d = np.abs(np.asarray(got, np.float64) - ref) / bound
+    return np.where(np.isfinite(d), d, np.inf)
+
+
+def erf64(x):
+    return torch.special.erf(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))).numpy()
+
+
+def gelu64(h):
+    return 0.5 * h * (1.0 + erf64(h / np.sqrt(2.0)))
+
+
+# =====================================================================================================================
+# LayerNorm
+# =====================================================================================================================
+def layernorm_ref(x, w, b, eps):
+    x = np.asarray(x, np.float64)
+    mean = x.mean(-1, keepdims=True)
+    var = ((x - mean) ** 2).mean(-1, keepdims=True)
+    return (x - mean) / np.sqrt(var + eps) * np.asarray(w, np.float64) + np.asarray(b, np.float64)
+
+
+def layernorm_kappa(x, eps):
+    x = np.asarray(x, np.float64)
+    return np.sqrt((x * x).mean(-1) / (x.var(-1) + eps))
+
+
+def layernorm_bound(x, w, b, eps, out_bf16):
+    """two-pass bound: with L = D / 64 + 7 roundings in a lane's chain plus the 64-lane tree plus the division,
+    t = L kappa u is the error of the mean in units of sqrt(var + eps);
+    |dy| <= |w| (t + |xhat| ((L / 2 + 9) u + t^2 / 2)) + u |y|  (+ 2^-8 |y| for a bf16 output)"""
+    x, w, b = (np.asarray(v, np.float64) for v in (x, w, b))
+    D = x.shape[-1]
+    L = D / 64 + 7
+    mean = x.mean(-1, keepdims=True)
+    sig = np.sqrt(((x - mean) ** 2).mean(-1, keepdims=True) + eps)
+    xh = (x - mean) / sig
+    y = xh * w + b
+    t = L * layernorm_kappa(x, eps)[..., None] * U
+    return np.abs(w) * (t + np.abs(xh) * ((L / 2 + 9) * U + 0.5 * t * t)) + (U + (BF if out_bf16 else 0.0)) * np.abs(y)
+
+
+def _wave_sum32(p):
+    """xor-shuffle tree over the 64 lanes (last axis), fp32"""
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        p = (p + p[..., lanes ^ o]).astype(np.float32)
+    return p[..., :1]
+
+
+def emulate_layernorm(x, w, b, eps, V, out_bf16):
+    """ln_kernel in NumPy fp32: lane l owns elements V l + 64 V i (+ 0 .. V - 1), sums them in that order, then the tree"""
+    x = np.asarray(x, np.float32)
+    rows, D = x.shape
+    v = x.reshape(rows, D // (64 * V), 64, V)
+    s = np.zeros((rows, 64), np.float32)
+    for i in range(v.shape[1]):
+        for e in range(V):
+            s = (s + v[:, i, :, e]).astype(np.float32)
+    mean = (_wave_sum32(s) / np.float32(D)).astype(np.float32)
+    q = np.zeros((rows, 64), np.float32)
+    for i in range(v.shape[1]):
+        for e in range(V):
+            c = (v[:, i, :, e] - mean).astype(np.float32)
+            q = (q + (c * c).astype(np.float32)).astype(np.float32)
+    var = (_wave_sum32(q) / np.float32(D)).astype(np.float32)
+    rstd = (np.float32(1.0) / np.sqrt((var + np.float32(eps)).astype(np.float32))).astype(np.float32)
+    o = ((((x - mean).astype(np.float32) * rstd).astype(np.float32) * np.asarray(w, np.float32)).astype(np.float32)
+         + np.asarray(b, np.float32)).astype(np.float32)
+    return rounded(o, out_bf16)
+
+
+LN_VARIANTS = ("no_eps", "one_pass", "div_dm1", "wb_pair_swap", "mean_over_stride")
+# the class of rows on which each variant must land >= 3 x beyond the bound (classes of ln_inputs; None: any row)
+LN_CATCHES = {"no_eps": "near_const", "one_pass": "offset", "div_dm1": None, "wb_pair_swap": None, "mean_over_stride": None}
+
+
+def layernorm_variant(name, x, w, b, eps, x_padded=None):
+    """a wrong ln_kernel; x_padded [rows, x_stride] is the buffer the rows sit in (mean_over_stride reads into the gap)"""
+    x, w, b = (np.asarray(v, np.float64) for v in (x, w, b))
+    D = x.shape[-1]
+    mean = x.mean(-1, keepdims=True)
+    var = ((x - mean) ** 2).mean(-1, keepdims=True)
+    if name == "no_eps":
+        return (x - mean) / np.sqrt(var) * w + b
+    if name == "one_pass":  # E[x^2] - mean^2 with fp32 running sums
+        x32 = x.astype(np.float32)
+        s, q = np.zeros(x.shape[0], np.float32), np.zeros(x.shape[0], np.float32)
+        for d in range(D):
+            s = (s + x32[:, d]).astype(np.float32)
+            q = (q + (x32[:, d] * x32[:, d]).astype(np.float32)).astype(np.float32)
+        m32 = (s / np.float32(D)).astype(np.float32)
+        v32 = ((q / np.float32(D)).astype(np.float32) - (m32 * m32).astype(np.float32)).astype(np.float32)
+        v32 = np.maximum(v32, np.float32(0))
+        return (x - m32[:, None].astype(np.float64)) / np.sqrt(v32[:, None].astype(np.float64) + eps) * w + b
+    if name == "div_dm1":
+        return (x - mean) / np.sqrt(var * D / (D - 1) + eps) * w + b
+    if name == "wb_pair_swap":
+        sw = np.arange(D) ^ 1
+        return (x - mean) / np.sqrt(var + eps) * w[sw] + b[sw]
+    if name == "mean_over_stride":
+        m = np.asarray(x_padded, np.float64).mean(-1, keepdims=True)
+        v = ((x - m) ** 2).mean(-1, keepdims=True)
+        return (x - m) / np.sqrt(v + eps) * w + b
+    raise KeyError(name)
+
+
+LN_CLASSES = ("ordinary", "offset", "near_const", "outlier_ch")
+
+
+def ln_inputs(rows, D, seed, eps=1e-6):
+    """x [rows, D] fp32, gains, biases and the class of every row (index into LN_CLASSES).  Row r has class (r + seed) % 4: ordinary
+    U(-2, 2); mean 100, std 0.5; 1 + 1.7e-3 u (variance ~ 1e-6 = eps); four channels at +-60 ... 100 -- the classes of
+    test_gpu_vit_units.inputs.  Gains 1 +- 0.1 with every ~50th channel one of synth.GAINS (0.05 ... 20); biases U(-1, 1), so that
+    some outputs are small against their two terms."""
+    x = synth.hash_uniform_np((rows, D), seed, 2.0)
+    cls = (np.arange(rows) + seed) % 4
+    r = np.nonzero(cls == 1)[0]
+    x[r] = synth.hash_uniform_np((len(r), D), seed + 1, 0.87, 100.0)
+    r = np.nonzero(cls == 2)[0]
+    x[r] = synth.hash_uniform_np((len(r), D), seed + 2, 1.7e-3, 1.0)
+    r = np.nonzero(cls == 3)[0]
+    ch = np.array([7, 29, 40, 61]) * (D // 64) if D > 64 else np.array([7, 29, 40, 61])
+    x[np.ix_(r, ch)] = np.array([60.0, -75.0, 90.0, -100.0], np.float32)
+    w = synth.hash_uniform_np((D,), seed + 3, 0.1, 1.0)
+    h = synth.hash_u32_np(D, seed + 4)
+    idx = np.nonzero(h % np.uint32(50) == 0)[0]
+    w[idx] = np.asarray(synth.GAINS, np.float32)[(h[idx] >> np.uint32(8)) % np.uint32(len(synth.GAINS))]
+    w[0], w[D - 1] = np.float32(0.05), np.float32(20.0)  # (both ends of the range in every width)
+    b = synth.hash_uniform_np((D,), seed + 5, 1.0)
+    return x, w, b, cls
+
+
+# (D, rows, x_stride - D as "c" contiguous | "3D" | "odd", x offset in floats, branch): ln_kernel<., V>; V = 2 needs D % 128 == 0,
+# even strides and 8-byte aligned pointers.  Every D and every row count of the issue; 4 rows fill one block, 5 and 257 need a second.
+LN_LAUNCHES = [
+    (64, 1, "c", 0, "V1"), (128, 3, "c", 0, "V2"), (192, 4, "c", 0, "V1"), (384, 5, "c", 0, "V2"), (64 * LN_MAX_E, 5, "c", 0, "V2"),
+    (384, 257, "c", 0, "V2"), (384, 257, "3D", 0, "V2"), (64 * LN_MAX_E, 1, "3D", 0, "V2"), (64, 257, "3D", 0, "V1"),
+    (128, 5, "odd", 0, "V1"), (384, 257, "odd", 0, "V1"), (64 * LN_MAX_E, 3, "odd", 0, "V1"), (192, 257, "odd", 0, "V1"),
+    (128, 4, "c", 1, "V1"), (384, 257, "c", 1, "V1"), (64 * LN_MAX_E, 4, "c", 1, "V1"),
+]
+
+
+def ln_stride(D, mode):
+    return {"c": D, "3D": 3 * D, "odd": D + 1}[mode]
+
+
+def ln_vector_width(D, x_stride, out_stride, x_off):
+    """the launcher's choice (misc.hip: hipt_layernorm_launch), for buffers that are themselves 8-byte aligned"""
+    return 2 if D % 128 == 0 and x_stride % 2 == 0 and out_stride % 2 == 0 and x_off % 2 == 0 else 1
+
+
+# =====================================================================================================================
+# Linear
+# =====================================================================================================================
+def _act64(h, epilogue):
+    return gelu64(h) if epilogue == "gelu" else (np.maximum(h, 0.0) if epilogue == "relu" else h)
+
+
+def linear_ref(a, w, bias, resid=None, epilogue="none"):
+    """act(a w^T + bias) + resid in float64; epilogue in {"none", "gelu", "relu"}"""
+    h = np.asarray(a, np.float64) @ np.asarray(w, np.float64).T + np.asarray(bias, np.float64)
+    y = _act64(h, epilogue)
+    return y + np.asarray(resid, np.float64) if resid is not None else y
+
+
+def linear_terms(a, w, bias, resid=None):
+    """S = sum_k |a_k w_k| + |bias| (+ |resid|)"""
+    S = np.abs(np.asarray(a, np.float64)) @ np.abs(np.asarray(w, np.float64)).T + np.abs(np.asarray(bias, np.float64))
+    return S + np.abs(np.asarray(resid, np.float64)) if resid is not None else S
+
+
+def linear_bound(a, w, bias, resid=None, epilogue="none", out_bf16=False):
+    """(K + 4) 2^-23 S + 2^-133, x 1.13 and + C_G 2^-23 max(|h|, |gelu h|) under GELU, + 2^-8 |y| for a bf16 output"""
+    K = np.asarray(a).shape[-1]
+    acc = (K + 4) * U * linear_terms(a, w, bias, resid)
+    y = linear_ref(a, w, bias, resid, epilogue)
+    if epilogue == "gelu":
+        h = linear_ref(a, w, bias)
+        acc = GELU_LIP * acc + C_G * U * np.maximum(np.abs(h), np.abs(gelu64(h)))
+    return acc + TINY + (BF * np.abs(y) if out_bf16 else 0.0)
+
+
+def gelu32(h):
+    """gelu_erf of common.h in fp32 (the host's erff, not the device's)"""
+    h = torch.from_numpy(np.ascontiguousarray(h, dtype=np.float32))
+    return (0.5 * h * (1.0 + torch.special.erf(h * np.float32(0.70710678118654752440)))).numpy()
+
+
+def emulate_linear(a, w, bias, resid=None, epilogue="none", out_bf16=False, bf16_ops=False):
+    """fp32 accumulation one MFMA k-group at a time (16 values in fp32, 32 in bf16), fp32 epilogue, one rounding"""
+    a, w = np.asarray(a, np.float32), np.asarray(w, np.float32)
+    kc = 32 if bf16_ops else 16
+    acc = np.zeros((a.shape[0], w.shape[0]), np.float32)
+    for k in range(0, a.shape[1], kc):
+        acc = (acc + a[:, k:k + kc] @ w[:, k:k + kc].T).astype(np.float32)
+    v = (acc + np.asarray(bias, np.float32)).astype(np.float32)
+    if epilogue == "gelu":
+        v = gelu32(v)
+    elif epilogue == "relu":
+        v = np.maximum(v, np.float32(0))
+    if resid is not None:
+        v = (v + np.asarray(resid, np.float32)).astype(np.float32)
+    return rounded(v, out_bf16)
+
+
+LINEAR_VARIANTS = ("bias_tile", "last_kstep", "resid_before_gelu", "round_before_resid", "row_M")
+
+
+def linear_variant(name, a, w, bias, resid=None, epilogue="none", bf16_ops=False, a_next=None):
+    """a wrong GEMM in float64 -> (result before the output rounding, mask of the elements it corrupts).  a_next: the row that
+    follows A in memory (row_M)"""
+    a, w, bias = (np.asarray(v, np.float64) for v in (a, w, bias))
+    M, K = a.shape
+    Nn = w.shape[0]
+    r = np.asarray(resid, np.float64) if resid is not None else 0.0
+    mask = np.ones((M, Nn), bool)
+    if name == "bias_tile":
+        t0 = 32 * ((Nn - 1) // 32)
+        b2 = bias.copy()
+        b2[t0:t0 + 32] = 0.0
+        mask[:] = False
+        mask[:, t0:t0 + 32] = True
+        return _act64(a @ w.T + b2, epilogue) + r, mask
+    if name == "last_kstep":
+        kc = 32 if bf16_ops else 16
+        return _act64(a[:, :K - kc] @ w[:, :K - kc].T + bias, epilogue) + r, mask
+    if name == "resid_before_gelu":
+        return _act64(a @ w.T + bias + r, epilogue), mask
+    if name == "round_before_resid":
+        h = _act64(a @ w.T + bias, epilogue)
+        return (bf16_round(h).astype(np.float64) if bf16_ops else h) + r, mask
+    if name == "row_M":
+        a2 = a.copy()
+        a2[M - 1] = np.asarray(a_next, np.float64)
+        mask[:] = False
+        mask[M - 1] = True
+        return _act64(a2 @ w.T + bias, epilogue) + r, mask
+    raise KeyError(name)
+
+
+CANCEL_GAIN = 65536.0
+MIN_TAIL, MIN_NEG = 0.02, 0.015  # GELU pre-activations beyond |8| / in [-8, -2] (test_gpu_vit_units.MIN_TAIL, MIN_NEG)
+
+
+def linear_inputs(M, Nn, K, seed, bf16_ops, gelu=False, resid=False):
+    """A [M + 1, K] (the last row is what follows A in memory), W [Nn, K], bias, resid or None, mask of the cancelling rows --
+    values already rounded to bf16 where the kernel reads bf16.
+    W: U(-1.5, 1.5) / sqrt K, its second half of K the first half rotated by one (W[n, K/2 + k] = W[n, (k + 1) % (K/2)]).
+    Cancelling rows (every 5th and the last but one): a = 65536 (z, -(1 - 2^-12) rot(z)): the two halves of the sum cancel to 2^-12 of their
+    terms, S / |y| >= 1e3.  gelu: the bias of columns n % 8 == 0 is +-(9 ... 12) and of n % 8 == 1 is -5 +- 2.5 (the far tails and
+    the negative lobe); otherwise U(-0.5, 0.5)."""
+    h = K // 2
+    a = synth.hash_uniform_np((M + 1, K), seed, 1.0)
+    w = synth.hash_uniform_np((Nn, K), seed + 1, 1.5 / np.sqrt(K))
+    w[:, h:] = np.roll(w[:, :h], -1, axis=1)
+    cancel = np.zeros(M, bool)
+    cancel[::5] = True
+    cancel[max(M - 2, 0)] = True
+    if M > 1:
+        cancel[M - 1] = False  # (the last row stays ordinary: a kernel that reads row M in its place shows against an O(1) bound)
+    rows = np.nonzero(cancel)[0]
+    z = a[rows, :h] * np.float32(CANCEL_GAIN)
+    a[rows, :h] = z
+    a[rows, h:] = -np.roll(z, -1, axis=1) * np.float32(1.0 - 2.0 ** -12)
+    bias = synth.hash_uniform_np((Nn,), seed + 2, 0.5)
+    if gelu:
+        n = np.arange(Nn)
+        u = synth.hash_uniform_np((Nn,), seed + 3, 1.0)
+        bias = np.where(n % 8 == 0, np.where(u >= 0, 1.0, -1.0) * (10.5 + 1.5 * u), bias)
+        bias = np.where(n % 8 == 1, -5.0 + 2.5 * u, bias).astype(np.float32)
+    r = synth.hash_uniform_np((M, Nn), seed + 4, 1.0) if resid else None
+    if bf16_ops:
+        a, w = bf16_round(a), bf16_round(w)
+    return a, w, bias, r, cancel
+
+
+# the seven plain-loader epilogue combinations of gemm.hip: dispatch -> (flags, activation, resid, "output is bf16 in the bf16 dtype")
+EPILOGUES = {
+    "plain": (0, "none", False, True),
+    "gelu": (EPI_GELU, "gelu", False, True),
+    "relu": (EPI_RELU, "relu", False, True),
+    "f32": (EPI_OUT_F32, "none", False, False),
+    "relu_f32": (EPI_RELU | EPI_OUT_F32, "relu", False, False),
+    "gelu_f32": (EPI_GELU | EPI_OUT_F32, "gelu", False, False),
+    "resid_f32": (EPI_RESID | EPI_OUT_F32, "none", True, False),
+}
+LIN_M = (1, 15, 16, 17, 272, 273, SMALL_M, SMALL_M + 1, 1361)
+LIN_N = (4, 8, 36, 128, 132, 384)
+LIN_K = {F32: (32, 64, 96, 192, 384, 1024), BF16: (64, 128, 192, 384, 1024, 1536)}
+
+
+def linear_branch(M, K, dtype):
+    """the kernel gemm.hip: launch picks for a plain hipt_linear call"""
+    if M > SMALL_M:
+        return "tiled"
+    return "ring" if K % (SMALL_RING * 4 * (4 if dtype == F32 else 8)) == 0 else "guarded"
+
+
+def linear_launches(epi, dtype):
+    """nine launches per (epilogue, dtype): every M once, every N and every K of the dtype at least once, the N and K cycles shifted
+    by the epilogue so that the pairings differ between epilogues; every third launch with padded leading dimensions; M = 1361 in
+    bf16 is always the largest shape (1361 x 384 x 1536).
+    -> (M, N, K, padded, branch)"""
+    e = list(EPILOGUES).index(epi)
+    out = []
+    for i, M in enumerate(LIN_M):
+        Nn, K = LIN_N[(i + e) % 6], LIN_K[dtype][(i + 2 * e + 1) % 6]
+        if M == 1361 and dtype == BF16:
+            Nn, K = 384, 1536
+        out.append((M, Nn, K, i % 3 == 1, linear_branch(M, K, dtype)))
+    return out
+
+
+def linear_lds(Nn, K, dtype, padded):
+    """(lda, ldw, ldc) in elements"""
+    return (K + 16, K + (4 if dtype == F32 else 8), Nn + 4) if padded else (K, K, Nn)
+
+
+# =====================================================================================================================
+# Attention
+# =====================================================================================================================
+def _split(qkv, heads):
+    B, ntok, C3 = qkv.shape
+    dh = C3 // 3 // heads
+    return np.transpose(np.asarray(qkv).reshape(B, ntok, 3, heads, dh), (2, 0, 3, 1, 4))  # q, k, v [B, heads, ntok, dh]
+
+
+def attention_ref(qkv, heads, scale):
+    """-> (out [B, ntok, heads dh], probs [B, heads, ntok, ntok]) in float64"""
+    q, k, v = _split(np.asarray(qkv, np.float64), heads)
+    s = q @ k.transpose(0, 1, 3, 2) * scale
+    e = np.exp(s - s.max(-1, keepdims=True))
+    p = e / e.sum(-1, keepdims=True)
+    B, _, ntok, dh = q.shape
+    return (p @ v).transpose(0, 2, 1, 3).reshape(B, ntok, heads * dh), p
+
+
+def attention_bound(qkv, heads, scale, bf16, kernel="attn"):
+    """-> (bound of out, bound of probs), DESIGN.md 22.4.  Both kernels round at the same points (the unnormalised exponentials to
+    bf16 before P V, the stored output); they differ in how the exponent is formed -- (s - m) sl2e in two roundings in attention.hip,
+    one fma against the rounded m sl2e, which is common to the row and cancels, in attention2.hip -- and the 4 u |t| term covers both,
+    so `kernel` does not change the bound (it does change the emulation)."""
+    assert kernel in ("attn", "attn64")
+    q, k, v = _split(np.asarray(qkv, np.float64), heads)
+    B, _, ntok, dh = q.shape
+    s = q @ k.transpose(0, 1, 3, 2) * scale
+    t = s - s.max(-1, keepdims=True)
+    e = np.exp(t)
+    p = e / e.sum(-1, keepdims=True)
+    delta = (dh + 4) * U * abs(scale) * (np.abs(q) @ np.abs(k).transpose(0, 1, 3, 2))
+    rho = np.expm1(delta + (p * delta).sum(-1, keepdims=True) + U * (C_P + 4 * np.abs(t) + ntok + 4))
+    bp = rho * p + FLUSH
+    av = np.abs(v)
+    o = (p @ v)
+    bo = (rho * p) @ av + ((ntok + 4) * U + (BF if bf16 else 0.0)) * (p @ av) + (BF if bf16 else U) * np.abs(o) + FLUSH * (1 + av.sum(-2, keepdims=True))
+    return bo.transpose(0, 2, 1, 3).reshape(B, ntok, heads * dh), bp
+
+
+def emulate_attention(qkv, heads, scale, bf16, kernel="attn"):
+    """-> (out, probs): fp32 scores one MFMA k-group at a time, fp32 softmax in the exp2 domain with the kernel's exponent arithmetic,
+    P rounded to bf16 before P V in bf16 mode, P V accumulated 16 (fp32) or 32 (bf16) keys at a time, one rounding of the output"""
+    q, k, v = (np.ascontiguousarray(x, dtype=np.float32) for x in _split(np.asarray(qkv, np.float32), heads))
+    B, _, ntok, dh = q.shape
+    kc = 32 if bf16 else 16
+    s = np.zeros((B, heads, ntok, ntok), np.float32)
+    for d in range(0, dh, kc):
+        s = (s + q[..., d:d + kc] @ k[..., d:d + kc].transpose(0, 1, 3, 2)).astype(np.float32)
+    sl2e = np.float32(np.float32(scale) * np.float32(1.4426950408889634))
+    m = s.max(-1, keepdims=True)
+    if kernel == "attn":
+        x = ((s - m).astype(np.float32) * sl2e).astype(np.float32)
+    else:
+        ms = (-m * sl2e).astype(np.float32)
+        x = (s.astype(np.float64) * np.float64(sl2e) + ms.astype(np.float64)).astype(np.float32)
+    e = np.exp2(x).astype(np.float32)
+    l = np.zeros((B, heads, ntok, 1), np.float32)
+    for j in range(0, ntok, 16):
+        l = (l + e[..., j:j + 16].sum(-1, keepdims=True, dtype=np.float32)).astype(np.float32)
+    inv = (np.float32(1.0) / l).astype(np.float32)
+    probs = (e * inv).astype(np.float32)
+    pe = bf16_round(e) if bf16 else e
+    o = np.zeros((B, heads, ntok, dh), np.float32)
+    for j in range(0, ntok, kc):
+        o = (o + pe[..., j:j + kc] @ v[..., j:j + kc, :]).astype(np.float32)
+    o = (o * inv).astype(np.float32)
+    return rounded(o.transpose(0, 2, 1, 3).reshape(B, ntok, heads * dh), bf16), probs.astype(np.float64)
+
+
+ATTN_VARIANTS = ("scale_twice", "no_log2e", "pad_unmasked", "no_max", "v_group_perm", "next_head_v")
+# the input family (attn_inputs) on which each variant must be caught; pad_unmasked is wrong only where ntok % 16 != 0, v_group_perm
+# needs ntok >= 4, next_head_v heads >= 2
+ATTN_CATCHES = {"scale_twice": "ordinary", "no_log2e": "ordinary", "pad_unmasked": "ordinary", "no_max": "spike_first",
+                "v_group_perm": "ordinary", "next_head_v": "ordinary"}
+
+
+def attention_variant(name, qkv, heads, scale):
+    """a wrong attention kernel -> (out, probs) before the output rounding"""
+    q, k, v = _split(np.asarray(qkv, np.float64), heads)
+    B, _, ntok, dh = q.shape
+    s = q @ k.transpose(0, 1, 3, 2) * scale
+    if name == "scale_twice":
+        s = s * scale
+    if name == "pad_unmasked":  # the padding keys of the last partial 16-key tile score 0 and their V rows are zero
+        npad = -ntok % 16
+        s = np.concatenate([s, np.zeros(s.shape[:-1] + (npad,))], -1)
+        v = np.concatenate([v, np.zeros(v.shape[:2] + (npad, dh))], 2)
+    if name == "no_max":  # fp32 exponentials of the raw scores
+        with np.errstate(over="ignore", invalid="ignore"):
+            e = np.exp(s.astype(np.float32)).astype(np.float32)
+            p = (e / e.sum(-1, keepdims=True, dtype=np.float32)).astype(np.float64)
+    else:
+        t = s - s.max(-1, keepdims=True)
+        e = np.exp2(t) if name == "no_log2e" else np.exp(t)
+        p = e / e.sum(-1, keepdims=True)
+    if name == "v_group_perm":  # keys 0 .. 3 of the first tile meet V rows 3 .. 0
+        v = v.copy()
+        v[:, :, :4] = v[:, :, 3::-1] if ntok >= 4 else v[:, :, :4]
+    if name == "next_head_v":
+        v = np.roll(v, -1, axis=1)
+    with np.errstate(invalid="ignore"):
+        o = (p @ v).transpose(0, 2, 1, 3).reshape(B, ntok, heads * dh)
+    return o, p[..., :ntok]
+
+
+ATTN_FAMILIES = ("ordinary", "spike_first", "spike_last", "flat_row")
+SPIKE = 60.0
+
+
+def attn_inputs(B, ntok, heads, dh, seed, family, bf16):
+    """qkv [B, ntok, 3 heads dh] U(-1.5, 1.5), rounded to bf16 where the kernel reads bf16.  spike_first / spike_last: key
+    min(3, ntok - 1) / ntok - 1 (the last valid key of a partial tile) of every head x 60; flat_row: query min(1, ntok - 1) x 1e-3 (all its
+    logits nearly equal).  -> (qkv, index of the spiked key or None)"""
+    C = heads * dh
+    qkv = synth.hash_uniform_np((B, ntok, 3 * C), seed, 1.5)
+    key = None
+    if family in ("spike_first", "spike_last"):
+        key = min(3, ntok - 1) if family == "spike_first" else ntok - 1
+        qkv[:, key, C:2 * C] *= np.float32(SPIKE)
+    elif family == "flat_row":
+        qkv[:, min(1, ntok - 1), :C] *= np.float32(1e-3)
+    return (bf16_round(qkv) if bf16 else qkv), key
+
+
+def spike_rows(qkv, heads, scale, key, overflow=False):
+    """[B, heads, ntok] mask of the query rows whose maximum is the spiked key (those with q . k > 0: about half); overflow: only
+    those whose score there is beyond 89, where exp overflows fp32"""
+    q, k, _ = _split(np.asarray(qkv, np.float64), heads)
+    s = q @ k.transpose(0, 1, 3, 2) * scale
+    return (s.argmax(-1) == key) & ((not overflow) | (s.max(-1) > 89.0))
+
+
+ATTN_NTOK = (1, 15, 16, 17, 32, 33, 257, 272, 273, 288)
+ATTN_BH = ((1, 2), (8, 6), (9, 6))
+ATTN_MAX = 288
+
+
+def attention_branch(ntok, dh, B, heads, bf16, probs):
+    """what attention.hip / attention2.hip launch: the kernel, its key tiles, whether the grid splits the query tiles (y > 1 asks
+    for more than four query tiles as well), how many keys of the last tile are masked"""
+    k64 = bf16 and dh == 64 and ATTN_MAX - 32 < ntok <= ATTN_MAX and not probs
+    tiles = (17 if ntok <= ATTN_MAX - 16 else 18) if k64 else (2 if ntok <= 32 else 18)
+    return f"{'attn64' if k64 else 'attn'}-nkt{tiles}-{'ysplit' if B * heads <= 48 else 'y1'}-pad{-ntok % 16}"
+
+
+def attention_launches(dh, bf16):
+    """ten launches per (dh, dtype): every ntok once, the three (B, heads) in turn (257 and 273 both with 54 heads and with 48 over
+    the two head widths) -> (B, ntok, heads, family); the families in turn as well, the spikes at the partial tiles"""
+    out = []
+    for i, ntok in enumerate(ATTN_NTOK):
+        B, heads = ATTN_BH[(i + (dh == 64)) % 3]
+        if ntok == 273 and dh == 64:
+            B, heads = ATTN_BH[2]  # (the 64-wide-head kernel with 18 key tiles on the unsplit grid; 288 has the split one)
+        fam = ATTN_FAMILIES[(i + 2 * (dh == 64) + bf16) % 4]
+        if ntok in (17, 33, 273) and dh == 64:
+            fam = "spike_last"
+        if ntok in (15, 257) and dh == 32:
+            fam = "spike_last"
+        out.append((B, ntok, heads, fam))
+    return out
