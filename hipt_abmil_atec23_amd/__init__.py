@@ -50,6 +50,8 @@ _LAZY = {
     "point_polygon_test": ("tiling", "point_polygon_test"), "process_contour": ("tiling", "process_contour"),
     "process_contours": ("tiling", "process_contours"), "process_contours_like": ("tiling", "process_contours_like"),
     "pack_slide": ("tiling", "pack_slide"), "plan_contours": ("tiling", "plan_contours"),
+    # Pillow's Image.resize of uint8 RGB images (the heat-maps' background, the ResNet routes' patch resize)
+    "resize_u8": ("resize", "resize_u8"), "resize_table": ("resize", "resize_table"), "resize_patches": ("resize", "resize_patches"),
 }
 
 

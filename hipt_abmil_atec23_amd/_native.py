@@ -88,6 +88,7 @@ PCT_REF_TILE, PCT_QUERIES_PER_WG = 512, 128   # HIPT_PCT_REF_TILE, HIPT_PCT_QUER
 HIER_MAX_L, HIER_MAX_UPSCALE, HIER_MAX_HEADS, HIER_MAX_LUT = 4096, 256, 8, 4096   # HIPT_HIER_MAX_*
 TILE_BASIC, TILE_CENTER, TILE_FOUR_PT, TILE_FOUR_PT_HARD = 0, 1, 2, 3             # HIPT_TILE_*
 TILING_COORD_BOUND, TILING_EDGE_CHUNK, TILING_TILE, TILING_CONTOUR_INTS = 1 << 30, 1024, 256, 9   # HIPT_TILING_*
+RESIZE_ROUTE_AUTO, RESIZE_ROUTE_GENERAL, RESIZE_ROUTE_FUSED, RESIZE_MAX_KSIZE = 0, 1, 2, 512      # HIPT_RESIZE_*
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -188,6 +189,8 @@ SIGNATURES = {
                               _p]),
     "hipt_point_polygon_test": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p]),
     "hipt_tile_contours": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _i64, _p]),
+    "hipt_resize_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "hipt_resize_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _sz, _i, _p]),
 }
 
 _lib = None

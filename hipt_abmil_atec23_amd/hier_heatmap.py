@@ -11,7 +11,8 @@ counts over the original ones (``closed_form_percentiles``; ``hipt_hier_ranks``)
 pixel's scores once and writes every picture from them.  All arithmetic is integer, float64 in the reference's order, or the
 float32 blend of ``heatmap`` -- the pictures are the reference's byte for byte.
 
-Host work, by design: the colour table (matplotlib), Pillow's ``resize`` of the region for the background, the PNG files.
+Host work, by design: the colour table (matplotlib) and the PNG files.  The background -- Pillow's ``region.resize`` -- is
+``resize.resize_u8`` on the region tensor already on the device, Pillow's bytes; ``host_resize=True`` is Pillow itself.
 As in ``heatmap`` the blend is cv2.addWeighted's documented formula, not cv2 itself.
 """
 from __future__ import annotations
@@ -299,13 +300,13 @@ def _as_region_array(region) -> np.ndarray:
 
 
 def hierarchical_heatmaps(hipt, region, offset=128, scale=4, alpha=0.5, cmap="coolwarm", threshold=None, w256=2, pairs=None,
-                          which=("4k", "256", "blend"), base=None):
+                          which=("4k", "256", "blend"), base=None, host_resize=False):
     """The hierarchical heat-maps of one region (a PIL image or a uint8 ``[H, W, 3]`` array or tensor; H and W multiples of 256) as
     a dict of uint8 device tensors (``compose_heatmaps`` names them): the four ``shifted_regions`` go through ViT-256 and ViT-4K
     (``region_attention_maps``), the ranks and the pictures follow on the device.  ``base`` (uint8 ``[Hs, Ws, 3]``) is the
-    background; absent, it is Pillow's ``region.resize((Ws, Hs))`` computed on the host, as the reference does (:385)."""
+    background; absent, it is the reference's ``region.resize((Ws, Hs))`` (:385) -- computed on the device by ``resize_u8``, the same
+    bytes, or with ``host_resize=True`` by Pillow on the host."""
     import torch
-    from PIL import Image
     if scale not in SCALES:
         raise ValueError(f"hier_heatmap: scale {scale}; the pictures exist at {SCALES}")
     if H._is_tensor(region) and region.is_cuda:
@@ -318,7 +319,11 @@ def hierarchical_heatmaps(hipt, region, offset=128, scale=4, alpha=0.5, cmap="co
         raise ValueError(f"hier_heatmap: a {h} x {w} region; the shifted layers line up only on whole 256-pixel patches")
     w_256, h_256 = h // 256, w // 256   # (the reference's naming: tensor dimension 2, the image's rows, is "w")
     a256, a4k = region_attention_maps(hipt, shifted_regions(r_dev, offset))
-    if base is None:
+    if base is None and not host_resize:
+        from .resize import resize_u8
+        base = resize_u8(r_dev, (w // scale, h // scale))
+    elif base is None:
+        from PIL import Image
         pil = region if isinstance(region, Image.Image) else Image.fromarray(_as_region_array(region) if r_np is None else r_np)
         base = np.array(pil.resize((w // scale, h // scale)))
     return compose_heatmaps(a256, a4k, w_256, h_256, base, offset=offset, scale=scale, alpha=alpha, cmap=cmap, threshold=threshold,

@@ -849,6 +849,39 @@ int hipt_point_polygon_test(const int32_t* verts, int V, const int32_t* poly_off
 int hipt_tile_contours(const int32_t* verts, int V, const int32_t* poly_off, int P, const int32_t* contours, int C, const int32_t* units,
                        int U, int mode, int ref_patch_size, int shift, uint8_t* keep, int64_t keep_len, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * Pillow's Image.resize of 8-bit RGB images (HIPT_4K/hipt_heatmap_utils.py:385, HIPT_4K/hipt_4k.py:204, datasets/dataset_h5.py:92,202,
+ * wsi_core/WholeSlideImage.py:690-694).  Integer arithmetic only; the results are Pillow's bytes.
+ *
+ * src uint8 [n, in_h, in_w, 3] -> dst uint8 [n, out_h, out_w, 3], interleaved RGB, contiguous, n >= 1; every image of a call shares
+ * the geometry and the tables.  Pillow (ImagingResample, reducing_gap = None, no box) resizes in two separable passes, horizontal
+ * first, and stores the intermediate image as uint8.  A pass along an axis from I to O samples is, per output xx and channel,
+ *     out = clip((2^21 + sum_{x < xmax} in[xmin + x] * k[xx * ksize + x]) >> 22, 0, 255)         (int32, arithmetic shift)
+ * with (xmin, xmax) = b[2 xx], b[2 xx + 1].  k (int32 [O, ksize]) and b (int32 [O, 2]) are DEVICE arrays the caller computes once per
+ * (I, O, filter) on the host in doubles (precompute_coeffs + normalize_coeffs_8bpc; hipt_abmil_atec23_amd/resize.py: resize_table):
+ * kx, bx, ksize_x for the width, ky, by, ksize_y for the height.  An axis whose length does not change is skipped, as Pillow skips
+ * it (its table pointers may be NULL and are ignored); with both unchanged dst becomes a copy of src.  The caller guarantees
+ * 255 * sum_x |k[xx, x]| + 2^21 < 2^31 for every row (true of Pillow's filters); the kernel clamps every (xmin, xmax) it reads to the
+ * image and to its staged window, so a wrong table gives wrong pixels and no access outside src, dst, the tables or the workspace.
+ *
+ * Routes.  HIPT_RESIZE_FUSED: one launch; a workgroup runs the horizontal pass over the input rows its output tile's vertical taps
+ * need, keeps them in LDS as uint8 (clipped exactly as the stored intermediate image) and runs the vertical pass out of LDS: the
+ * input is read once, no intermediate image reaches memory, no workspace.  It takes calls that change both axes and whose tile fits
+ * 64 KiB of LDS, else HIPT_E_UNSUPPORTED with nothing launched.  HIPT_RESIZE_GENERAL: one launch per changing axis (two, one or --
+ * equal sizes, the copy -- one); with two, the intermediate image [n, in_h, out_w, 3] is carved from ws.  HIPT_RESIZE_AUTO: fused
+ * where it applies, else general.  hipt_resize_workspace_bytes: the bytes ws must hold for a route -- 0 for FUSED and for calls that
+ * change at most one axis; for AUTO the general route's need, since the choice also depends on the tap counts (0 too when the
+ * geometry is outside the envelope: the call itself says why).  ws: 256-byte aligned (NULL with ws_bytes = 0 where nothing is needed).
+ * Envelope: every side below 2^24, n * max(in_h, out_h) * max(in_w, out_w) * 3 below 2^40, ksize_x, ksize_y <= HIPT_RESIZE_MAX_KSIZE,
+ * else HIPT_E_UNSUPPORTED with nothing launched.  src 16-byte aligned (rows are read as 16-byte vectors), dst and the tables 4-byte;
+ * src != dst.  No atomics, no allocation, no host synchronisation: the launches can be captured into a graph.
+ * ---------------------------------------------------------------------------------- */
+enum { HIPT_RESIZE_AUTO = 0, HIPT_RESIZE_GENERAL = 1, HIPT_RESIZE_FUSED = 2 };
+#define HIPT_RESIZE_MAX_KSIZE 512
+size_t hipt_resize_workspace_bytes(int n, int in_h, int in_w, int out_h, int out_w, int route);
+int hipt_resize_u8(const uint8_t* src, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* kx, const int32_t* bx, int ksize_x,
+                   const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst, void* ws, size_t ws_bytes, int route, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

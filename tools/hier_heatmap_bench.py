@@ -4,8 +4,9 @@ Timed with device events around ``iters`` calls, median of ``rounds`` rounds, ev
   compose      ``compose_heatmaps`` (two rank launches + the render launch) at scale 4 and at scale 1
   ranks        the two ``hipt_hier_ranks`` launches alone
   render       compose minus ranks: the render launch (plus the small permute in front of the ranks)
-  whole call   ``hierarchical_heatmaps`` at scale 4 (four regions through ViT-256 / ViT-4K, Pillow's resize on the host, the
-               pictures), with a host clock around calls that end in a device synchronise
+  whole call   ``hierarchical_heatmaps`` at scale 4 (four regions through ViT-256 / ViT-4K, Pillow's resize on the host --
+               ``host_resize=True``; tools/resize_bench.py times the default, the device resize -- and the pictures), with a
+               host clock around calls that end in a device synchronise
 The render kernel's figure of merit is the bytes it must write (144 per pixel for 48 pictures) per second, against the HBM peak
 (8.0 TB/s specified; MI355X_MICROARCH: 6.29 TB/s measured for a copy).  Attention maps are seeded random numbers: the kernels'
 time does not depend on the values.  The pictures of the scale-4 case are compared with the numpy restatement when
@@ -121,9 +122,9 @@ def main():
         HH.hierarchical_heatmaps(m, region_d, scale=4, **kw)
         torch.cuda.synchronize()
     per = {"with_host_resize": [], "base_given": []}
-    whole(), whole(base=base)
+    whole(host_resize=True), whole(base=base)
     for _ in range(args.rounds):
-        for name, kw in (("with_host_resize", {}), ("base_given", {"base": base})):
+        for name, kw in (("with_host_resize", {"host_resize": True}), ("base_given", {"base": base})):
             t0 = time.perf_counter()
             whole(**kw)
             per[name].append(time.perf_counter() - t0)
