@@ -46,6 +46,13 @@ _LAZY = {
     "region_attention_maps": ("hier_heatmap", "region_attention_maps"), "shifted_regions": ("hier_heatmap", "shifted_regions"),
     "colour_table_n": ("hier_heatmap", "colour_table_n"), "cmap_map": ("hier_heatmap", "cmap_map"),
     "create_hierarchical_heatmaps_indiv": ("hier_heatmap", "create_hierarchical_heatmaps_indiv"),
+    "hierarchical_heatmaps_concat_select": ("hier_heatmap", "hierarchical_heatmaps_concat_select"),
+    "create_hierarchical_heatmaps_concat_select": ("hier_heatmap", "create_hierarchical_heatmaps_concat_select"),
+    # patch-level ViT-256 attention heat-maps in batches (create_patch_heatmaps_indiv, create_patch_heatmaps_concat)
+    "patch_heatmaps": ("patch_heatmap", "patch_heatmaps"), "compose_patch_heatmaps": ("patch_heatmap", "compose_patch_heatmaps"),
+    "patch_attention_maps": ("patch_heatmap", "patch_attention_maps"), "shifted_patches": ("patch_heatmap", "shifted_patches"),
+    "create_patch_heatmaps_indiv": ("patch_heatmap", "create_patch_heatmaps_indiv"),
+    "create_patch_heatmaps_concat": ("patch_heatmap", "create_patch_heatmaps_concat"),
     # patch coordinates from tissue contours (WholeSlideImage.process_contour, the contour checking functions)
     "point_polygon_test": ("tiling", "point_polygon_test"), "process_contour": ("tiling", "process_contour"),
     "process_contours": ("tiling", "process_contours"), "process_contours_like": ("tiling", "process_contours_like"),

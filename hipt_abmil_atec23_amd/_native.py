@@ -86,6 +86,7 @@ HEATMAP_TILE_W, HEATMAP_TILE_H, HEATMAP_MAX_DIM, HEATMAP_LUT_ENTRIES = 32, 8, 1 
 PCT_RANKDATA, PCT_OF_SCORE = 0, 1
 PCT_REF_TILE, PCT_QUERIES_PER_WG = 512, 128   # HIPT_PCT_REF_TILE, HIPT_PCT_QUERIES_PER_WG
 HIER_MAX_L, HIER_MAX_UPSCALE, HIER_MAX_HEADS, HIER_MAX_LUT = 4096, 256, 8, 4096   # HIPT_HIER_MAX_*
+PATCH_MAX_P = 1 << 20                                                             # HIPT_PATCH_MAX_P
 TILE_BASIC, TILE_CENTER, TILE_FOUR_PT, TILE_FOUR_PT_HARD = 0, 1, 2, 3             # HIPT_TILE_*
 TILING_COORD_BOUND, TILING_EDGE_CHUNK, TILING_TILE, TILING_CONTOUR_INTS = 1 << 30, 1024, 256, 9   # HIPT_TILING_*
 RESIZE_ROUTE_AUTO, RESIZE_ROUTE_GENERAL, RESIZE_ROUTE_FUSED, RESIZE_MAX_KSIZE = 0, 1, 2, 512      # HIPT_RESIZE_*
@@ -187,6 +188,7 @@ SIGNATURES = {
     "hipt_hier_ranks": (_i, [_p, _i, _i, _i, _p, _p]),
     "hipt_hier_render": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, C.c_double, C.c_double, _p, _i, _i, C.c_double, _p, _p, _p, _p,
                               _p]),
+    "hipt_patch_render": (_i, [_p, _p, _i, _i, _p, _i, _i, C.c_double, _i, C.c_double, _i, _p, _p, _p]),
     "hipt_point_polygon_test": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p]),
     "hipt_tile_contours": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _i64, _p]),
     "hipt_resize_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),

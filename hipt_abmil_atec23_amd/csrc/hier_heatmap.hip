@@ -10,10 +10,11 @@
 //                          each layer, forms the nh + nh scores once and writes every requested picture from them: 12 bytes a
 //                          picture, as three whole 32-bit words, lane after lane on consecutive addresses.  The ViT-256 scores wait
 //                          in LDS while the loop over the ViT-4K heads pairs them.
+// The four-pixel look-up, paint, store and the thresholded picture's rule are heat_paint.h's, shared with patch_heatmap.hip.
 // All arithmetic is integer, float64 in the order written, or the float32 blend of common.h.
 // -ffp-contract=off (Makefile): every float64 operation and the blend's two products and their sum are rounded one by one.
 // No inline assembly, no atomics; every store is a vector store.
-#include "common.h"
+#include "heat_paint.h"   // the four-pixel look-up, blend, store and the thresholded picture's rule
 
 namespace {
 
@@ -22,7 +23,6 @@ constexpr int HR_MAX_L = HIPT_HIER_MAX_L;
 constexpr int HH_THREADS = 128;                    // rendering: lanes (groups of four pixels) per workgroup
 constexpr int HH_MAX_HEADS = HIPT_HIER_MAX_HEADS;
 constexpr int HH_MAX_LUT = HIPT_HIER_MAX_LUT;
-constexpr int HH_PX = 4;                           // pixels per lane
 static_assert(HR_MAX_L % 4 == 0, "the counting loop reads four values at a time");
 static_assert(HH_MAX_LUT * 4 + HH_MAX_HEADS * HH_PX * 8 * HH_THREADS <= 64 * 1024, "the render kernel's LDS fits the default limit");
 
@@ -73,44 +73,12 @@ struct HierArgs {
     signed char slot[HH_MAX_HEADS * HH_MAX_HEADS];   // picture of hm_blend for the pair (j, i) at [j * HH_MAX_HEADS + i], or -1
 };
 
-struct Words3 {
-    uint32_t w[3];
-};
-
-// 12 bytes (four pixels) as three aligned words
-__device__ __forceinline__ void hh_store(uint8_t* dst, const uint8_t (&o)[12]) {
-    Words3 w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        w.w[k] = (uint32_t)o[4 * k] | ((uint32_t)o[4 * k + 1] << 8) | ((uint32_t)o[4 * k + 2] << 16) | ((uint32_t)o[4 * k + 3] << 24);
-    *(Words3*)dst = w;
-}
-
-__device__ __forceinline__ int hh_entry(double score, int lut_n) {   // matplotlib's look-up of a value in [0, 1]
-    const int e = (int)(score * (double)lut_n);
-    return min(max(e, 0), lut_n - 1);
-}
-
-// one picture's four pixels: table entries -> colours -> blend with the base -> store
-__device__ __forceinline__ void hh_paint(uint8_t* dst, const uint32_t* lut, const int (&entry)[HH_PX], const uint8_t (&base)[12], float a,
-                                         float b) {
-    uint8_t o[12];
-#pragma unroll
-    for (int k = 0; k < HH_PX; ++k) {
-        const uint32_t c = lut[entry[k]];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) o[3 * k + ch] = blend_u8((uint8_t)(c >> (8 * ch)), base[3 * k + ch], a, b);
-    }
-    hh_store(dst, o);
-}
-
 __global__ __launch_bounds__(HH_THREADS) void hier_render_kernel(const HierArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* lut = (uint32_t*)smem;                                      // [lut_n] packed r | g << 8 | b << 16
     double* s256_lds = (double*)(smem + (((size_t)A.lut_n * 4 + 15) & ~(size_t)15));   // [nh][HH_PX][HH_THREADS]
     const int t = threadIdx.x;
-    for (int e = t; e < A.lut_n; e += HH_THREADS)
-        lut[e] = (uint32_t)A.lut[3 * e] | ((uint32_t)A.lut[3 * e + 1] << 8) | ((uint32_t)A.lut[3 * e + 2] << 16);
+    hh_stage_lut(lut, A.lut, A.lut_n, t, HH_THREADS);
     __syncthreads();   // (the only barrier: lanes past the image leave after it)
 
     const int gpr = A.Ws / HH_PX;   // groups per row (Ws % 4 == 0: a group never straddles rows)
@@ -122,11 +90,7 @@ __global__ __launch_bounds__(HH_THREADS) void hier_render_kernel(const HierArgs 
     const int bmask = (1 << A.lb) - 1;
 
     uint8_t base[12];
-    {
-        const Words3 w = *(const Words3*)(A.base + pix * 3);
-#pragma unroll
-        for (int k = 0; k < 12; ++k) base[k] = (uint8_t)(w.w[k >> 2] >> (8 * (k & 3)));
-    }
+    hh_load(A.base + pix * 3, base);
 
     // where every layer reads: the patch (the ViT-4K token) and the ViT-256 token of it, or -1 where the layer is absent
     int patch[4][HH_PX], token[2][HH_PX];
@@ -164,22 +128,7 @@ __global__ __launch_bounds__(HH_THREADS) void hier_render_kernel(const HierArgs 
             s256_lds[((size_t)i * HH_PX + k) * HH_THREADS + t] = s[k];
         }
         if (A.hm256) hh_paint(A.hm256 + (size_t)i * pic + pix * 3, lut, entry, base, A.a, A.b);
-        if (A.hm_thr) {
-            uint8_t o[12];
-#pragma unroll
-            for (int k = 0; k < HH_PX; ++k) {
-                const bool above = s[k] > A.thr || (s[k] == A.thr && A.thr == 0.95);   // (a score equal to a threshold of 0.95 IS the 0.95 mark)
-                const bool equal = s[k] == A.thr && !above;
-                const uint32_t c = lut[above ? A.idx_hi : A.idx_thr];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const uint8_t bl = blend_u8((uint8_t)(c >> (8 * ch)), base[3 * k + ch], A.a, A.b);
-                    // below: the base image; above: the blend; equal: neither half of the reference's sum is blanked -- a uint8 sum, which wraps
-                    o[3 * k + ch] = above ? bl : (equal ? (uint8_t)(bl + base[3 * k + ch]) : base[3 * k + ch]);
-                }
-            }
-            hh_store(A.hm_thr + (size_t)i * pic + pix * 3, o);
-        }
+        if (A.hm_thr) hh_paint_threshold(A.hm_thr + (size_t)i * pic + pix * 3, lut, s, A.thr, A.idx_hi, A.idx_thr, base, A.a, A.b);
     }
 
     if (!A.hm4k && !A.hm_blend) return;
@@ -299,12 +248,7 @@ extern "C" int hipt_hier_render(const double* pct4k, const double* pct256, int n
     A.base = base;
     A.lut = lut;
     A.lut_n = lut_n;
-    A.idx_hi = (int)(0.95 * (double)lut_n);
-    A.idx_thr = 0;
-    if (use_threshold && threshold >= 0.0 && threshold <= 1.0) {   // (no score lies outside [0, 1]: nothing equals another threshold)
-        const int e = (int)(threshold * (double)lut_n);
-        A.idx_thr = e < lut_n - 1 ? e : lut_n - 1;
-    }
+    hh_threshold_entries(lut_n, use_threshold, threshold, &A.idx_hi, &A.idx_thr);
     A.a = (float)alpha;
     A.b = (float)(1.0 - alpha);
     A.w256 = w256;

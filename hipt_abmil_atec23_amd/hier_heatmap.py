@@ -299,13 +299,9 @@ def _as_region_array(region) -> np.ndarray:
     return a
 
 
-def hierarchical_heatmaps(hipt, region, offset=128, scale=4, alpha=0.5, cmap="coolwarm", threshold=None, w256=2, pairs=None,
-                          which=("4k", "256", "blend"), base=None, host_resize=False):
-    """The hierarchical heat-maps of one region (a PIL image or a uint8 ``[H, W, 3]`` array or tensor; H and W multiples of 256) as
-    a dict of uint8 device tensors (``compose_heatmaps`` names them): the four ``shifted_regions`` go through ViT-256 and ViT-4K
-    (``region_attention_maps``), the ranks and the pictures follow on the device.  ``base`` (uint8 ``[Hs, Ws, 3]``) is the
-    background; absent, it is the reference's ``region.resize((Ws, Hs))`` (:385) -- computed on the device by ``resize_u8``, the same
-    bytes, or with ``host_resize=True`` by Pillow on the host."""
+def _region_and_background(hipt, region, scale, base, host_resize):
+    """``(the region on ViT-256's device, the background)``: ``base`` where given, else the reference's ``region.resize((Ws, Hs))``
+    (:385) by ``resize_u8`` on the device or, with ``host_resize``, by Pillow on the host."""
     import torch
     if scale not in SCALES:
         raise ValueError(f"hier_heatmap: scale {scale}; the pictures exist at {SCALES}")
@@ -317,8 +313,6 @@ def hierarchical_heatmaps(hipt, region, offset=128, scale=4, alpha=0.5, cmap="co
     h, w = int(r_dev.shape[0]), int(r_dev.shape[1])
     if h % 256 or w % 256 or not h or not w:
         raise ValueError(f"hier_heatmap: a {h} x {w} region; the shifted layers line up only on whole 256-pixel patches")
-    w_256, h_256 = h // 256, w // 256   # (the reference's naming: tensor dimension 2, the image's rows, is "w")
-    a256, a4k = region_attention_maps(hipt, shifted_regions(r_dev, offset))
     if base is None and not host_resize:
         from .resize import resize_u8
         base = resize_u8(r_dev, (w // scale, h // scale))
@@ -326,6 +320,19 @@ def hierarchical_heatmaps(hipt, region, offset=128, scale=4, alpha=0.5, cmap="co
         from PIL import Image
         pil = region if isinstance(region, Image.Image) else Image.fromarray(_as_region_array(region) if r_np is None else r_np)
         base = np.array(pil.resize((w // scale, h // scale)))
+    return r_dev, base
+
+
+def hierarchical_heatmaps(hipt, region, offset=128, scale=4, alpha=0.5, cmap="coolwarm", threshold=None, w256=2, pairs=None,
+                          which=("4k", "256", "blend"), base=None, host_resize=False):
+    """The hierarchical heat-maps of one region (a PIL image or a uint8 ``[H, W, 3]`` array or tensor; H and W multiples of 256) as
+    a dict of uint8 device tensors (``compose_heatmaps`` names them): the four ``shifted_regions`` go through ViT-256 and ViT-4K
+    (``region_attention_maps``), the ranks and the pictures follow on the device.  ``base`` (uint8 ``[Hs, Ws, 3]``) is the
+    background; absent, it is the reference's ``region.resize((Ws, Hs))`` (:385) -- computed on the device by ``resize_u8``, the same
+    bytes, or with ``host_resize=True`` by Pillow on the host."""
+    r_dev, base = _region_and_background(hipt, region, scale, base, host_resize)
+    w_256, h_256 = int(r_dev.shape[0]) // 256, int(r_dev.shape[1]) // 256   # (the reference's naming: tensor dimension 2, the image's rows, is "w")
+    a256, a4k = region_attention_maps(hipt, shifted_regions(r_dev, offset))
     return compose_heatmaps(a256, a4k, w_256, h_256, base, offset=offset, scale=scale, alpha=alpha, cmap=cmap, threshold=threshold,
                             w256=w256, pairs=pairs, which=which)
 
@@ -367,3 +374,43 @@ def create_hierarchical_heatmaps_indiv_like(region, model256, model4k, output_di
     hipt = types.SimpleNamespace(model256=model256, model4k=model4k)
     create_hierarchical_heatmaps_indiv(region, hipt, output_dir, fname, offset=offset, scale=scale, alpha=alpha, cmap=cmap,
                                        threshold=threshold)
+
+
+def hierarchical_heatmaps_concat_select(hipt, region, heads4k=(0, 5), heads256=(2,), offset=128, scale=4, alpha=0.5, cmap="coolwarm",
+                                        w256=2, base=None, host_resize=False):
+    """The side-by-side grid of hipt_heatmap_utils.py:584-667 (``create_hierarchical_heatmaps_concat_select``) as one uint8 device
+    tensor ``[(1 + len(heads256)) * Hs, (1 + len(heads4k)) * Ws, 3]``: the background and the ViT-4K pictures of ``heads4k`` on top,
+    and under them, for every head i of ``heads256``, its ViT-256 picture and the blended pictures of the pairs (j, i).  The tiles
+    are the pictures of ONE ``hierarchical_heatmaps`` call with ``pairs=`` set, copied into the canvas on the device.  The top row
+    shows the four-layer ViT-4K score, as every other picture of the family does; the reference's top row (:644) colours the first
+    layer's ranks alone."""
+    import torch
+    heads4k, heads256 = [int(j) for j in heads4k], [int(i) for i in heads256]
+    if not heads4k or not heads256:
+        raise ValueError("hier_heatmap: concat_select needs at least one ViT-4K head and one ViT-256 head")
+    pairs = [(j, i) for i in heads256 for j in heads4k]
+    r_dev, base = _region_and_background(hipt, region, scale, base, host_resize)
+    res = hierarchical_heatmaps(hipt, r_dev, offset=offset, scale=scale, alpha=alpha, cmap=cmap, w256=w256, pairs=pairs, base=base)
+    hs, ws = int(res["4k"].shape[1]), int(res["4k"].shape[2])
+    dev = res["4k"].device
+    canvas = torch.empty(((1 + len(heads256)) * hs, (1 + len(heads4k)) * ws, 3), dtype=torch.uint8, device=dev)
+    canvas[:hs, :ws] = H._device_image(H._as_array(base), dev)
+    for c, j in enumerate(heads4k):
+        canvas[:hs, (c + 1) * ws:(c + 2) * ws] = res["4k"][j]
+    for r, i in enumerate(heads256):
+        canvas[(r + 1) * hs:(r + 2) * hs, :ws] = res["256"][i]
+        for c in range(len(heads4k)):
+            canvas[(r + 1) * hs:(r + 2) * hs, (c + 1) * ws:(c + 2) * ws] = res["blend"][r * len(heads4k) + c]
+    return canvas
+
+
+def create_hierarchical_heatmaps_concat_select(region, hipt, output_dir, fname, offset=128, scale=4, alpha=0.5, cmap="coolwarm",
+                                               heads4k=(0, 5), heads256=(2,)):
+    """Saves ``hierarchical_heatmaps_concat_select``'s grid as ``{fname}_heatmap.png`` (the reference's name, :668) under
+    ``output_dir`` and returns the path.  The file is RGB; the reference's is the same layout with an opaque alpha channel."""
+    from PIL import Image
+    canvas = hierarchical_heatmaps_concat_select(hipt, region, heads4k=heads4k, heads256=heads256, offset=offset, scale=scale,
+                                                 alpha=alpha, cmap=cmap)
+    path = os.path.join(output_dir, "%s_heatmap.png" % fname)
+    Image.fromarray(canvas.cpu().numpy()).save(path)
+    return path

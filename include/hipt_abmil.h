@@ -36,8 +36,8 @@ extern "C" {
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
  * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) and the
- * tiling pair (hipt_point_polygon_test, hipt_tile_contours) were added later under the same number: additive, nothing existing
- * changed. */
+ * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair and hipt_patch_render were added later under the same
+ * number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -799,6 +799,28 @@ int hipt_hier_render(const double* pct4k, const double* pct256, int nh, int w_25
                      const uint8_t* base, const uint8_t* lut, int lut_n, double alpha, double w256, const int32_t* pairs, int npairs,
                      int use_threshold, double threshold, uint8_t* hm4k, uint8_t* hm256, uint8_t* hm_blend, uint8_t* hm256_thr,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Patch-level ViT-256 attention heat-maps (HIPT_4K/attention_visualization_utils.py:293-421 create_patch_heatmaps_indiv / _concat;
+ * DESIGN.md 24), for a batch of P patches of 256 x 256 pixels in one launch.
+ *   pct     float64 [P, 2, nh, 256]   hipt_hier_ranks (f = 16) of the [CLS] attention over the 16 x 16 tokens of each patch (layer 1)
+ *                                     and of its copy shifted by 16 pixels (layer 2)
+ *   patches uint8 [P, 256, 256, 3], lut uint8 [lut_n, 3]
+ * At pixel (y, x) of a patch, in float64 with every operation rounded on its own: u1 = pct[p, 0, i, (y / 16) * 16 + x / 16];
+ * layer 2 is present iff y >= offset and x >= offset, u2 = pct[p, 1, i, ((y - offset) / 16) * 16 + (x - offset) / 16];
+ *   score = (u1 + u2) / 200 where layer 2 is present, u1 / 100 elsewhere           (0 <= offset <= 256; at 256 nothing overlaps)
+ * hm shows score: colour = lut[min(trunc(score * lut_n), lut_n - 1)], pixel = the blend of hipt_hier_render with the patch.
+ * hm_thr (needs use_threshold) is hipt_hier_render's hm256_thr rule on score: the patch where score < threshold, the blend of entry
+ * trunc(0.95 * lut_n) where it is above, the uint8 wrapping sum of the patch and the blend of the threshold's own entry where equal.
+ * cols == 0: an output is [P, nh, 256, 256, 3].  cols > 0: it is a mosaic [P, ceil(nh / cols) * 256, cols * 256, 3] with head i at
+ * tile (i / cols, i % cols); the unused tiles of the last row are written 0.  Either output may be NULL, not both; they are 4-byte
+ * aligned like patches, distinct, and neither is patches.
+ * Envelope: P <= HIPT_PATCH_MAX_P, 1 <= nh <= HIPT_HIER_MAX_HEADS, 2 <= lut_n <= HIPT_HIER_MAX_LUT, else HIPT_E_UNSUPPORTED with nothing
+ * launched; 0 <= cols <= HIPT_HIER_MAX_HEADS; P = 0 returns HIPT_OK.  One launch on `stream`, no workspace, no atomics, no host read-back.
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_PATCH_MAX_P 1048576
+int hipt_patch_render(const double* pct, const uint8_t* patches, int P, int nh, const uint8_t* lut, int lut_n, int offset, double alpha,
+                      int use_threshold, double threshold, int cols, uint8_t* hm, uint8_t* hm_thr, void* stream);
 
 /* ----------------------------------------------------------------------------------
  * Patch coordinates from tissue contours (wsi_core/WholeSlideImage.py:357-372, 415-506; wsi_core/util_classes.py:53-111;
