@@ -59,6 +59,10 @@ _LAZY = {
     "pack_slide": ("tiling", "pack_slide"), "plan_contours": ("tiling", "plan_contours"),
     # Pillow's Image.resize of uint8 RGB images (the heat-maps' background, the ResNet routes' patch resize)
     "resize_u8": ("resize", "resize_u8"), "resize_table": ("resize", "resize_table"), "resize_patches": ("resize", "resize_patches"),
+    # Macenko stain normalisation of uint8 RGB images (extract_features_fp.py --use_transforms macenko)
+    "macenko_fit": ("macenko", "macenko_fit"), "macenko_apply": ("macenko", "macenko_apply"),
+    "macenko_normalize": ("macenko", "macenko_normalize"), "MacenkoNormalizer": ("macenko", "MacenkoNormalizer"),
+    "extract_slide_normalised": ("feature_store", "extract_slide_normalised"),
 }
 
 

@@ -193,6 +193,11 @@ SIGNATURES = {
     "hipt_tile_contours": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _i64, _p]),
     "hipt_resize_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hipt_resize_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _sz, _i, _p]),
+    "hipt_macenko_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hipt_macenko_fit": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _sz, _p]),
+    "hipt_macenko_apply": (_i, [_p, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "hipt_macenko_normalize": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    "hipt_macenko_keys": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -248,6 +248,45 @@ def extract_slide_augmented(model, batches: Iterable[Tuple[torch.Tensor, torch.T
     return _extract(model, batches, writers, run, coalesce)
 
 
+class NormalisedSlide(str):
+    """The ``.pt`` path ``extract_slide_normalised`` wrote (a ``str``), with ``fallbacks``: how many regions had no stain plane."""
+    fallbacks = 0
+
+
+def extract_slide_normalised(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], feat_dir: str, slide_id: str, coalesce: int = 8,
+                             reference_input: bool = True, **macenko_kw) -> str:
+    """``extract_features_fp.py --use_transforms macenko``: the loop of ``extract_slide`` with every (gathered) call
+    Macenko-normalised on the device (``macenko.macenko_normalize``) before it goes through ``model``.  Regions
+    must be raw uint8 RGB (the stain model is fitted to the bytes): float regions raise ``ValueError``.
+
+    ``reference_input=True`` feeds ``model`` what the reference's route feeds it: the planar float32 tensor ``normalised / 255``
+    in [0, 1], with no mean / std normalisation after it.  ``False`` feeds the normalised uint8 images, which then take the
+    model's usual eval transforms.  ``macenko_kw``: ``Io``, ``alpha``, ``beta``, ``target`` of ``macenko_normalize``.  An image's
+    normalisation does not depend on the call it shares, so the file is the same for every ``coalesce``.
+
+    Returns the ``.pt`` path as a ``NormalisedSlide``: a ``str`` whose attribute ``fallbacks`` is the number of regions that fell
+    back (no stain plane: passed on unchanged, as the reference's ``except`` does) -- counted on the device, read once after the
+    loop.  Nothing is kept outside the returned value."""
+    from .macenko import macenko_normalize
+
+    bad = set(macenko_kw) - {"Io", "alpha", "beta", "target"}
+    if bad:
+        raise TypeError(f"extract_slide_normalised: unknown arguments {sorted(bad)}")
+    counts = []
+
+    def run(regions, first):
+        if regions.dtype != torch.uint8:
+            raise ValueError(f"extract_slide_normalised: regions must be raw uint8 RGB (got {regions.dtype}); the reference normalises "
+                             f"the image before any other transform")
+        x, status = macenko_normalize(regions, out_dtype=torch.float32 if reference_input else torch.uint8, return_status=True, **macenko_kw)
+        counts.append(status.sum())
+        return [model(x)]
+
+    path = NormalisedSlide(_extract(model, batches, [FeatureWriter(feat_dir, slide_id)], run, coalesce)[0])
+    path.fallbacks = int(torch.stack(counts).sum()) if counts else 0
+    return path
+
+
 def _is_resnet(model) -> bool:
     from .resnet18 import ResNet18_Baseline
     from .resnet_custom import ResNet_Baseline

@@ -36,7 +36,7 @@ extern "C" {
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
  * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) and the
- * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair and hipt_patch_render were added later under the same
+ * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair, hipt_patch_render and the hipt_macenko_* five were added later under the same
  * number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
@@ -903,6 +903,51 @@ enum { HIPT_RESIZE_AUTO = 0, HIPT_RESIZE_GENERAL = 1, HIPT_RESIZE_FUSED = 2 };
 size_t hipt_resize_workspace_bytes(int n, int in_h, int in_w, int out_h, int out_w, int route);
 int hipt_resize_u8(const uint8_t* src, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* kx, const int32_t* bx, int ksize_x,
                    const int32_t* ky, const int32_t* by, int ksize_y, uint8_t* dst, void* ws, size_t ws_bytes, int route, void* stream);
+
+/* ----------------------------------------------------------------------------------
+ * Macenko stain normalisation of 8-bit RGB images (extract_features_fp.py:41-60, --use_transforms macenko: torchstain's
+ * MacenkoNormalizer, torch backend).  Added under ABI 6: additive.
+ *
+ * src: R images of h x w pixels, uint8, planar [R, 3, h, w] (interleaved = 0) or interleaved [R, h, w, 3], contiguous.  Per image:
+ *   OD = -log((I + 1) / Io) (float32, a 256-entry table); tissue = the pixels with no channel OD < beta, n of them;
+ *   E = the eigenvectors (e1, e2) of the two largest eigenvalues, ascending, of the unbiased covariance of OD over the tissue (sums and
+ *       Jacobi in float64), each with its largest-magnitude component made positive;
+ *   phi = atan2(OD . e2, OD . e1) over the tissue; minPhi, maxPhi = its order statistics of rank 1 + round_half_even(0.01 q (n - 1)),
+ *       q = alpha and 100 - alpha -- exact order statistics (three histogram passes over the order-preserving integer image of the
+ *       float32 key, -0.0 equal to +0.0), never an interpolation;
+ *   vMin = E [cos minPhi, sin minPhi], vMax likewise; HE [3, 2] = [vMin, vMax] if vMin[0] > vMax[0], else [vMax, vMin];
+ *   C [2] = (HE^T HE)^-1 HE^T OD for ALL pixels; maxC[j] = the order statistic of C[j] at q = 99 over the h w pixels;
+ *   out = trunc(min(Io exp(-(ref_HE (C ref_maxC / maxC))), 255)).
+ * status[r] (int32): 0, or 1 = fallback: n < 2, a non-finite entry of the covariance, HE or maxC, maxC[j] <= 0, or a select that
+ * ended on an empty bin.  HE and maxC of a fallback image are written as zeros; apply copies its pixels through unchanged.  Nothing is
+ * read back to decide it.  An image's HE, maxC, status and output bytes do not depend on R, on its place in the batch or on the
+ * other images, and are the same from run to run (float64 sums in a fixed order, integer atomics only).
+ *
+ * hipt_macenko_fit: HE float32 [R, 3, 2], maxC float32 [R, 2], status int32 [R]; aux (NULL, or float32 [R, 16]) receives per image
+ *   e1[3], e2[3], minPhi, maxPhi, the 2 x 3 matrix (HE^T HE)^-1 HE^T, then n and status as int32 bit patterns.
+ * hipt_macenko_apply: the last line above for given HE / maxC / status (status NULL: all 0) and a target ref_HE float32 [3, 2] /
+ *   ref_maxC float32 [2] on the device (NULL: torchstain's constants).  dst: uint8 in src's layout (dst_f32 = 0), or float32 planar
+ *   [R, 3, h, w] equal to uint8 / 255 (dst_f32 = 1): the tensor the reference's route hands its model.  No workspace.
+ * hipt_macenko_normalize: fit, then apply, on `stream`; HE / maxC / status may be NULL (they then live in the workspace).
+ * hipt_macenko_keys: the float32 keys of every pixel as the passes compute them, for tests: keys [R, 3, h w] = phi, C[0], C[1] from
+ *   aux's E and matrix, tissue uint8 [R, h w].
+ * ws: hipt_macenko_workspace_bytes(R, h, w) bytes (0 for a geometry outside the envelope), 256-byte aligned; it holds the table,
+ * 128 bytes, 16 KiB of histograms and at most 1024 slabs of 10 doubles per image -- nothing per pixel -- and carries nothing from
+ * call to call.  HIPT_E_BADARG before any launch for R < 1, h w < 1, Io <= 0, alpha outside (0, 50), beta < 0, a missing pointer,
+ * dst == src; HIPT_E_UNSUPPORTED for h w >= 2^31; HIPT_E_WORKSPACE for a short or misaligned ws.  16-byte aligned src / dst and
+ * h w % 16 == 0 take the 16-byte loads and stores; anything else is read and written byte by byte, with the same results.
+ * No allocation, no host synchronisation, no float atomics: the launches can be captured into a graph.
+ * ---------------------------------------------------------------------------------- */
+size_t hipt_macenko_workspace_bytes(int R, int h, int w);
+int hipt_macenko_fit(const uint8_t* src, int interleaved, int R, int h, int w, double Io, double alpha, double beta, float* HE, float* maxC,
+                     int32_t* status, float* aux, void* ws, size_t ws_bytes, void* stream);
+int hipt_macenko_apply(const uint8_t* src, int interleaved, int R, int h, int w, double Io, const float* HE, const float* maxC,
+                       const int32_t* status, const float* ref_HE, const float* ref_maxC, void* dst, int dst_f32, void* stream);
+int hipt_macenko_normalize(const uint8_t* src, int interleaved, int R, int h, int w, double Io, double alpha, double beta,
+                           const float* ref_HE, const float* ref_maxC, void* dst, int dst_f32, float* HE, float* maxC, int32_t* status,
+                           void* ws, size_t ws_bytes, void* stream);
+int hipt_macenko_keys(const uint8_t* src, int interleaved, int R, int h, int w, double Io, double beta, const float* aux, float* keys,
+                      uint8_t* tissue, void* stream);
 
 #ifdef __cplusplus
 }
