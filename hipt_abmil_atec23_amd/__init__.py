@@ -63,6 +63,11 @@ _LAZY = {
     "macenko_fit": ("macenko", "macenko_fit"), "macenko_apply": ("macenko", "macenko_apply"),
     "macenko_normalize": ("macenko", "macenko_normalize"), "MacenkoNormalizer": ("macenko", "MacenkoNormalizer"),
     "extract_slide_normalised": ("feature_store", "extract_slide_normalised"),
+    # the tissue mask of WholeSlideImage.segmentTissue (saturation, median, threshold / Otsu, closing) and its contour filter
+    "tissue_mask": ("segment", "tissue_mask"), "segment_tissue": ("segment", "segment_tissue"),
+    "saturation_u8": ("segment", "saturation_u8"), "median_blur_u8": ("segment", "median_blur_u8"),
+    "otsu_threshold": ("segment", "otsu_threshold"), "morph_close_u8": ("segment", "morph_close_u8"),
+    "contour_area": ("segment", "contour_area"), "filter_contours": ("segment", "filter_contours"),
 }
 
 

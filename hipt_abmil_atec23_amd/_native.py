@@ -90,6 +90,7 @@ PATCH_MAX_P = 1 << 20                                                           
 TILE_BASIC, TILE_CENTER, TILE_FOUR_PT, TILE_FOUR_PT_HARD = 0, 1, 2, 3             # HIPT_TILE_*
 TILING_COORD_BOUND, TILING_EDGE_CHUNK, TILING_TILE, TILING_CONTOUR_INTS = 1 << 30, 1024, 256, 9   # HIPT_TILING_*
 RESIZE_ROUTE_AUTO, RESIZE_ROUTE_GENERAL, RESIZE_ROUTE_FUSED, RESIZE_MAX_KSIZE = 0, 1, 2, 512      # HIPT_RESIZE_*
+SEGMENT_MAX_MEDIAN, SEGMENT_MAX_CLOSE = 15, 128                                                   # HIPT_SEGMENT_MAX_*
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -198,6 +199,12 @@ SIGNATURES = {
     "hipt_macenko_apply": (_i, [_p, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _i, _p]),
     "hipt_macenko_normalize": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "hipt_macenko_keys": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p]),
+    "hipt_segment_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hipt_segment_mask": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "hipt_segment_saturation": (_i, [_p, _i, _i, _i, _p, _p]),
+    "hipt_segment_median": (_i, [_p, _i, _i, _i, _p, _p]),
+    "hipt_segment_otsu": (_i, [_p, _i, _i, _p, _p, _p]),
+    "hipt_segment_close": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -36,7 +36,7 @@ extern "C" {
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
  * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) and the
- * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair, hipt_patch_render and the hipt_macenko_* five were added later under the same
+ * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair, hipt_patch_render, the hipt_macenko_* five and the hipt_segment_* six were added later under the same
  * number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
@@ -948,6 +948,43 @@ int hipt_macenko_normalize(const uint8_t* src, int interleaved, int R, int h, in
                            void* ws, size_t ws_bytes, void* stream);
 int hipt_macenko_keys(const uint8_t* src, int interleaved, int R, int h, int w, double Io, double beta, const float* aux, float* keys,
                       uint8_t* tissue, void* stream);
+
+/* ----------------------------------------------------------------------------------
+ * Tissue segmentation mask: the pixel stages of WholeSlideImage.segmentTissue (wsi_core/WholeSlideImage.py:111-203) up to the binary
+ * mask.  Added under ABI 6: additive.  Contour tracing (cv2.findContours) stays on the host.
+ *
+ * src: one uint8 image [h, w, channels], interleaved, channels 3 (RGB) or 4 (RGBA; the fourth channel is ignored).  Every plane below
+ * is uint8 [h, w], contiguous.  The definitions, restated from OpenCV's published implementation:
+ *   saturation  v = max(r, g, b), d = v - min(r, g, b), S = (d * sdiv[v] + 2048) >> 12; sdiv[0] = 0, sdiv[v] = rint(255 * 4096 / v)
+ *   median      the exact median of the mthresh x mthresh window, indices clamped to the image; mthresh odd, 1 (a copy) ..
+ *               HIPT_SEGMENT_MAX_MEDIAN
+ *   Otsu        256 integer counts of the median plane; then, in float64 and in this order: scale = 1 / (h w), mu = (sum i hist[i]) scale;
+ *               for i = 0 .. 255: p = hist[i] scale; mu1 *= q1; q1 += p; q2 = 1 - q1; skip i if min(q1, q2) < FLT_EPSILON or
+ *               max(q1, q2) > 1 - FLT_EPSILON; mu1 = (mu1 + i p) / q1; mu2 = (mu - q1 mu1) / q2; sigma = q1 q2 (mu1 - mu2)^2; the first i
+ *               with a strictly larger sigma is the threshold (0 if there is none)
+ *   threshold   mask = med > t ? sthresh_up : 0; t = sthresh, or with use_otsu the value above, which never leaves the device
+ *   closing     dilate, then erode, with a close x close rectangle, anchor close / 2: both read offsets -(close / 2) .. close - 1 -
+ *               close / 2 on each axis; outside the image counts 0 for the dilation and 255 for the erosion; close = 0: no closing;
+ *               close <= HIPT_SEGMENT_MAX_CLOSE and may exceed the image's sides
+ * hipt_segment_mask: all of it on `stream`.  sat, med (planes) and thresh (int32 [1], the threshold used) may be NULL.
+ * Stage entries: hipt_segment_saturation (src image -> sat); hipt_segment_median (src plane -> dst, window ksize);
+ * hipt_segment_otsu (src plane -> hist int32 [256], thresh int32 [1]); hipt_segment_close (src plane -> dst; grey-scale, any bytes).
+ * ws: hipt_segment_workspace_bytes(h, w, close) bytes (0 outside the envelope), 256-byte aligned: the histogram, the threshold, the
+ * median plane and, for close > 0, two planes; hipt_segment_close takes the same size.  Nothing is carried from call to call.
+ * HIPT_E_BADARG before any launch for a missing pointer, two buffers that are the same, h w < 1 or >= 2^31, channels not 3 / 4,
+ * sthresh / sthresh_up outside 0 .. 255, mthresh < 1, close < 0; HIPT_E_UNSUPPORTED for an even mthresh, mthresh >
+ * HIPT_SEGMENT_MAX_MEDIAN, close > HIPT_SEGMENT_MAX_CLOSE; HIPT_E_WORKSPACE for a short or misaligned ws.
+ * No allocation, no host synchronisation, integer atomics only: the launches can be captured into a graph.
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_SEGMENT_MAX_MEDIAN 15
+#define HIPT_SEGMENT_MAX_CLOSE 128
+size_t hipt_segment_workspace_bytes(int h, int w, int close);
+int hipt_segment_mask(const uint8_t* src, int h, int w, int channels, int sthresh, int sthresh_up, int mthresh, int close, int use_otsu,
+                      uint8_t* mask, uint8_t* sat, uint8_t* med, int32_t* thresh, void* ws, size_t ws_bytes, void* stream);
+int hipt_segment_saturation(const uint8_t* src, int h, int w, int channels, uint8_t* sat, void* stream);
+int hipt_segment_median(const uint8_t* src, int h, int w, int ksize, uint8_t* dst, void* stream);
+int hipt_segment_otsu(const uint8_t* src, int h, int w, int32_t* hist, int32_t* thresh, void* stream);
+int hipt_segment_close(const uint8_t* src, int h, int w, int close, uint8_t* dst, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
