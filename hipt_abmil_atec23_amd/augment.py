@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from . import _frontend as F
 from . import _native as N
 
 HFLIP, VFLIP, AFFINE, BLUR = 1, 2, 4, 8                       # hipt_augment_params.flags
@@ -187,19 +188,6 @@ def draw_region_params(policy: str, seed: int, slide_id: str, k: int, first: int
     return out
 
 
-def _layout(regions: torch.Tensor) -> Tuple[bool, int, int]:
-    if regions.dtype != torch.uint8:
-        raise ValueError(f"augmentation takes raw uint8 RGB regions (got {regions.dtype}); the reference augments before "
-                         f"eval_transforms, so normalised float input cannot be augmented faithfully")
-    if regions.dim() != 4:
-        raise ValueError(f"regions must be [R,3,rows,cols] or [R,rows,cols,3], got {tuple(regions.shape)}")
-    if regions.shape[-1] == 3 and regions.shape[1] != 3:  # (HIPT_4K's test: [R,3,rows,3] counts as planar)
-        return True, int(regions.shape[1]), int(regions.shape[2])
-    if regions.shape[1] == 3:
-        return False, int(regions.shape[2]), int(regions.shape[3])
-    raise ValueError(f"regions must be [R,3,rows,cols] or [R,rows,cols,3], got {tuple(regions.shape)}")
-
-
 def pack_records(params: Sequence[RegionParams]) -> torch.Tensor:
     """the parameter records as a host uint8 tensor (pinned: the device copy is asynchronous)"""
     arr = (AugmentParams * len(params))(*[p.record() for p in params])
@@ -210,7 +198,7 @@ def pack_records(params: Sequence[RegionParams]) -> torch.Tensor:
 
 def augment_regions(regions_u8: torch.Tensor, params: Sequence[RegionParams], out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``regions_u8`` (uint8 on a HIP device, planar or interleaved) with region i transformed by ``params[i]``; same layout."""
-    interleaved, rows, cols = _layout(regions_u8)
+    interleaved, rows, cols = F.rgb_layout("augment_regions", regions_u8, dims=(4,))
     N.require_cuda(regions_u8, "augment_regions")
     n = regions_u8.shape[0]
     if len(params) != n:
@@ -218,15 +206,12 @@ def augment_regions(regions_u8: torch.Tensor, params: Sequence[RegionParams], ou
     if any(p.blur_sigma is not None for p in params) and rows < 2:
         raise ValueError("blur: reflect padding needs at least 2 rows")
     src = regions_u8.contiguous()
-    dst = torch.empty_like(src) if out is None else out
-    if dst.shape != src.shape or dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.device != src.device:
-        raise ValueError("out must be a contiguous uint8 tensor shaped like the regions, on their device")
+    dev = src.device
+    dst = F.check_out("augment_regions", out, src.shape, torch.uint8, dev, not_alias=(src,))   # (the kernel reads neighbours: never in place)
     if n == 0:
         return dst
-    dev = src.device
     rec = pack_records(params).to(dev, non_blocking=True)
-    wsb = N.lib().hipt_augment_workspace_bytes(n, rows, cols)
-    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
+    ws, _ = F.scratch("hipt_augment_workspace_bytes", n, rows, cols, dev=dev)
     N.call("hipt_augment_regions", N.ptr(src), int(interleaved), n, rows, cols, N.ptr(rec), N.ptr(dst), N.ptr(ws), ws.numel(),
            N.stream_ptr(dev))
     cur = torch.cuda.current_stream(dev)
@@ -248,5 +233,5 @@ class RegionAugment:
         return draw_region_params(self.policy, self.seed, slide_id, k, first, count, rows, cols)
 
     def __call__(self, regions: torch.Tensor, slide_id: str = "", k: int = 1, first: int = 0) -> torch.Tensor:
-        _, rows, cols = _layout(regions)
+        _, rows, cols = F.rgb_layout("RegionAugment", regions, dims=(4,))
         return augment_regions(regions, self.params(slide_id, k, first, regions.shape[0], rows, cols))

@@ -28,10 +28,10 @@ import math
 
 import numpy as np
 
+from . import _frontend as F
 from . import _native as N
 
 LUT_ENTRIES = N.HEATMAP_LUT_ENTRIES
-_lut_cache = {}   # (colormap name, device) -> uint8 [258, 3] tensor; (name, None) -> the host array
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -63,9 +63,9 @@ def table_index(overlay) -> np.ndarray:
 def to_percentiles(scores):
     """``scipy.stats.rankdata(scores, 'average') / len(scores) * 100`` (wsi_core/wsi_utils.py:124-127): in numpy for numpy
     scores; a device tensor is ranked on the device (``hipt_score_counts``) and a float64 device tensor comes back, the same bits."""
-    if _is_tensor(scores):
-        _check_no_nan("to_percentiles", scores=scores)
-        s = _as_f64(scores, _resolve_device(None, (scores,)))
+    if F.is_tensor(scores):
+        F.check_no_nan("to_percentiles", scores=scores)
+        s = _as_f64(scores, F.resolve_device("heatmap", None, (scores,)))
         return _counts_call(s, s, N.PCT_RANKDATA, pct=True)[2]
     s = np.asarray(scores, dtype=np.float64).reshape(-1)
     n = len(s)
@@ -115,14 +115,6 @@ def patch_values(scores, *, binarize=False, thresh=0.5, convert_to_percentiles=F
 # ------------------------------------------------------------------------------------------------------------------------------
 # argument checks (all before any native call)
 # ------------------------------------------------------------------------------------------------------------------------------
-def _is_tensor(a) -> bool:
-    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
-
-
-def _as_array(a):
-    return a if a is None or _is_tensor(a) else np.asarray(a)
-
-
 def _check_geometry(scores, coords, patch_size, scale, region_size):
     """Shapes, dtypes and sizes; returns ``(N, w, h)``."""
     if scores.ndim not in (1, 2):   # (a 2-D array is flattened, as the reference does)
@@ -148,13 +140,6 @@ def _check_geometry(scores, coords, patch_size, scale, region_size):
     return n, w, h
 
 
-def _check_image(name, a, shape, dtype_names):
-    if a is None:
-        return
-    if tuple(a.shape) != shape or str(a.dtype).replace("torch.", "") not in dtype_names:
-        raise ValueError(f"heatmap: {name} must be {dtype_names[0]} {list(shape)}, got {a.dtype} {list(a.shape)}")
-
-
 def _check_values(xy_min, xy_max, scores_finite):
     if xy_min < 0:
         raise ValueError("heatmap: negative coordinates (coords are relative to the region's top-left corner; the reference's "
@@ -165,28 +150,11 @@ def _check_values(xy_min, xy_max, scores_finite):
         raise ValueError("heatmap: scores contain NaN or infinity")
 
 
-def _resolve_device(device, tensors):
-    import torch
-    refs = [t for t in tensors if _is_tensor(t)]
-    if refs:
-        dev = refs[0].device if device is None else torch.device(device)
-    else:
-        dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"heatmap: device {dev}; hipt_abmil_atec23_amd runs only on a HIP device (there is deliberately no CPU path)")
-    if not torch.cuda.is_available():
-        raise RuntimeError("heatmap: no HIP device; hipt_abmil_atec23_amd runs only on a HIP device (there is deliberately no CPU path)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    N.same_device("heatmap", dev, *refs)
-    return dev
-
-
 # ------------------------------------------------------------------------------------------------------------------------------
 # score ranks on the device (csrc/percentile.hip)
 # ------------------------------------------------------------------------------------------------------------------------------
 def _check_one_device(what, arrays):
-    devs = sorted({str(a.device) for a in arrays if _is_tensor(a)})
+    devs = sorted({str(a.device) for a in arrays if F.is_tensor(a)})
     if len(devs) > 1:
         raise ValueError(f"{what}: scores and reference scores are on different devices ({', '.join(devs)})")
 
@@ -194,25 +162,8 @@ def _check_one_device(what, arrays):
 def _as_f64(a, dev):
     """A flat, contiguous float64 tensor on ``dev`` (float32 scores widen exactly, as numpy's comparison promotes them)."""
     import torch
-    t = a if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    t = a if F.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
     return t.detach().to(dev, torch.float64).reshape(-1).contiguous()
-
-
-def _check_no_nan(what, **named):
-    """``ValueError`` on a NaN; numpy arrays are looked at on the host, device tensors with one synchronisation, which is left
-    out while the stream is being captured into a graph (the kernel then counts a NaN as neither below nor above anything)."""
-    import torch
-    for name, a in named.items():
-        if a is None:
-            continue
-        if _is_tensor(a):
-            if a.is_cuda and torch.cuda.is_current_stream_capturing():
-                continue
-            bad = bool(torch.isnan(a).any()) if a.numel() else False
-        else:
-            bad = bool(np.isnan(np.asarray(a, dtype=np.float64)).any())
-        if bad:
-            raise ValueError(f"{what}: {name} contain NaN")
 
 
 def _counts_call(q, ref, mode, *, counts=False, pct=False):
@@ -237,17 +188,17 @@ def _check_score_args(what, scores, ref_scores):
     if nref >= 2 ** 31:
         raise ValueError(f"{what}: {nref} reference scores; the counts are int32")
     _check_one_device(what, (scores, ref_scores))
-    _check_no_nan(what, scores=scores, ref_scores=ref_scores)
-    return _resolve_device(None, (scores, ref_scores))
+    F.check_no_nan(what, scores=scores, ref_scores=ref_scores)
+    return F.resolve_device("heatmap", None, (scores, ref_scores))
 
 
 def score_counts(q, ref):
     """``(less, leq)``, int32 ``[len(q)]``: how many values of ``ref`` are smaller than each ``q[i]``, and how many are smaller or
     equal (IEEE comparisons in float64).  Numpy in, numpy out; device tensors in, tensors out."""
-    q, ref = _as_array(q), _as_array(ref)
+    q, ref = F.as_array(q), F.as_array(ref)
     dev = _check_score_args("score_counts", q, ref)
     less, leq, _ = _counts_call(_as_f64(q, dev), _as_f64(ref, dev), N.PCT_OF_SCORE, counts=True)
-    if _is_tensor(q):
+    if F.is_tensor(q):
         return less, leq
     return less.cpu().numpy(), leq.cpu().numpy()
 
@@ -265,13 +216,13 @@ def score2percentile(scores, ref_scores, out_dtype=None):
     ``out_dtype`` (``torch.float32`` reproduces the reference's storage, which assigns into a float32 array).  ``scores`` as a
     numpy array: a numpy array comes back (copied from the device, not recomputed); as a device tensor: a tensor.  ``ref_scores``
     may be either kind."""
-    scores, ref_scores = _as_array(scores), _as_array(ref_scores)
+    scores, ref_scores = F.as_array(scores), F.as_array(ref_scores)
     dev = _check_score_args("score2percentile", scores, ref_scores)
     out = _counts_call(_as_f64(scores, dev), _as_f64(ref_scores, dev), N.PCT_OF_SCORE, pct=True)[2].reshape(tuple(scores.shape))
     dtype = _torch_dtype(out_dtype)
     if dtype is not None:
         out = out.to(dtype)
-    return out if _is_tensor(scores) else out.cpu().numpy()
+    return out if F.is_tensor(scores) else out.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -280,7 +231,7 @@ def score2percentile(scores, ref_scores, out_dtype=None):
 def _host_inputs(scores, coords, patch_size, scale, *, binarize, thresh, convert_to_percentiles):
     """Numpy inputs: ``(xy int32 [N, 2], v float64 [N], paint uint8 [N])`` with the value checks done, or None when an input
     is a device tensor (``_device_inputs`` then works on the device)."""
-    if _is_tensor(scores) or _is_tensor(coords):
+    if F.is_tensor(scores) or F.is_tensor(coords):
         return None
     xy, _, _ = scaled_geometry(coords, patch_size, scale)
     s = np.asarray(scores, dtype=np.float64).reshape(-1)
@@ -296,8 +247,8 @@ def _device_inputs(host, scores, coords, patch_size, scale, dev, *, binarize, th
     _, pw, ph = scaled_geometry(np.zeros((0, 2), dtype=np.int64), patch_size, scale)
     if host is not None:
         return tuple(torch.from_numpy(a).to(dev) for a in host) + (pw, ph)
-    s = (scores if _is_tensor(scores) else torch.from_numpy(np.asarray(scores))).to(dev, torch.float64).reshape(-1).contiguous()
-    c = (coords if _is_tensor(coords) else torch.from_numpy(np.asarray(coords))).to(dev)
+    s = (scores if F.is_tensor(scores) else torch.from_numpy(np.asarray(scores))).to(dev, torch.float64).reshape(-1).contiguous()
+    c = (coords if F.is_tensor(coords) else torch.from_numpy(np.asarray(coords))).to(dev)
     sc = np.broadcast_to(np.asarray(scale, dtype=np.float64), (2,))
     c = c.to(torch.float64)
     xyf = torch.ceil(torch.stack([c[:, 0] * float(sc[0]), c[:, 1] * float(sc[1])], dim=1))   # (scalars: no host-to-device copy)
@@ -313,40 +264,14 @@ def _device_inputs(host, scores, coords, patch_size, scale, dev, *, binarize, th
     return xyf.to(torch.int32).contiguous(), v.contiguous(), keep.to(torch.uint8), pw, ph
 
 
-def _device_image(a, dev):
-    """A mask (bool) or canvas (uint8) as contiguous bytes on ``dev``."""
-    import torch
-    if a is None:
-        return None
-    t = (a if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev).contiguous()
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
-
-
-def _lut_host(cmap):
-    if not isinstance(cmap, str):
-        return colour_table(cmap)
-    if (cmap, None) not in _lut_cache:
-        _lut_cache[(cmap, None)] = colour_table(cmap)
-    return _lut_cache[(cmap, None)]
-
-
-def _lut_on(cmap, table, dev):
-    """The table on ``dev``; named colormaps are copied there once (so a later call can be captured into a graph)."""
-    import torch
-    if not isinstance(cmap, str):
-        return torch.from_numpy(table).to(dev)
-    if (cmap, str(dev)) not in _lut_cache:
-        _lut_cache[(cmap, str(dev))] = torch.from_numpy(table).to(dev)
-    return _lut_cache[(cmap, str(dev))]
-
-
 def _workspace(n, pw, ph, w, h, dev):
-    import torch
-    need = int(N.lib().hipt_heatmap_workspace_bytes(n, pw, ph, w, h))
+    """The scratch of the per-tile patch lists (``_frontend.scratch``); the library sizes it 0 for a call beyond the kernel's envelope.
+    It keeps its name and signature because tests/test_gpu_workspace_guard.py replaces it with a fenced buffer."""
+    ws, need = F.scratch("hipt_heatmap_workspace_bytes", n, pw, ph, w, h, dev=dev)
     if n and not need:
         raise ValueError(f"heatmap: {n} patches of {pw} x {ph} on a {w} x {h} canvas are beyond the kernel's envelope "
                          f"(patches x tiles per patch < 2^31)")
-    return torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    return ws
 
 
 def heatmap_overlay(scores, coords, patch_size, scale, region_size, *, binarize=False, thresh=0.5, convert_to_percentiles=False,
@@ -355,11 +280,11 @@ def heatmap_overlay(scores, coords, patch_size, scale, region_size, *, binarize=
     score / 100 where it reaches the threshold, else 0; 1 or 0 and the mean rounded half to even when ``binarize``), and the
     number of covering patches.  Numpy in, numpy out; device tensors in, tensors out."""
     import torch
-    scores, coords = _as_array(scores), _as_array(coords)
+    scores, coords = F.as_array(scores), F.as_array(coords)
     n, w, h = _check_geometry(scores, coords, patch_size, scale, region_size)
     how = dict(binarize=binarize, thresh=thresh, convert_to_percentiles=convert_to_percentiles)
     host = _host_inputs(scores, coords, patch_size, scale, **how)
-    dev = _resolve_device(device, (scores, coords))
+    dev = F.resolve_device("heatmap", device, (scores, coords))
     with torch.cuda.device(dev):
         xy, v, paint, pw, ph = _device_inputs(host, scores, coords, patch_size, scale, dev, **how)
         ws = _workspace(n, pw, ph, w, h, dev)
@@ -367,7 +292,7 @@ def heatmap_overlay(scores, coords, patch_size, scale, region_size, *, binarize=
         count = torch.empty((h, w), dtype=torch.int32, device=dev)
         N.call("hipt_heatmap_overlay", N.ptr(xy), N.ptr(v), N.ptr(paint), n, pw, ph, w, h, int(bool(binarize)), N.ptr(overlay),
                N.ptr(count), None, N.ptr(ws), ws.numel(), N.stream_ptr(dev))
-    if _is_tensor(scores):
+    if F.is_tensor(scores):
         return overlay, count
     return overlay.cpu().numpy(), count.cpu().numpy()
 
@@ -386,28 +311,28 @@ def render_heatmap(scores, coords, patch_size, scale, region_size, *, canvas=Non
     if blur:
         raise NotImplementedError("render_heatmap: blur=True is not supported (cv2's fixed-point uint8 Gaussian blur cannot be "
                                   "reproduced without cv2; DESIGN.md 14)")
-    scores, coords, mask, canvas = _as_array(scores), _as_array(coords), _as_array(mask), _as_array(canvas)
+    scores, coords, mask, canvas = F.as_array(scores), F.as_array(coords), F.as_array(mask), F.as_array(canvas)
     n, w, h = _check_geometry(scores, coords, patch_size, scale, region_size)
-    _check_image("mask", mask, (h, w), ("bool",))
-    _check_image("canvas", canvas, (h, w, 3), ("uint8",))
+    F.check_image("heatmap", "mask", mask, (h, w), ("bool",))
+    F.check_image("heatmap", "canvas", canvas, (h, w, 3), ("uint8",))
     alpha = float(alpha)
     if math.isnan(alpha):
         raise ValueError("heatmap: alpha is NaN")
-    table = _lut_host(cmap)
+    table = F.table_host(colour_table, cmap)
     how = dict(binarize=binarize, thresh=thresh, convert_to_percentiles=convert_to_percentiles)
     host = _host_inputs(scores, coords, patch_size, scale, **how)
-    dev = _resolve_device(device, (scores, coords, mask, canvas))
+    dev = F.resolve_device("heatmap", device, (scores, coords, mask, canvas))
     with torch.cuda.device(dev):
         xy, v, paint, pw, ph = _device_inputs(host, scores, coords, patch_size, scale, dev, **how)
-        lut = _lut_on(cmap, table, dev)
-        mask_d = _device_image(mask, dev)
-        canvas_d = _device_image(canvas, dev)
+        lut = F.table_on(colour_table, cmap, table, dev)
+        mask_d = F.to_device(mask, dev)
+        canvas_d = F.to_device(canvas, dev)
         ws = _workspace(n, pw, ph, w, h, dev)
         img = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
         overlay = torch.empty((h, w), dtype=torch.float64, device=dev) if return_overlay else None
         N.call("hipt_heatmap_render", N.ptr(xy), N.ptr(v), N.ptr(paint), n, pw, ph, w, h, int(bool(binarize)), N.ptr(mask_d),
                N.ptr(canvas_d), N.ptr(lut), alpha, N.ptr(img), N.ptr(overlay), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
-    if not _is_tensor(scores):
+    if not F.is_tensor(scores):
         img = img.cpu().numpy()
         overlay = overlay.cpu().numpy() if return_overlay else None
     return (img, overlay) if return_overlay else img
@@ -430,13 +355,13 @@ def sample_rois(scores, coords, k=5, mode="range_sample", seed=1, score_start=0.
     in.  As in the reference, an empty window of ``range_sample`` yields index -1: the last patch."""
     if mode not in ("range_sample", "topk", "reverse_topk"):
         raise NotImplementedError(f"sample_rois: mode {mode!r}")
-    scores, coords = _as_array(scores), _as_array(coords)
+    scores, coords = F.as_array(scores), F.as_array(coords)
     if scores.ndim == 2:
         scores = scores.flatten()
     scores = to_percentiles(scores)
-    if _is_tensor(scores):
+    if F.is_tensor(scores):
         scores = scores.cpu().numpy()
-    if _is_tensor(coords):
+    if F.is_tensor(coords):
         coords = coords.cpu().numpy()
     if top_left is not None and bot_right is not None:
         scores, coords = screen_coords(scores, coords, top_left, bot_right)
@@ -461,7 +386,7 @@ def compute_from_batches(model, feature_extractor, batches, clam_pred=None, ref_
     import torch
     out_dtype = _torch_dtype(out_dtype)
     if ref_scores is not None:
-        ref_scores = _as_array(ref_scores)
+        ref_scores = F.as_array(ref_scores)
         _check_score_args("compute_from_batches", None, ref_scores)   # (the reference scores are looked at once, not per batch)
     ref = None
     all_scores, all_coords = [], []
@@ -477,10 +402,10 @@ def compute_from_batches(model, feature_extractor, batches, clam_pred=None, ref_
             if ref_scores is not None:
                 if ref is None or ref.device != a.device:
                     _check_one_device("compute_from_batches", (a, ref_scores))
-                    ref = _as_f64(ref_scores, _resolve_device(None, (a, ref_scores)))
-                _check_no_nan("compute_from_batches", scores=a)
+                    ref = _as_f64(ref_scores, F.resolve_device("heatmap", None, (a, ref_scores)))
+                F.check_no_nan("compute_from_batches", scores=a)
                 a = _counts_call(_as_f64(a, ref.device), ref, N.PCT_OF_SCORE, pct=True)[2].reshape(-1, 1).to(out_dtype)
-        c = coords.cpu().numpy() if _is_tensor(coords) else np.asarray(coords)
+        c = coords.cpu().numpy() if F.is_tensor(coords) else np.asarray(coords)
         if on_batch is not None:
             on_batch(a, c, features)
         all_scores.append(a)

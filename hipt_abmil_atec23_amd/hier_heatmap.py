@@ -22,12 +22,11 @@ import os
 
 import numpy as np
 
+from . import _frontend as F
 from . import _native as N
-from . import heatmap as H
 
 SCALES = (1, 2, 4, 8, 16)
 PICTURES = ("4k", "256", "blend", "256th")
-_table_cache = {}   # (colormap name, device or None) -> the table
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -88,22 +87,15 @@ def colour_table_n(cmap="coolwarm") -> np.ndarray:
     return np.ascontiguousarray((rgba * 255)[:, :3].astype(np.uint8))
 
 
-def _table(cmap, dev):
-    """The colour table of ``cmap`` (a name, a matplotlib colormap or a uint8 ``[N, 3]`` array) on ``dev``; named ones are copied
-    there once, so that a later call can be captured into a graph."""
-    import torch
-    if isinstance(cmap, str):
-        if (cmap, None) not in _table_cache:
-            _table_cache[(cmap, None)] = colour_table_n(cmap)
-        if (cmap, str(dev)) not in _table_cache:
-            _table_cache[(cmap, str(dev))] = torch.from_numpy(_table_cache[(cmap, None)]).to(dev)
-        return _table_cache[(cmap, str(dev))]
-    if H._is_tensor(cmap) or isinstance(cmap, np.ndarray):
-        t = cmap if H._is_tensor(cmap) else torch.from_numpy(np.ascontiguousarray(cmap))
-        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != 3 or not 2 <= t.shape[0] <= N.HIER_MAX_LUT:
-            raise ValueError(f"hier_heatmap: a colour table is uint8 [N, 3] with 2 <= N <= {N.HIER_MAX_LUT}, got {t.dtype} {list(t.shape)}")
-        return t.to(dev).contiguous()
-    return torch.from_numpy(colour_table_n(cmap)).to(dev)
+def host_table(cmap, what="hier_heatmap"):
+    """The colour table of ``cmap`` -- a name, a matplotlib colormap or a uint8 ``[N, 3]`` array or tensor -- checked and still where
+    it is: a table the kernels cannot hold is refused before anything runs.  ``_frontend.table_on`` takes it to the device."""
+    if F.is_tensor(cmap) or isinstance(cmap, np.ndarray):
+        if str(cmap.dtype).replace("torch.", "") != "uint8" or len(cmap.shape) != 2 or cmap.shape[1] != 3 or \
+                not 2 <= cmap.shape[0] <= N.HIER_MAX_LUT:
+            raise ValueError(f"{what}: a colour table is uint8 [N, 3] with 2 <= N <= {N.HIER_MAX_LUT}, got {cmap.dtype} {list(cmap.shape)}")
+        return cmap
+    return F.table_host(colour_table_n, cmap)
 
 
 def shifted_regions(region_u8, offset: int = 128):
@@ -114,7 +106,7 @@ def shifted_regions(region_u8, offset: int = 128):
     ``offset / 2`` pixels.  The aim is the reference's pictures, so that is reproduced, not repaired.  A numpy array gives numpy
     arrays; a tensor gives tensors on its device (nothing is copied to the host)."""
     import torch
-    as_numpy = not H._is_tensor(region_u8)
+    as_numpy = not F.is_tensor(region_u8)
     r = torch.from_numpy(np.ascontiguousarray(region_u8)) if as_numpy else region_u8
     if r.dtype != torch.uint8 or r.dim() != 3 or r.shape[2] != 3:
         raise ValueError(f"shifted_regions: the region is uint8 [H, W, 3], got {r.dtype} {list(r.shape)}")
@@ -139,7 +131,7 @@ def _region_tensor(hipt, region):
     device: ToTensor + Normalize(0.5, 0.5) by ``hipt_u8_normalize``, the bits ``eval_transforms`` computes on the host."""
     import torch
     d256 = hipt.model256.weight_device
-    t = region if H._is_tensor(region) else torch.from_numpy(np.array(region))   # (a copy: a PIL image's array is read-only)
+    t = region if F.is_tensor(region) else torch.from_numpy(np.array(region))   # (a copy: a PIL image's array is read-only)
     if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
         raise ValueError(f"hier_heatmap: a region is uint8 [H, W, 3], got {t.dtype} {list(t.shape)}")
     t = t.to(d256).contiguous()
@@ -195,7 +187,7 @@ def hier_ranks(x, f: int):
     """float64 device tensor, the shape of ``x``: the percentile ranks of every vector ``x[..., :]`` (float32, on the device) as if
     upscaled by ``f`` (``hipt_hier_ranks``; ``closed_form_percentiles`` is the same in numpy)."""
     import torch
-    if not H._is_tensor(x) or x.dtype != torch.float32 or x.dim() < 1:
+    if not F.is_tensor(x) or x.dtype != torch.float32 or x.dim() < 1:
         raise ValueError("hier_ranks: x is a float32 device tensor [..., L]")
     N.require_cuda(x, "hier_ranks")
     L = int(x.shape[-1])
@@ -253,7 +245,7 @@ def compose_heatmaps(a256, a4k, w_256, h_256, base, *, offset=128, scale=4, alph
     if alpha != alpha or not w256 > 0 or (threshold is not None and float(threshold) != float(threshold)):
         raise ValueError("hier_heatmap: alpha / threshold is NaN, or w256 is not positive")
     for name, a in (("a256", a256), ("a4k", a4k)):
-        if not H._is_tensor(a) or a.dtype != torch.float32:
+        if not F.is_tensor(a) or a.dtype != torch.float32:
             raise ValueError(f"hier_heatmap: {name} is a float32 device tensor")
     n = w_256 * h_256
     if a4k.dim() != 3 or a4k.shape[0] != 4 or a4k.shape[2] != n:
@@ -264,24 +256,17 @@ def compose_heatmaps(a256, a4k, w_256, h_256, base, *, offset=128, scale=4, alph
     if not (1 <= nh <= N.HIER_MAX_HEADS and 1 <= n <= N.HIER_MAX_L):
         raise ValueError(f"hier_heatmap: {nh} heads, {n} patches outside 1 .. {N.HIER_MAX_HEADS} heads, 1 .. {N.HIER_MAX_L} patches")
     hs, ws = w_256 * 256 // scale, h_256 * 256 // scale
-    dev = H._resolve_device(None, (a4k, a256))
-    H._check_no_nan("hier_heatmap", a256=a256[:2], a4k=a4k)
-    base = H._as_array(base)
-    H._check_image("base", base, (hs, ws, 3), ("uint8",))
-    base_d = H._device_image(base, dev)
+    dev = F.resolve_device("heatmap", None, (a4k, a256))
+    F.check_no_nan("hier_heatmap", a256=a256[:2], a4k=a4k)
+    base = F.as_array(base)
+    F.check_image("heatmap", "base", base, (hs, ws, 3), ("uint8",))
+    table = host_table(cmap)
+    base_d = F.to_device(base, dev)
     flat_pairs, npairs = _check_pairs(pairs, nh) if "blend" in which else (None, 0)
     shapes = {"4k": (nh, hs, ws, 3), "256": (nh, hs, ws, 3), "blend": (npairs, hs, ws, 3), "256th": (nh, hs, ws, 3)}
-    res = {}
-    for k in which:
-        buf = None if out is None else out.get(k)
-        if buf is None:
-            buf = torch.empty(shapes[k], dtype=torch.uint8, device=dev)
-        elif (not H._is_tensor(buf) or buf.dtype != torch.uint8 or tuple(buf.shape) != shapes[k] or buf.device != dev
-              or not buf.is_contiguous()):
-            raise ValueError(f"hier_heatmap: out[{k!r}] must be a contiguous uint8 {list(shapes[k])} tensor on {dev}")
-        res[k] = buf
+    res = {k: F.check_out("hier_heatmap", None if out is None else out.get(k), shapes[k], torch.uint8, dev, name=f"out[{k!r}]") for k in which}
     with torch.cuda.device(dev):
-        table = _table(cmap, dev)
+        table = F.table_on(colour_table_n, cmap, table, dev)
         pct4k = hier_ranks(a4k, 256 // scale)                                          # [4, nh, n]
         pct256 = hier_ranks(a256[:2].permute(0, 2, 1, 3).contiguous(), 16 // scale)    # [2, nh, n, 256]
         off = [(offset * k) // scale for k in (1, 2, 3)]
@@ -293,7 +278,7 @@ def compose_heatmaps(a256, a4k, w_256, h_256, base, *, offset=128, scale=4, alph
 
 
 def _as_region_array(region) -> np.ndarray:
-    a = region.cpu().numpy() if H._is_tensor(region) else np.asarray(region)
+    a = region.cpu().numpy() if F.is_tensor(region) else np.asarray(region)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
         raise ValueError(f"hier_heatmap: the region is an RGB image (uint8 [H, W, 3]), got {a.dtype} {list(a.shape)}")
     return a
@@ -305,7 +290,7 @@ def _region_and_background(hipt, region, scale, base, host_resize):
     import torch
     if scale not in SCALES:
         raise ValueError(f"hier_heatmap: scale {scale}; the pictures exist at {SCALES}")
-    if H._is_tensor(region) and region.is_cuda:
+    if F.is_tensor(region) and region.is_cuda:
         r_dev, r_np = region, None
     else:
         r_np = _as_region_array(region)
@@ -394,7 +379,7 @@ def hierarchical_heatmaps_concat_select(hipt, region, heads4k=(0, 5), heads256=(
     hs, ws = int(res["4k"].shape[1]), int(res["4k"].shape[2])
     dev = res["4k"].device
     canvas = torch.empty(((1 + len(heads256)) * hs, (1 + len(heads4k)) * ws, 3), dtype=torch.uint8, device=dev)
-    canvas[:hs, :ws] = H._device_image(H._as_array(base), dev)
+    canvas[:hs, :ws] = F.to_device(F.as_array(base), dev)
     for c, j in enumerate(heads4k):
         canvas[:hs, (c + 1) * ws:(c + 2) * ws] = res["4k"][j]
     for r, i in enumerate(heads256):

@@ -19,28 +19,18 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _frontend as F
 from . import _native as N
 
 HE_REF = ((0.5626, 0.2159), (0.7201, 0.8012), (0.4062, 0.5581))
 MAXC_REF = (1.9705, 1.0308)
 
 
-def _layout(x, what: str) -> Tuple[torch.Tensor, bool, int, int, bool]:
+def _images(x, what: str) -> Tuple[torch.Tensor, bool, int, int, bool]:
     """(x as a batch, interleaved, h, w, batched); ValueError for anything but uint8 RGB [.., 3, h, w] / [.., h, w, 3]"""
-    if not torch.is_tensor(x):
-        raise ValueError(f"{what}: x is a uint8 tensor, got {type(x).__name__}")
-    if x.dtype != torch.uint8:
-        raise ValueError(f"{what} takes raw uint8 RGB images (got {x.dtype}); the stain model is fitted to the bytes")
-    if x.dim() not in (3, 4):
-        raise ValueError(f"{what}: x is uint8 [3, h, w] / [h, w, 3] or a batch of either, got {list(x.shape)}")
+    il, h, w = F.rgb_layout(what, x)
     batched = x.dim() == 4
     xb = x if batched else x[None]
-    if xb.shape[-1] == 3 and xb.shape[1] != 3:   # (as augment_regions: [R, 3, h, 3] counts as planar)
-        il, h, w = True, int(xb.shape[1]), int(xb.shape[2])
-    elif xb.shape[1] == 3:
-        il, h, w = False, int(xb.shape[2]), int(xb.shape[3])
-    else:
-        raise ValueError(f"{what}: x is uint8 [3, h, w] / [h, w, 3] or a batch of either, got {list(x.shape)}")
     if xb.shape[0] < 1 or h * w < 1 or h * w >= 1 << 31:
         raise ValueError(f"{what}: {xb.shape[0]} images of {h} x {w} pixels (at least one, h * w below 2^31)")
     return xb, il, h, w, batched
@@ -74,28 +64,17 @@ def _check_target(what: str, target, dev):
     return he.to(device=dev, dtype=torch.float32).reshape(6).contiguous(), mc.to(device=dev, dtype=torch.float32).reshape(2).contiguous()
 
 
-def _check_out(what: str, out, x, xb, il, h, w, batched, out_dtype):
+def _out_shape(what: str, out, x, xb, h, w, batched, out_dtype):
+    """The result's shape; a given ``out`` is checked against it here, before the question for a device."""
     if out_dtype not in (torch.uint8, torch.float32):
         raise ValueError(f"{what}: out_dtype is torch.uint8 or torch.float32, got {out_dtype}")
-    r = xb.shape[0]
     if out_dtype == torch.uint8:
         shape = tuple(x.shape)
     else:   # the reference route's tensor: planar whatever the input's layout
-        shape = (r, 3, h, w) if batched else (3, h, w)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != out_dtype or tuple(out.shape) != shape or out.device != x.device
-                            or not out.is_contiguous() or out.data_ptr() == x.data_ptr()):
-        raise ValueError(f"{what}: out must be a contiguous {out_dtype} {list(shape)} tensor on {x.device}, and not x")
+        shape = (xb.shape[0], 3, h, w) if batched else (3, h, w)
+    if out is not None:
+        F.check_out(what, out, shape, out_dtype, x.device, not_alias=(x,))
     return shape
-
-
-def _require_device(what: str, x):
-    if not x.is_cuda:
-        raise ValueError(f"{what}: x is on {x.device}; the normalisation runs on a HIP device only")
-
-
-def _workspace(r, h, w, dev):
-    need = int(N.lib().hipt_macenko_workspace_bytes(r, h, w))
-    return torch.empty((max(need, 256),), dtype=torch.uint8, device=dev), need
 
 
 def macenko_fit(x_u8, Io=240, alpha=1, beta=0.15, *, _aux=False):
@@ -105,17 +84,16 @@ def macenko_fit(x_u8, Io=240, alpha=1, beta=0.15, *, _aux=False):
     degenerate fit); its ``HE`` and ``maxC`` are zeros.  ``(HE[i], maxC[i])`` is a ``target`` for the other two functions:
     torchstain's ``normalizer.fit(target_image)``.  ValueError -- before any native call -- for float input, another shape, a
     CPU tensor, ``Io <= 0``, ``alpha`` outside (0, 50) or ``beta < 0``."""
-    xb, il, h, w, _ = _layout(x_u8, "macenko_fit")
+    xb, il, h, w, _ = _images(x_u8, "macenko_fit")
     Io, alpha, beta = _check_params("macenko_fit", Io, alpha, beta)
-    _require_device("macenko_fit", xb)
-    dev, r = xb.device, int(xb.shape[0])
+    dev, r = F.resolve_device("macenko_fit", None, (xb,), exc=ValueError), int(xb.shape[0])
     src = xb.detach().contiguous()
     with torch.cuda.device(dev):
         he = torch.empty((r, 3, 2), dtype=torch.float32, device=dev)
         mc = torch.empty((r, 2), dtype=torch.float32, device=dev)
         st = torch.empty((r,), dtype=torch.int32, device=dev)
         aux = torch.empty((r, 16), dtype=torch.float32, device=dev) if _aux else None
-        ws, need = _workspace(r, h, w, dev)
+        ws, need = F.scratch("hipt_macenko_workspace_bytes", r, h, w, dev=dev)
         N.call("hipt_macenko_fit", N.ptr(src), int(il), r, h, w, Io, alpha, beta, N.ptr(he), N.ptr(mc), N.ptr(st), N.ptr(aux), N.ptr(ws), need,
                N.stream_ptr(dev))
     return (he, mc, st, aux) if _aux else (he, mc, st)
@@ -126,16 +104,15 @@ def macenko_apply(x_u8, HE, maxC, status=None, target=None, out=None, out_dtype=
     ``target`` -- ``None`` for torchstain's reference constants, or the ``(HE [3, 2], maxC [2])`` of one fitted image.  Images
     whose ``status`` is not 0 are copied through.  ``out_dtype=torch.uint8``: the input's shape and layout;
     ``torch.float32``: planar ``[R, 3, h, w]`` (``[3, h, w]`` for one image) equal to the uint8 result / 255."""
-    xb, il, h, w, batched = _layout(x_u8, "macenko_apply")
+    xb, il, h, w, batched = _images(x_u8, "macenko_apply")
     Io, _, _ = _check_params("macenko_apply", Io, 1, 0)
-    shape = _check_out("macenko_apply", out, x_u8, xb, il, h, w, batched, out_dtype)
+    shape = _out_shape("macenko_apply", out, x_u8, xb, h, w, batched, out_dtype)
     r = int(xb.shape[0])
     if not torch.is_tensor(HE) or not torch.is_tensor(maxC) or HE.numel() != 6 * r or maxC.numel() != 2 * r:
         raise ValueError(f"macenko_apply: HE is [{r}, 3, 2] and maxC [{r}, 2], one per image")
     if status is not None and (not torch.is_tensor(status) or status.numel() != r):
         raise ValueError(f"macenko_apply: status is int32 [{r}]")
-    _require_device("macenko_apply", xb)
-    dev = xb.device
+    dev = F.resolve_device("macenko_apply", None, (xb,), exc=ValueError)
     ref_he, ref_mc = _check_target("macenko_apply", target, dev)
     he = HE.to(device=dev, dtype=torch.float32).contiguous()
     mc = maxC.to(device=dev, dtype=torch.float32).contiguous()
@@ -154,18 +131,17 @@ def macenko_normalize(x_u8, Io=240, alpha=1, beta=0.15, target=None, out=None, o
     synchronisation, so a call with a preallocated ``out`` can be captured into a graph.  Bit for bit what the two functions
     give one after the other.  Returns the normalised images (``out``, where given), with ``return_status=True`` the pair
     ``(images, status int32 [R])``.  Arguments as in the two functions."""
-    xb, il, h, w, batched = _layout(x_u8, "macenko_normalize")
+    xb, il, h, w, batched = _images(x_u8, "macenko_normalize")
     Io, alpha, beta = _check_params("macenko_normalize", Io, alpha, beta)
-    shape = _check_out("macenko_normalize", out, x_u8, xb, il, h, w, batched, out_dtype)
-    _require_device("macenko_normalize", xb)
-    dev, r = xb.device, int(xb.shape[0])
+    shape = _out_shape("macenko_normalize", out, x_u8, xb, h, w, batched, out_dtype)
+    dev, r = F.resolve_device("macenko_normalize", None, (xb,), exc=ValueError), int(xb.shape[0])
     ref_he, ref_mc = _check_target("macenko_normalize", target, dev)
     src = xb.detach().contiguous()
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(shape, dtype=out_dtype, device=dev)
         st = torch.empty((r,), dtype=torch.int32, device=dev) if return_status else None
-        ws, need = _workspace(r, h, w, dev)
+        ws, need = F.scratch("hipt_macenko_workspace_bytes", r, h, w, dev=dev)
         N.call("hipt_macenko_normalize", N.ptr(src), int(il), r, h, w, Io, alpha, beta, N.ptr(ref_he), N.ptr(ref_mc), N.ptr(out),
                int(out_dtype == torch.float32), None, None, N.ptr(st), N.ptr(ws), need, N.stream_ptr(dev))
     return (out, st) if return_status else out
@@ -174,10 +150,9 @@ def macenko_normalize(x_u8, Io=240, alpha=1, beta=0.15, target=None, out=None, o
 def macenko_keys(x_u8, aux, Io=240, beta=0.15):
     """For tests: ``(keys float32 [R, 3, h * w], tissue uint8 [R, h * w])`` -- phi, C[0], C[1] of every pixel exactly as the
     select passes compute them from ``aux`` (``macenko_fit(..., _aux=True)[3]``)."""
-    xb, il, h, w, _ = _layout(x_u8, "macenko_keys")
+    xb, il, h, w, _ = _images(x_u8, "macenko_keys")
     Io, _, beta = _check_params("macenko_keys", Io, 1, beta)
-    _require_device("macenko_keys", xb)
-    dev, r = xb.device, int(xb.shape[0])
+    dev, r = F.resolve_device("macenko_keys", None, (xb,), exc=ValueError), int(xb.shape[0])
     src = xb.detach().contiguous()
     aux = aux.to(device=dev, dtype=torch.float32).contiguous()
     with torch.cuda.device(dev):
@@ -202,7 +177,7 @@ class MacenkoNormalizer:
     def _u8(self, I):
         if not torch.is_tensor(I) or I.dim() != 3 or I.shape[0] != 3:
             raise ValueError(f"MacenkoNormalizer: I is [3, h, w] with values 0..255, got {list(getattr(I, 'shape', []))}")
-        dev = torch.device(self.device) if self.device is not None else (I.device if I.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        dev = F.resolve_device("MacenkoNormalizer", self.device, (I,), exc=ValueError, staged=True)
         if I.dtype != torch.uint8:
             I = I.round().clamp(0, 255).to(torch.uint8)
         return I.to(dev)

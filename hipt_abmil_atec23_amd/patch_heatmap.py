@@ -20,8 +20,8 @@ import os
 
 import numpy as np
 
+from . import _frontend as F
 from . import _native as N
-from . import heatmap as H
 from . import hier_heatmap as HH
 
 SIDE = 256     # pixels along a patch
@@ -34,12 +34,12 @@ def _patch_batch(patches, what):
     if isinstance(patches, (list, tuple)):
         if not patches:
             raise ValueError(f"{what}: no patches")
-        items = [p if H._is_tensor(p) else torch.from_numpy(np.array(p)) for p in patches]   # (a copy: a PIL image's array is read-only)
+        items = [p if F.is_tensor(p) else torch.from_numpy(np.array(p)) for p in patches]   # (a copy: a PIL image's array is read-only)
         if any(t.dim() != 3 for t in items) or len({(t.dtype, tuple(t.shape), t.device) for t in items}) != 1:
             raise ValueError(f"{what}: a list holds uint8 [256, 256, 3] patches of one kind")
         t, single = torch.stack(items), False
     else:
-        t = patches if H._is_tensor(patches) else torch.from_numpy(np.array(patches))
+        t = patches if F.is_tensor(patches) else torch.from_numpy(np.array(patches))
         single = t.dim() == 3
         if single:
             t = t[None]
@@ -55,7 +55,7 @@ def shifted_patches(patches_u8):
     white (255) margin of 16 pixels added to the right and below (attention_visualization_utils.py:310-311).  A numpy array gives a
     numpy array; a tensor gives a tensor on its device (nothing is copied to the host)."""
     import torch
-    as_numpy = not H._is_tensor(patches_u8)
+    as_numpy = not F.is_tensor(patches_u8)
     t = torch.from_numpy(np.ascontiguousarray(patches_u8)) if as_numpy else patches_u8
     if t.dtype != torch.uint8 or t.dim() != 4 or tuple(t.shape[1:]) != (SIDE, SIDE, 3):
         raise ValueError(f"shifted_patches: patches are uint8 [P, {SIDE}, {SIDE}, 3], got {t.dtype} {list(t.shape)}")
@@ -88,20 +88,6 @@ def mosaic_shape(nh: int, cols: int):
     return ((nh + cols - 1) // cols) * SIDE, cols * SIDE
 
 
-def _check_table(cmap):
-    """A colour table the kernel cannot hold is refused before anything runs (``hier_heatmap._table`` builds it afterwards)."""
-    if isinstance(cmap, str):
-        if (cmap, None) not in HH._table_cache:
-            HH._table_cache[(cmap, None)] = HH.colour_table_n(cmap)
-    elif H._is_tensor(cmap) or isinstance(cmap, np.ndarray):
-        if str(cmap.dtype).replace("torch.", "") != "uint8" or len(cmap.shape) != 2 or cmap.shape[1] != 3 or \
-                not 2 <= cmap.shape[0] <= N.HIER_MAX_LUT:
-            raise ValueError(f"patch_heatmap: a colour table is uint8 [N, 3] with 2 <= N <= {N.HIER_MAX_LUT}, got {cmap.dtype} "
-                             f"{list(cmap.shape)}")
-    else:
-        HH.colour_table_n(cmap)
-
-
 def compose_patch_heatmaps(a256, patches, *, offset=16, alpha=0.5, cmap="coolwarm", threshold=None, concat=False, cols=3, out=None,
                            which=None):
     """The pictures of P patches from their raw attention maps, as a dict of uint8 device tensors.
@@ -129,33 +115,26 @@ def compose_patch_heatmaps(a256, patches, *, offset=16, alpha=0.5, cmap="coolwar
     alpha = float(alpha)
     if alpha != alpha or (threshold is not None and float(threshold) != float(threshold)):
         raise ValueError("patch_heatmap: alpha / threshold is NaN")
-    if not H._is_tensor(a256) or a256.dtype != torch.float32:
+    if not F.is_tensor(a256) or a256.dtype != torch.float32:
         raise ValueError("patch_heatmap: a256 is a float32 device tensor")
     if a256.dim() != 4 or a256.shape[1] != 2 or a256.shape[3] != SIDE:
         raise ValueError(f"patch_heatmap: a256 must be [P, 2, nh, 256], got {list(a256.shape)}")
     p, nh = int(a256.shape[0]), int(a256.shape[2])
     if not (1 <= nh <= N.HIER_MAX_HEADS and 1 <= p <= N.PATCH_MAX_P):
         raise ValueError(f"patch_heatmap: {nh} heads, {p} patches outside 1 .. {N.HIER_MAX_HEADS} heads, 1 .. {N.PATCH_MAX_P} patches")
-    patches = H._as_array(patches)
-    H._check_image("patches", patches, (p, SIDE, SIDE, 3), ("uint8",))
-    _check_table(cmap)
-    H._check_no_nan("patch_heatmap", a256=a256)
-    dev = H._resolve_device(None, (a256,))
-    patches_d = H._device_image(patches, dev)
+    patches = F.as_array(patches)
+    F.check_image("heatmap", "patches", patches, (p, SIDE, SIDE, 3), ("uint8",))
+    table = HH.host_table(cmap, "patch_heatmap")
+    F.check_no_nan("patch_heatmap", a256=a256)
+    dev = F.resolve_device("heatmap", None, (a256,))
+    patches_d = F.to_device(patches, dev)
     shape = (p,) + mosaic_shape(nh, cols) + (3,) if concat else (p, nh, SIDE, SIDE, 3)
-    res = {}
-    for k in which:
-        buf = None if out is None else out.get(k)
-        if buf is None:
-            buf = torch.empty(shape, dtype=torch.uint8, device=dev)
-        elif (not H._is_tensor(buf) or buf.dtype != torch.uint8 or tuple(buf.shape) != shape or buf.device != dev
-              or not buf.is_contiguous()):
-            raise ValueError(f"patch_heatmap: out[{k!r}] must be a contiguous uint8 {list(shape)} tensor on {dev}")
-        res[k] = buf
+    res = {k: F.check_out("patch_heatmap", None if out is None else out.get(k), shape, torch.uint8, dev, not_alias=(patches_d,),
+                          name=f"out[{k!r}]") for k in which}   # (hipt_patch_render refuses the patches as an output: never in place)
     if len(res) == 2 and res["256"].data_ptr() == res["256th"].data_ptr():
         raise ValueError("patch_heatmap: out['256'] and out['256th'] are one buffer")
     with torch.cuda.device(dev):
-        table = HH._table(cmap, dev)
+        table = F.table_on(HH.colour_table_n, cmap, table, dev)
         pct = HH.hier_ranks(a256, 16)   # [P, 2, nh, 256]
         N.call("hipt_patch_render", N.ptr(pct), N.ptr(patches_d), p, nh, N.ptr(table), int(table.shape[0]), offset, alpha,
                int(threshold is not None), float(threshold) if threshold is not None else 0.0, cols if concat else 0,

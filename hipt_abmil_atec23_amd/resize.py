@@ -17,6 +17,7 @@ import math
 
 import numpy as np
 
+from . import _frontend as F
 from . import _native as N
 
 PRECISION_BITS = 22
@@ -127,12 +128,9 @@ def _device_table(in_len, out_len, name, dev):
 def _check_size(size):
     try:
         ow, oh = size
-        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (ow, oh))
     except (TypeError, ValueError):
-        ok = False
-    if not ok or int(ow) < 1 or int(oh) < 1:
-        raise ValueError(f"resize: size is (width, height) in positive integers, got {size!r}")
-    return int(ow), int(oh)
+        raise ValueError(f"resize: size is (width, height) in positive integers, got {size!r}") from None
+    return F.check_int("resize", "size's width", ow, 1), F.check_int("resize", "size's height", oh, 1)
 
 
 def resize_u8(x, size, resample="bicubic", out=None, *, _route=None):
@@ -145,7 +143,7 @@ def resize_u8(x, size, resample="bicubic", out=None, *, _route=None):
     copied to the host.  ValueError -- before any native call -- for a CPU tensor, another dtype or channel count, a non-positive
     size or an unknown filter."""
     import torch
-    if type(x).__module__.split(".")[0] != "torch" or not hasattr(x, "data_ptr"):
+    if not F.is_tensor(x):
         raise ValueError(f"resize_u8: x is a uint8 device tensor, got {type(x).__name__}")
     if x.dtype != torch.uint8 or x.dim() not in (3, 4) or x.shape[-1] != 3:
         raise ValueError(f"resize_u8: x is uint8 [H, W, 3] or [n, H, W, 3], got {x.dtype} {list(x.shape)}")
@@ -154,8 +152,7 @@ def resize_u8(x, size, resample="bicubic", out=None, *, _route=None):
     if _route not in _ROUTES:
         raise ValueError(f"resize_u8: route {_route!r}; the routes are 'general' and 'fused'")
     route = _ROUTES[_route]
-    if not x.is_cuda:
-        raise ValueError(f"resize_u8: x is on {x.device}; the resize runs on a HIP device only")
+    dev = F.resolve_device("resize_u8", None, (x,), exc=ValueError)
     batched = x.dim() == 4
     n = int(x.shape[0]) if batched else 1
     h, w = int(x.shape[-3]), int(x.shape[-2])
@@ -169,12 +166,7 @@ def resize_u8(x, size, resample="bicubic", out=None, *, _route=None):
     if oh != h:
         resize_table(h, oh, name)
     shape = (n, oh, ow, 3) if batched else (oh, ow, 3)
-    dev = x.device
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=dev)
-    elif (type(out).__module__.split(".")[0] != "torch" or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != dev
-          or not out.is_contiguous() or out.data_ptr() == x.data_ptr()):
-        raise ValueError(f"resize_u8: out must be a contiguous uint8 {list(shape)} tensor on {dev}, and not x")
+    out = F.check_out("resize_u8", out, shape, torch.uint8, dev, not_alias=(x,))
     x = x.detach().contiguous()
     if x.data_ptr() % 16:
         x = x.clone()   # (a view into a larger tensor: the kernels read 16-byte vectors)
@@ -188,8 +180,7 @@ def resize_u8(x, size, resample="bicubic", out=None, *, _route=None):
         if oh != h:
             ky, by = _device_table(h, oh, name, dev)
             ksy = int(ky.shape[1])
-        need = int(N.lib().hipt_resize_workspace_bytes(n, h, w, oh, ow, route))
-        ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+        ws, need = F.scratch("hipt_resize_workspace_bytes", n, h, w, oh, ow, route, dev=dev, floor=0)   # (no scratch: ws is None)
         N.call("hipt_resize_u8", N.ptr(x), n, h, w, oh, ow, N.ptr(kx), N.ptr(bx), ksx, N.ptr(ky), N.ptr(by), ksy, N.ptr(out), N.ptr(ws),
                need, route, N.stream_ptr(dev))
     return out
@@ -210,9 +201,8 @@ def resize_patches(x, target_patch_size=-1, custom_downsample=1):
     datasets/dataset_h5.py:200-202) for a batch of patches ``x`` (uint8 ``[n, P, P, 3]`` on the device): ``x`` itself when neither
     ``target_patch_size > 0`` nor ``custom_downsample > 1``, else the bicubic resize to ``target_size(P, ...)``, ready for
     ``resnet50_baseline`` / ``resnet18_baseline``'s uint8 ``[B, H, W, 3]`` input."""
-    if isinstance(target_patch_size, bool) or isinstance(custom_downsample, bool) or \
-            not isinstance(target_patch_size, (int, np.integer)) or not isinstance(custom_downsample, (int, np.integer)):
-        raise ValueError(f"resize_patches: target_patch_size {target_patch_size!r} / custom_downsample {custom_downsample!r} are integers")
+    F.check_int("resize_patches", "target_patch_size", target_patch_size)
+    F.check_int("resize_patches", "custom_downsample", custom_downsample)
     if not hasattr(x, "dim") or x.dim() != 4 or x.shape[1] != x.shape[2]:
         raise ValueError(f"resize_patches: x is a batch of square patches, uint8 [n, P, P, 3], got {list(getattr(x, 'shape', []))}")
     size = target_size(int(x.shape[1]), int(target_patch_size), int(custom_downsample))

@@ -15,72 +15,17 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _frontend as F
 from . import _native as N
 
 MAX_MEDIAN, MAX_CLOSE = N.SEGMENT_MAX_MEDIAN, N.SEGMENT_MAX_CLOSE
 
 
-def _is_tensor(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
-
-
-def _check_int(what: str, name: str, v, lo: int, hi: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError(f"{what}: {name} is an integer in {lo} .. {hi}, got {v!r}")
-    return int(v)
-
-
 def _check_median(what: str, k) -> int:
-    k = _check_int(what, "the median window", k, 1, 1 << 30)
+    k = F.check_int(what, "the median window", k, 1, 1 << 30)
     if k % 2 == 0 or k > MAX_MEDIAN:
         raise ValueError(f"{what}: the median window is odd and at most {MAX_MEDIAN}, got {k}")
     return k
-
-
-def _to_device(what: str, x, device, dims: int):
-    """``x`` (numpy array or tensor, uint8, ``dims`` axes) as a contiguous device tensor; every refusal comes before the device is touched"""
-    import torch
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.uint8 or x.ndim != dims:
-            raise ValueError(f"{what}: the input is uint8 with {dims} axes, got {x.dtype} {list(x.shape)}")
-        t = None
-    elif _is_tensor(x):
-        if x.dtype != torch.uint8 or x.dim() != dims:
-            raise ValueError(f"{what}: the input is uint8 with {dims} axes, got {x.dtype} {list(x.shape)}")
-        t = x
-    else:
-        raise ValueError(f"{what}: the input is a numpy array or a device tensor, got {type(x).__name__}")
-    shape = tuple(int(v) for v in x.shape)
-    if dims == 3 and shape[2] not in (3, 4):
-        raise ValueError(f"{what}: the image is uint8 [H, W, 3] or [H, W, 4], got {list(shape)}")
-    if shape[0] < 1 or shape[1] < 1 or shape[0] * shape[1] >= 1 << 31:
-        raise ValueError(f"{what}: {shape[0]} x {shape[1]} pixels (at least one, H * W below 2^31)")
-    if t is None:
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise ValueError(f"{what}: device {dev}; the segmentation runs on a HIP device only")
-        return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    if not t.is_cuda:
-        raise ValueError(f"{what}: the input is on {t.device}; the segmentation runs on a HIP device only (pass a numpy array to have it copied)")
-    if device is not None and torch.device(device).type == "cuda" and torch.device(device).index not in (None, t.device.index):
-        raise ValueError(f"{what}: the input is on {t.device}, device= says {device}")
-    return t.detach().contiguous()
-
-
-def _check_out(what: str, out, shape, dev, *others):
-    import torch
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=dev)
-    if (not _is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != dev or not out.is_contiguous()
-            or any(out.data_ptr() == o.data_ptr() for o in others)):
-        raise ValueError(f"{what}: out must be a contiguous uint8 {list(shape)} tensor on {dev}, and not the input")
-    return out
-
-
-def _workspace(h: int, w: int, close: int, dev):
-    import torch
-    need = int(N.lib().hipt_segment_workspace_bytes(h, w, close))
-    return torch.empty((max(need, 256),), dtype=torch.uint8, device=dev), need
 
 
 def tissue_mask(img, sthresh=20, sthresh_up=255, mthresh=7, close=0, use_otsu=False, out=None, return_parts=False, device=None):
@@ -93,21 +38,21 @@ def tissue_mask(img, sthresh=20, sthresh_up=255, mthresh=7, close=0, use_otsu=Fa
     dtype or shape, a CPU tensor, thresholds outside 0 .. 255, an even ``mthresh`` or one above 15, ``close`` outside 0 .. 128."""
     import torch
     what = "tissue_mask"
-    sthresh = _check_int(what, "sthresh", sthresh, 0, 255)
-    sthresh_up = _check_int(what, "sthresh_up", sthresh_up, 0, 255)
+    sthresh = F.check_int(what, "sthresh", sthresh, 0, 255)
+    sthresh_up = F.check_int(what, "sthresh_up", sthresh_up, 0, 255)
     mthresh = _check_median(what, mthresh)
-    close = _check_int(what, "close", close, 0, MAX_CLOSE)
-    x = _to_device(what, img, device, 3)
+    close = F.check_int(what, "close", close, 0, MAX_CLOSE)
+    x = F.as_device_u8(what, img, device, dims=3, channels=(3, 4))
     h, w, ch = (int(v) for v in x.shape)
     dev = x.device
-    out = _check_out(what, out, (h, w), dev, x)
+    out = F.check_out(what, out, (h, w), torch.uint8, dev, not_alias=(x,))
     with torch.cuda.device(dev):
         med = sat = thr = None
         if return_parts:
             med = torch.empty((h, w), dtype=torch.uint8, device=dev)
             sat = torch.empty((h, w), dtype=torch.uint8, device=dev)
             thr = torch.empty((1,), dtype=torch.int32, device=dev)
-        ws, need = _workspace(h, w, close, dev)
+        ws, need = F.scratch("hipt_segment_workspace_bytes", h, w, close, dev=dev)
         N.call("hipt_segment_mask", N.ptr(x), h, w, ch, sthresh, sthresh_up, mthresh, close, int(bool(use_otsu)), N.ptr(out), N.ptr(sat),
                N.ptr(med), N.ptr(thr), N.ptr(ws), need, N.stream_ptr(dev))
     return (out, med, sat, thr) if return_parts else out
@@ -116,9 +61,9 @@ def tissue_mask(img, sthresh=20, sthresh_up=255, mthresh=7, close=0, use_otsu=Fa
 def saturation_u8(img, out=None, device=None):
     """The S channel of ``cv2.cvtColor(img, cv2.COLOR_RGB2HSV)`` for a uint8 ``[H, W, 3|4]`` image, as a uint8 device tensor ``[H, W]``."""
     import torch
-    x = _to_device("saturation_u8", img, device, 3)
+    x = F.as_device_u8("saturation_u8", img, device, dims=3, channels=(3, 4))
     h, w, ch = (int(v) for v in x.shape)
-    out = _check_out("saturation_u8", out, (h, w), x.device, x)
+    out = F.check_out("saturation_u8", out, (h, w), torch.uint8, x.device, not_alias=(x,))
     with torch.cuda.device(x.device):
         N.call("hipt_segment_saturation", N.ptr(x), h, w, ch, N.ptr(out), N.stream_ptr(x.device))
     return out
@@ -128,9 +73,9 @@ def median_blur_u8(x, ksize, out=None, device=None):
     """``cv2.medianBlur(x, ksize)`` of a uint8 plane ``[H, W]``: the exact median, borders replicated; ``ksize`` odd, 1 .. 15."""
     import torch
     ksize = _check_median("median_blur_u8", ksize)
-    x = _to_device("median_blur_u8", x, device, 2)
+    x = F.as_device_u8("median_blur_u8", x, device, dims=2)
     h, w = (int(v) for v in x.shape)
-    out = _check_out("median_blur_u8", out, (h, w), x.device, x)
+    out = F.check_out("median_blur_u8", out, (h, w), torch.uint8, x.device, not_alias=(x,))
     with torch.cuda.device(x.device):
         N.call("hipt_segment_median", N.ptr(x), h, w, ksize, N.ptr(out), N.stream_ptr(x.device))
     return out
@@ -140,7 +85,7 @@ def otsu_threshold(x, device=None):
     """``(hist int32 [256], thresh int32 [1])`` of a uint8 plane, both on the device: the counts, and the level
     ``cv2.threshold(x, 0, 255, cv2.THRESH_OTSU)`` returns."""
     import torch
-    x = _to_device("otsu_threshold", x, device, 2)
+    x = F.as_device_u8("otsu_threshold", x, device, dims=2)
     h, w = (int(v) for v in x.shape)
     with torch.cuda.device(x.device):
         hist = torch.empty((256,), dtype=torch.int32, device=x.device)
@@ -153,12 +98,12 @@ def morph_close_u8(x, size, out=None, device=None):
     """``cv2.morphologyEx(x, cv2.MORPH_CLOSE, np.ones((size, size), np.uint8))`` of a uint8 plane (any bytes, not only a binary
     picture); ``size`` 0 .. 128, 0 and 1 give a copy."""
     import torch
-    size = _check_int("morph_close_u8", "size", size, 0, MAX_CLOSE)
-    x = _to_device("morph_close_u8", x, device, 2)
+    size = F.check_int("morph_close_u8", "size", size, 0, MAX_CLOSE)
+    x = F.as_device_u8("morph_close_u8", x, device, dims=2)
     h, w = (int(v) for v in x.shape)
-    out = _check_out("morph_close_u8", out, (h, w), x.device, x)
+    out = F.check_out("morph_close_u8", out, (h, w), torch.uint8, x.device, not_alias=(x,))
     with torch.cuda.device(x.device):
-        ws, need = _workspace(h, w, size, x.device)
+        ws, need = F.scratch("hipt_segment_workspace_bytes", h, w, size, dev=x.device)
         N.call("hipt_segment_close", N.ptr(x), h, w, size, N.ptr(out), N.ptr(ws), need, N.stream_ptr(x.device))
     return out
 

@@ -16,6 +16,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _frontend as F
 from . import _native as N
 
 MODES = {"basic": N.TILE_BASIC, "center": N.TILE_CENTER, "four_pt": N.TILE_FOUR_PT, "four_pt_easy": N.TILE_FOUR_PT,
@@ -24,26 +25,9 @@ _MODE_NAMES = "'basic', 'center', 'four_pt' (= 'four_pt_easy'), 'four_pt_hard'"
 BOUND = N.TILING_COORD_BOUND   # every doubled coordinate lies strictly inside +-BOUND
 
 
-def _is_tensor(a):
-    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
-
-
-def _resolve_device(device, tensors=()):
-    import torch
-    on_dev = [t for t in tensors if _is_tensor(t) and t.is_cuda]
-    dev = torch.device(device) if device is not None else (on_dev[0].device if on_dev else torch.device("cuda"))
-    if dev.type != "cuda":
-        raise RuntimeError(f"tiling: device {dev}; hipt_abmil_atec23_amd runs only on a HIP device (there is deliberately no CPU path)")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tiling: no HIP device; hipt_abmil_atec23_amd runs only on a HIP device (there is deliberately no CPU path)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def _as_polygon(a, what):
     """An integer polygon as int64 [n, 2] on the host (cv2's [n, 1, 2] contours included)."""
-    if _is_tensor(a):
+    if F.is_tensor(a):
         a = a.detach().cpu().numpy()
     a = np.asarray(a)
     if a.size == 0:
@@ -75,18 +59,13 @@ def _pack(polys, what):
     return np.ascontiguousarray(verts, dtype=np.int32).reshape(-1, 2), off.astype(np.int32)
 
 
-def _to_dev(a, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 # ------------------------------------------------------------------------------------------------------------------------------
 # the primitive
 # ------------------------------------------------------------------------------------------------------------------------------
 def _doubled_points(points):
     """int32-ranged doubled points [Q, 2] as an int64 tensor where ``points`` lives; integers or exact multiples of 0.5."""
     import torch
-    t = points if _is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points)))
+    t = points if F.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points)))
     t = t.detach()
     if t.ndim == 1 and t.numel() == 2:
         t = t.reshape(1, 2)
@@ -125,13 +104,13 @@ def point_polygon_test(polygons, points, poly_id=None, device=None):
             raise ValueError(f"point_polygon_test: {len(polys)} polygons need a poly_id per point")
         ids = torch.zeros(Q, dtype=torch.int64)
     else:
-        ids = (poly_id if _is_tensor(poly_id) else torch.from_numpy(np.ascontiguousarray(np.asarray(poly_id)))).detach().reshape(-1)
+        ids = (poly_id if F.is_tensor(poly_id) else torch.from_numpy(np.ascontiguousarray(np.asarray(poly_id)))).detach().reshape(-1)
         if ids.is_floating_point() or ids.dtype == torch.bool or ids.numel() != Q:
             raise ValueError(f"point_polygon_test: poly_id must be {Q} integers")
         if Q and (int(ids.min()) < 0 or int(ids.max()) >= len(polys)):
             raise ValueError(f"point_polygon_test: poly_id outside [0, {len(polys)})")
-    dev = _resolve_device(device, (points, poly_id))
-    v_d, off_d = _to_dev(verts, dev), _to_dev(off, dev)
+    dev = F.resolve_device("tiling", device, (points, poly_id), staged=True)
+    v_d, off_d = F.to_device(verts, dev), F.to_device(off, dev)
     p_d = d.to(dev, torch.int32).contiguous()
     id_d = ids.to(dev, torch.int32).contiguous()
     out = torch.empty(Q, dtype=torch.int8, device=dev)
@@ -179,8 +158,8 @@ class _HostSlide:
         self.verts, self.off = _pack(polys, "tiling")
 
     def upload(self, device):
-        dev = _resolve_device(device, self.contours)
-        return PackedSlide(_to_dev(self.verts, dev), _to_dev(self.off, dev), self.ranges, self.boxes, dev)
+        dev = F.resolve_device("tiling", device, self.contours, staged=True)
+        return PackedSlide(F.to_device(self.verts, dev), F.to_device(self.off, dev), self.ranges, self.boxes, dev)
 
 
 def pack_slide(contours, holes, device=None):
@@ -194,11 +173,9 @@ def pack_slide(contours, holes, device=None):
 # the reference's glue (wsi_core/WholeSlideImage.py:415-470), in Python integers
 # ------------------------------------------------------------------------------------------------------------------------------
 def _int(v, what):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        if isinstance(v, (float, np.floating)) and float(v).is_integer():
-            return int(v)
-        raise ValueError(f"tiling: {what} must be an integer, got {v!r}")
-    return int(v)
+    if isinstance(v, (float, np.floating)) and float(v).is_integer():   # (a whole float counts: level_dim and the ROI come from arithmetic)
+        return int(v)
+    return F.check_int("tiling", what, v)
 
 
 def _pair(v, what):
@@ -327,8 +304,8 @@ def plan_contours(contours, holes, level_dim0, patch_downsample, patch_level_dim
     if isinstance(slide, _HostSlide):
         slide = slide.upload(device)
     dev = slide.device
-    desc_d = _to_dev(np.array(desc, np.int32).reshape(-1, N.TILING_CONTOUR_INTS), dev)
-    units_d = _to_dev(units, dev)
+    desc_d = F.to_device(np.array(desc, np.int32).reshape(-1, N.TILING_CONTOUR_INTS), dev)
+    units_d = F.to_device(units, dev)
     flags = torch.zeros(total, dtype=torch.uint8, device=dev)
     return TilePlan(slide, grids, desc_d, units_d, len(units), mode, ps0, shift, flags)
 
