@@ -63,6 +63,9 @@ _LAZY = {
     "macenko_fit": ("macenko", "macenko_fit"), "macenko_apply": ("macenko", "macenko_apply"),
     "macenko_normalize": ("macenko", "macenko_normalize"), "MacenkoNormalizer": ("macenko", "MacenkoNormalizer"),
     "extract_slide_normalised": ("feature_store", "extract_slide_normalised"),
+    # tensor-space augmentation of uint8 RGB regions (extract_features_fp.py --use_transforms all / spatial)
+    "TENSOR_POLICIES": ("tensor_augment", "TENSOR_POLICIES"), "draw_tensor_params": ("tensor_augment", "draw_tensor_params"),
+    "augment_tensor": ("tensor_augment", "augment_tensor"), "TensorAugment": ("tensor_augment", "TensorAugment"),
     # the tissue mask of WholeSlideImage.segmentTissue (saturation, median, threshold / Otsu, closing) and its contour filter
     "tissue_mask": ("segment", "tissue_mask"), "segment_tissue": ("segment", "segment_tissue"),
     "saturation_u8": ("segment", "saturation_u8"), "median_blur_u8": ("segment", "median_blur_u8"),

@@ -162,6 +162,8 @@ SIGNATURES = {
     "hipt_topk_segments": (_i, [_p, _i64, _p, _i, _i, _i, _p, _p, _p]),
     "hipt_augment_workspace_bytes": (_sz, [_i, _i, _i]),
     "hipt_augment_regions": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "hipt_augment_tensor_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hipt_augment_tensor": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "hipt_resnet_packed_bytes": (_sz, [_RW]),
     "hipt_resnet_pack_weights": (_i, [_RW, _p, _p]),
     "hipt_resnet_workspace_bytes": (_sz, [_RW, _i, _i, _i]),

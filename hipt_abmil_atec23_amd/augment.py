@@ -119,16 +119,12 @@ def _uniform(g: torch.Generator, lo: float, hi: float) -> float:
     return float(torch.empty(1).uniform_(float(lo), float(hi), generator=g).item())
 
 
-def draw_params(policy: str, generator: torch.Generator, rows: int, cols: int) -> RegionParams:
-    """Draw one region's parameters in torchvision's order: flips (``rand(1) < p``, H then V); RandomAffine.get_params
-    (angle, tx, ty, scale, shear_x: a draw only for an argument that is given); ColorJitter.get_params (``randperm(4)``, then
-    b, c, s, h: a factor that is off is not drawn); GaussianBlur.get_params (sigma)."""
-    if policy not in POLICIES:
-        raise ValueError(f"unknown augmentation policy {policy!r}; known: {sorted(POLICIES)}")
-    spec = POLICIES[policy]
-    p = RegionParams()
-    if spec is None:
-        return p
+def draw_spec(spec: dict, generator: torch.Generator, rows: int, cols: int, p):
+    """The draws of one region for ``spec`` (a value of ``POLICIES``, or of ``tensor_augment.TENSOR_POLICIES``) in torchvision's
+    order, written into ``p`` (a ``RegionParams`` or anything with its flip and colour fields): flips (``rand(1) < p``, H then
+    V); RandomAffine.get_params (angle, tx, ty, scale, shear_x: a draw only for an argument that is given) into
+    ``p.draws`` -- the matrix is the caller's, it differs between the PIL and the tensor path; ColorJitter.get_params
+    (``randperm(4)``, then b, c, s, h: a factor that is off is not drawn); GaussianBlur.get_params (sigma)."""
     g = generator
     if "flip" in spec:
         p.hflip = bool(torch.rand(1, generator=g) < spec["flip"])
@@ -144,8 +140,6 @@ def draw_params(policy: str, generator: torch.Generator, rows: int, cols: int) -
         scale = _uniform(g, *a["scale"]) if a["scale"] is not None else 1.0
         shear_x = _uniform(g, *a["shear"]) if a["shear"] is not None else 0.0
         p.draws.update(angle=angle, translate=(tx, ty), scale=scale, shear=(shear_x, 0.0))
-        p.affine = tuple(inverse_affine_matrix([cols * 0.5, rows * 0.5], angle, (tx, ty), scale, (shear_x, 0.0)))
-        _check_fixed(p.affine, rows, cols)
     if "jitter" in spec:
         perm = torch.randperm(4, generator=g).tolist()
         f = [None if r is None else _uniform(g, *r) for r in spec["jitter"]]
@@ -159,6 +153,23 @@ def draw_params(policy: str, generator: torch.Generator, rows: int, cols: int) -
         if rows < 2:
             raise ValueError("HIPT_blur: reflect padding needs at least 2 rows")
         p.blur_sigma = _uniform(g, *spec["blur"])
+    return p
+
+
+def draw_params(policy: str, generator: torch.Generator, rows: int, cols: int) -> RegionParams:
+    """Draw one region's parameters in torchvision's order (``draw_spec``); the affine is Pillow's AFFINE data about the image
+    centre ``[cols / 2, rows / 2]``."""
+    if policy not in POLICIES:
+        raise ValueError(f"unknown augmentation policy {policy!r}; known: {sorted(POLICIES)}")
+    spec = POLICIES[policy]
+    p = RegionParams()
+    if spec is None:
+        return p
+    draw_spec(spec, generator, rows, cols, p)
+    if "affine" in spec:
+        d = p.draws
+        p.affine = tuple(inverse_affine_matrix([cols * 0.5, rows * 0.5], d["angle"], d["translate"], d["scale"], d["shear"]))
+        _check_fixed(p.affine, rows, cols)
     return p
 
 

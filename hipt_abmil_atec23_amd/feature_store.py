@@ -225,14 +225,20 @@ def extract_slide_augmented(model, batches: Iterable[Tuple[torch.Tensor, torch.T
     (``augment.RegionAugment(policy, seed)``: region i of the slide gets the parameters seeded by (seed, slide_id, k, i)) and
     through ``model`` again -> ``pt_files/{slide}aug{k}.pt``, the files ``Generic_MIL_Dataset(use_augs=True)`` reads
     (datasets/dataset_generic.py:497-507).  Each file has its coords sidecar.  Regions must be raw uint8 RGB (the reference
-    augments before eval_transforms): float regions raise ``ValueError``.  Returns the written ``.pt`` paths, original first."""
-    from .augment import POLICIES, RegionAugment
+    augments before eval_transforms): float regions raise ``ValueError``.  Returns the written ``.pt`` paths, original first.
 
-    if policy not in POLICIES:
-        raise ValueError(f"unknown augmentation policy {policy!r}; known: {sorted(POLICIES)}")
+    ``policy`` ``"all"`` / ``"spatial"`` (the ResNet routes' two policies, ``tensor_augment.TensorAugment``) augment in tensor
+    space: the augmented copy reaches ``model`` as the normalised float32 planar tensor the reference's Compose ends in, and the
+    un-augmented file is still the model's plain run on the uint8 regions."""
+    from .augment import POLICIES, RegionAugment
+    from .tensor_augment import TENSOR_POLICIES, TensorAugment
+
+    if policy not in POLICIES and policy not in TENSOR_POLICIES:
+        raise ValueError(f"unknown augmentation policy {policy!r}; known: {sorted(POLICIES)} (uint8, before eval_transforms) and "
+                         f"{sorted(TENSOR_POLICIES)} (tensor space, normalised float32 out)")
     if n_augs < 0 or (n_augs == 0 and not include_original):
         raise ValueError(f"n_augs={n_augs}, include_original={include_original}: nothing to write")
-    aug = RegionAugment(policy, seed)
+    aug = TensorAugment(policy, seed) if policy in TENSOR_POLICIES else RegionAugment(policy, seed)
     writers = ([FeatureWriter(feat_dir, slide_id)] if include_original else []) + \
               [FeatureWriter(feat_dir, f"{slide_id}aug{k}") for k in range(1, n_augs + 1)]
 

@@ -534,6 +534,37 @@ int hipt_augment_regions(const uint8_t* src, int interleaved, int n, int rows, i
                          uint8_t* dst, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Tensor-space region augmentation (extract_features_fp.py:63-82, --use_transforms all / spatial): uint8 RGB in, normalised
+ * float32 out, one parameter record per region drawn by the caller.  The reference's Compose puts ToTensor first, so this is
+ * torchvision's TENSOR path in float32: x = u8 / 255; HFlip / VFlip; RandomAffine as a normalised grid read
+ * through grid_sample(nearest, zeros, align_corners=False); ColorJitter's float blends and float HSV hue shift (mean grey of the
+ * whole region for contrast); (x - mean) / std.  Added under ABI 6: additive; hipt_augment_params is untouched.
+ * flags: HIPT_AUG_HFLIP / _VFLIP / _AFFINE (flips act on the source, then the affine; BLUR is not read); ops: HIPT_AUG_BRIGHTNESS..
+ * ---------------------------------------------------------------------------------- */
+typedef struct hipt_tensor_augment_params {
+    float   theta[6];    /* inverse affine matrix about the image centre (output -> input, centred pixel units), read when AFFINE */
+    float   factor[3];   /* blend ratios of brightness, contrast, saturation                                                     */
+    float   hue;         /* added to the HSV hue in [0, 1), modulo 1                                                             */
+    int32_t flags;       /* HIPT_AUG_HFLIP | HIPT_AUG_VFLIP | HIPT_AUG_AFFINE                                                     */
+    int32_t n_ops;       /* colour ops applied, 0..4                                                                             */
+    int32_t ops[4];      /* HIPT_AUG_BRIGHTNESS.. in application order                                                           */
+    float   mean[3];     /* Normalize: (x - mean) / std per channel                                                              */
+    float   std[3];
+    int32_t reserved[2]; /* pads the record to 96 bytes                                                                          */
+} hipt_tensor_augment_params;
+
+/* workspace of hipt_augment_tensor: one float64 partial sum of grey per workgroup of the summing pass (0 outside the envelope) */
+size_t hipt_augment_tensor_workspace_bytes(int n, int rows, int cols);
+/* src uint8 [n,3,rows,cols] (interleaved = 0) or [n,rows,cols,3] (interleaved = 1); dst float32 planar [n,3,rows,cols]; params: n
+ * DEVICE records.  ws: hipt_augment_tensor_workspace_bytes(n, rows, cols) bytes, 256-byte aligned: two launches (sum, then finish).
+ * ws NULL with ws_bytes 0 is the caller's statement that no record holds HIPT_AUG_CONTRAST: one launch, and a record that breaks
+ * the statement has its region written as NaN.  HIPT_E_BADARG before any launch for a missing pointer, n < 1, rows cols < 1 or
+ * > 2^30, params / dst not 4-byte aligned, src and dst overlapping; HIPT_E_WORKSPACE for a short or misaligned ws.  A region's
+ * output depends on its own bytes and record only and is the same from run to run (fixed-order float64 sums, no atomics). */
+int hipt_augment_tensor(const uint8_t* src, int interleaved, int n, int rows, int cols, const hipt_tensor_augment_params* params,
+                        float* dst, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * ResNet-50 baseline feature extractor (models/resnet_custom.py:ResNet_Baseline, resnet50_baseline; the default route of
  * extract_features_fp.py:187,210-211): stem conv 7x7/2 + BN + ReLU, maxpool 3x3/2, layer1..layer3 of Bottleneck_Baseline
  * (stride on conv2), AdaptiveAvgPool2d(1) -> [n, 1024] fp32.  Eval-mode BatchNorm only (running statistics), folded into
