@@ -6,6 +6,8 @@ forwards go through the coarse entry points (one C call per ViT / region / bag).
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _native as N
@@ -84,6 +86,36 @@ def attention(qkv: torch.Tensor, num_heads: int, scale: float, dtype: int = N.HI
     return out, probs
 
 
+# ---- CLAM on one bag (include/hipt_abmil.h: hipt_clam_sb_forward, hipt_clam_mb_forward) ----
+# form -> (native call, its workspace size, workspace slot, shapes of (A_raw, M, logits) for n rows, does the call write Y_prob / Y_hat)
+_FORMS = {
+    "sb": ("hipt_clam_sb_forward", "hipt_clam_workspace_bytes", "clam", lambda w, n: ((1, n), (1, w.s1), (1, w.n_classes)), True),
+    "mb": ("hipt_clam_mb_forward", "hipt_clam_mb_workspace_bytes", "clam_mb", lambda w, n: ((w.n_att, n), (w.n_att, w.s1), (1, w.n_att)), False),
+}
+
+
+def clam_forward(w, bag: torch.Tensor, attention_only: bool = False, out=None, ws=None, form: str = "sb"):
+    """The single-bag CLAM forward in the form ``"sb"`` or ``"mb"`` (the ``K = w.n_att`` branches of a stacked weight image in one pass) on
+    ``bag [n >= 1, S0]``, contiguous, on the device, in the dtype of the weight image ``w``: NOT checked here, ``CLAM_SB._infer`` has.
+    Returns ``(A_raw, M, logits, Y_prob, Y_hat)``; ``"mb"`` has no ``Y_prob`` / ``Y_hat`` (None: softmax and argmax over the K logits are
+    the caller's), ``attention_only`` only ``A_raw``.  ``out``: the five to write into instead of fresh buffers; ``w`` and ``out`` may be
+    lists of equal length: one call per pair on one stream and workspace (``CLAM_MB`` branch by branch, into row views of shared outputs).
+    ``ws``: a zeroed workspace instead of the stream's own (it carries the partials and the finish ticket, left at zero by every call)."""
+    sym, ws_sym, slot, shapes, heads = _FORMS[form]
+    dev, n, st = bag.device, bag.shape[0], N.stream_ptr(bag.device)
+    if ws is None:
+        ws = workspace(dev, getattr(N.lib(), ws_sym)(C.byref(w[0] if isinstance(w, list) else w), n), (slot, st.value), zero=True)
+    if out is None:
+        (a, m, l), e = shapes(w, n), torch.empty
+        out = ((e(a, dtype=torch.float32, device=dev), None, None, None, None) if attention_only else
+               (e(a, dtype=torch.float32, device=dev), e(m, dtype=torch.float32, device=dev), e(l, dtype=torch.float32, device=dev)) +
+               ((e(l, dtype=torch.float32, device=dev), e((1, 1), dtype=torch.int64, device=dev)) if heads else (None, None)))
+    for w, (A_raw, M, logits, Y_prob, Y_hat) in (zip(w, out) if isinstance(w, list) else ((w, out),)):
+        own = (N.ptr(Y_prob), N.ptr(Y_hat)) if heads else ()
+        N.call(sym, C.byref(w), N.ptr(bag), n, 1 if attention_only else 0, N.ptr(A_raw), N.ptr(M), N.ptr(logits), *own, N.ptr(ws), ws.numel(), st)
+    return out
+
+
 # ---- CLAM over many bags in one call (include/hipt_abmil.h: hipt_clam_sb_forward_bags and its narrow / CLAM_MB forms) ----
 def check_offsets(offsets, rows: int) -> tuple:
     """The B+1 row offsets of a multi-bag call as a tuple of ints, or ``ValueError``: they start at 0, increase strictly (no
@@ -131,7 +163,6 @@ def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only:
     in the dtype of the weight image ``w`` (an ``_native.ClamWeights``).  Returns ``(A_raw, M, logits, Y_prob, Y_hat)`` -- the last
     four ``None`` with ``attention_only``.  ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions,
     sentinels)."""
-    import ctypes as C
     sym, ws_sym, shapes = _BAGS_FORMS[form]
     what = sym[len("hipt_"):]
     N.require_cuda(cat, what)

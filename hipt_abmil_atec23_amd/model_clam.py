@@ -402,9 +402,13 @@ class CLAM_SB(WeightImageCache, nn.Module):
     def _cls_tensors(self):
         return [self.classifiers.weight, self.classifiers.bias]
 
-    def _train_forward(self, h, label, instance_eval, return_features, attention_only):
+    def _check_bag(self, h):
         if h.dim() != 2 or h.shape[0] == 0 or h.shape[1] != self._sizes[0]:
             raise ValueError(f"expected a non-empty [N, {self._sizes[0]}] bag, got {tuple(h.shape)}")
+
+    def _train_forward(self, h, label, instance_eval, return_features, attention_only):
+        N.same_device(type(self).__name__, h.device, *self.parameters())
+        self._check_bag(h)
         fc1, gated = self.attention_net[0], self.attention_net[-1]
         wa, wb, wc = gated.attention_a[0], gated.attention_b[0], gated.attention_c
         n, (S0, S1, S2), K = h.shape[0], self._sizes, wc.out_features
@@ -426,12 +430,10 @@ class CLAM_SB(WeightImageCache, nn.Module):
         return logits, Y_prob, Y_hat, A_raw, results
 
     def _use_train_kernels(self, h, dropout_on) -> bool:
-        if not self._gate or not h.is_cuda:
-            return False
+        if not self._gate or not h.is_cuda or not (dropout_on or _needs_autograd(self, h)):
+            return False  # (asked first: an inference forward does not pay for the library's answer below)
         K = self.attention_net[-1].attention_c.out_features
-        if not _train_supported(self._sizes, K, self.n_classes, need_dbag=torch.is_grad_enabled() and h.requires_grad):
-            return False
-        return dropout_on or _needs_autograd(self, h)
+        return _train_supported(self._sizes, K, self.n_classes, need_dbag=torch.is_grad_enabled() and h.requires_grad)
 
     # ---- HIP inference path ---------------------------------------------------------------------------
     def _pack(self, device):
@@ -442,55 +444,57 @@ class CLAM_SB(WeightImageCache, nn.Module):
                                  n_classes=self.classifiers.out_features)
         return self._cached(device, (), build)[0]
 
-    def forward(self, h, label=None, instance_eval=False, return_features=False, attention_only=False):
+    def _route(self, h) -> str:
+        """Which path ``forward`` takes on ``h``.  ``'train'``: the training kernels.  ``'torch'``: whatever those do not take (ungated head,
+        CPU tensors, > 8 classes, widths beyond their LDS) keeps the PyTorch-op sequence as soon as dropout is active or a gradient is
+        needed -- the inference kernels have neither -- and so does a bag the caller keeps on the CPU (the reference's relocate() chooses
+        the CPU where there is no GPU, models/model_clam.py:102-106): PyTorch ops on the CPU.  ``'infer'``: the rest; a bag on a HIP device
+        never comes to ``'torch'`` this way (a CPU bag handed to a module on a HIP device is a caller's mistake and raises in ``_infer``)."""
         dropout_on = self.training and self._dropout > 0
         if self._use_train_kernels(h, dropout_on):
-            N.same_device(type(self).__name__, h.device, *self.parameters())
-            return self._train_forward(h, label, instance_eval, return_features, attention_only)
-        # whatever the training kernels do not take (ungated head, CPU tensors, > 8 classes, widths beyond their LDS) keeps the
-        # PyTorch-op sequence as soon as dropout is active or a gradient is needed: the inference kernels have neither
-        # ... and so does a bag the caller keeps on the CPU (the reference's relocate() chooses the CPU where there is no GPU,
-        # models/model_clam.py:102-106): PyTorch ops on the CPU.  A bag on a HIP device never comes this way.
-        # (a CPU bag handed to a module that lives on a HIP device is a caller's mistake and raises below)
+            return 'train'
         if not self._gate or dropout_on or _needs_autograd(self, h) or _all_on_cpu(self, h):
-            return self._torch_forward(h, label, instance_eval, return_features, attention_only)
-        if self._multi:
-            return self._multi_infer(h, label, instance_eval, return_features, attention_only)
-        N.require_cuda(h, "CLAM_SB")
-        if h.dim() != 2 or h.shape[0] == 0:
-            raise ValueError(f"expected a non-empty [N, {self.attention_net[0].in_features}] bag, got {tuple(h.shape)}")
-        w = self._pack(h.device)
-        if h.shape[1] != w.s0:
-            raise ValueError(f"bag width {h.shape[1]} != model input width {w.s0}")
-        dev = h.device
-        bag = Fn.as_compute(h, w.dtype)
-        n = bag.shape[0]
-        A_raw = torch.empty((1, n), dtype=torch.float32, device=dev)
-        st = N.stream_ptr(dev)
-        # one scratch (partials + finish ticket) per stream: two CLAM calls on two streams must not share them
-        ws = Fn.workspace(dev, N.lib().hipt_clam_workspace_bytes(C_.byref(w), n), ("clam", st.value), zero=True)
+            return 'torch'
+        return 'infer'
+
+    def forward(self, h, label=None, instance_eval=False, return_features=False, attention_only=False):
+        route = self._route(h)
+        run = self._infer if route == 'infer' else self._train_forward if route == 'train' else self._torch_forward
+        return run(h, label, instance_eval, return_features, attention_only)
+
+    def _infer_plan(self, device, n, attention_only):
+        """``(weights, form, views, w_gather, out)`` of ``_infer`` on ``n`` rows: what ``functional.clam_forward`` is called with (lists: one call
+        per pair), the weights to gather h1 rows with, and the outputs the calls fill between them (None: what the one call returns)."""
+        w = self._pack(device)
+        return w, "sb", None, w, None
+
+    def _infer(self, h, label, instance_eval, return_features, attention_only):
+        """model_clam.py:147-191 / :226-264 without autograd, for both classes: A [K, N] -> softmax over N per branch -> M [K, S1] ->
+        logits, K = 1 for ``CLAM_SB``."""
+        N.require_cuda(h, type(self).__name__)
+        self._check_bag(h)
+        dev, n = h.device, h.shape[0]
+        w, form, views, wg, out = self._infer_plan(dev, n, attention_only)
+        bag = h if h.dtype == Fn.torch_dtype(wg.dtype) and h.is_contiguous() else Fn.as_compute(h, wg.dtype)   # (only its address is used)
+        got = Fn.clam_forward(w, bag, attention_only, views, form=form)
+        A_raw, M, logits, Y_prob, Y_hat = got if out is None else out
         if attention_only:
-            N.call("hipt_clam_sb_forward", C_.byref(w), N.ptr(bag), n, 1, N.ptr(A_raw), None, None, None, None,
-                   N.ptr(ws), ws.numel(), st)
             return A_raw
-        M = torch.empty((1, w.s1), dtype=torch.float32, device=dev)
-        logits = torch.empty((1, w.n_classes), dtype=torch.float32, device=dev)
-        Y_prob = torch.empty_like(logits)
-        Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
-        N.call("hipt_clam_sb_forward", C_.byref(w), N.ptr(bag), n, 0, N.ptr(A_raw), N.ptr(M), N.ptr(logits), N.ptr(Y_prob),
-               N.ptr(Y_hat), N.ptr(ws), ws.numel(), st)
+        if Y_hat is None:  # the K-branch calls leave these to the host (:251-252, on K numbers); CLAM_SB keeps the kernel's own
+            Y_hat = torch.topk(logits, 1, dim=1)[1]
+            Y_prob = F.softmax(logits, dim=1)
         results = {}
         if instance_eval:
-            # inst_eval in eval mode (validate_clam, core_utils.py:506-560): top-k ids on the device (softmax is monotone:
-            # the ids of A_raw are those of softmax(A_raw)), then only the 2k selected rows of h1 are recomputed by the
-            # library instead of materialising h1 [N,S1]
-            if self.k_sample > n:
-                raise RuntimeError(f"selected index k out of range: k_sample={self.k_sample} > {n} rows (torch.topk, model_clam.py:120)")
-            ids = torch.empty((1, 2, self.k_sample), dtype=torch.int64, device=dev)
-            N.call("hipt_topk_rows", N.ptr(A_raw), 1, n, self.k_sample, N.ptr(ids), st)
-            rows = torch.empty((2 * self.k_sample, w.s1), dtype=torch.float32, device=dev)
-            N.call("hipt_clam_gather_h1", C_.byref(w), N.ptr(bag), N.ptr(ids), 2 * self.k_sample, N.ptr(rows), st)
-            results = self._instance_branch(lambda b: (rows[:self.k_sample], rows[self.k_sample:]), label)
+            # inst_eval in eval mode (validate_clam, core_utils.py:506-560): top-k / bottom-k ids per branch on the device (softmax is monotone:
+            # the ids of A_raw are those of softmax(A_raw)), then the library recomputes only the 2 K k selected rows of h1, not h1 [N, S1]
+            K, k, st = A_raw.shape[0], self.k_sample, N.stream_ptr(dev)
+            if k > n:
+                raise RuntimeError(f"selected index k out of range: k_sample={k} > {n} rows (torch.topk, model_clam.py:120)")
+            ids = torch.empty((K, 2, k), dtype=torch.int64, device=dev)
+            N.call("hipt_topk_rows", N.ptr(A_raw), K, n, k, N.ptr(ids), st)
+            rows = torch.empty((K, 2, k, wg.s1), dtype=torch.float32, device=dev)
+            N.call("hipt_clam_gather_h1", C_.byref(wg), N.ptr(bag), N.ptr(ids), 2 * K * k, N.ptr(rows), st)
+            results = self._instance_branch(lambda b: (rows[b, 0], rows[b, 1]), label)   # (b = 0 for CLAM_SB's one branch)
         if return_features:
             results.update({'features': M})
         return logits, Y_prob, Y_hat, A_raw, results
@@ -719,7 +723,7 @@ class CLAM_MB(CLAM_SB):
     ``gate=False`` and CPU tensors take the PyTorch-op sequence."""
 
     _multi = True
-    one_pass = True  # inference takes hipt_clam_mb_forward (one pass over the bag for all branches) where the library has it; False: branch by branch
+    one_pass = True  # inference takes the "mb" form of functional.clam_forward (one pass over the bag for all branches) where the library has it; False: branch by branch
     bags_one_call = False  # forward_bags takes hipt_clam_mb_forward_bags (all bags, all branches in one call) where the library has it; False: the loop over forward
 
     def __init__(self, gate=True, size_arg="small", dropout=0.0, k_sample=8, n_classes=2,
@@ -763,61 +767,20 @@ class CLAM_MB(CLAM_SB):
         one-pass streaming kernel says about it: what ``hipt_clam_mb_forward_bags`` takes.  The same cache entry."""
         return self._pack_branches(device, stacked=True)
 
-    def _multi_infer(self, h, label, instance_eval, return_features, attention_only):
-        """model_clam.py:226-264 without autograd: A [K, N] -> softmax over N per branch -> M [K, S1] -> logits[0, c] =
-        classifiers[c](M[c]) -- branch by branch through the CLAM_SB inference kernels."""
-        N.require_cuda(h, "CLAM_MB")
-        if h.dim() != 2 or h.shape[0] == 0 or h.shape[1] != self._sizes[0]:
-            raise ValueError(f"expected a non-empty [N, {self._sizes[0]}] bag, got {tuple(h.shape)}")
-        ws, mb = self._pack_branches(h.device)
-        if not self.one_pass:
-            mb = None
-        dev, K, n = h.device, self.n_classes, h.shape[0]
-        bag = Fn.as_compute(h, ws[0].dtype)
-        st = N.stream_ptr(dev)
-        A_raw = torch.empty((K, n), dtype=torch.float32, device=dev)
-        S1 = self._sizes[1]
-        if mb is not None:
-            # ONE pass over the bag: gate once per row, K logits, h1 left in bf16 for the pooling kernel (two launches instead of K)
-            scratch = Fn.workspace(dev, N.lib().hipt_clam_mb_workspace_bytes(C_.byref(mb), n), ("clam_mb", st.value), zero=True)
-            if attention_only:
-                N.call("hipt_clam_mb_forward", C_.byref(mb), N.ptr(bag), n, 1, N.ptr(A_raw), None, None, N.ptr(scratch), scratch.numel(), st)
-                return A_raw
-            M = torch.empty((K, S1), dtype=torch.float32, device=dev)
-            logits = torch.empty((1, K), dtype=torch.float32, device=dev)
-            N.call("hipt_clam_mb_forward", C_.byref(mb), N.ptr(bag), n, 0, N.ptr(A_raw), N.ptr(M), N.ptr(logits), N.ptr(scratch), scratch.numel(), st)
-            return self._multi_finish(logits, A_raw, M, ws, bag, n, label, instance_eval, return_features)
-        scratch = Fn.workspace(dev, N.lib().hipt_clam_workspace_bytes(C_.byref(ws[0]), n), ("clam", st.value), zero=True)
+    def _infer_plan(self, device, n, attention_only):
+        """ONE pass over the bag for all branches (gate once per row, K logits, h1 left in bf16 for the pooling kernel: two launches
+        instead of K) where ``one_pass`` is set and the library takes the stacked image; else branch by branch through the
+        ``CLAM_SB`` kernels, each call into its rows of the shared outputs (logits[0, c] = classifiers[c](M[c]), :248-250)."""
+        ws, mb = self._pack_branches(device)
+        if self.one_pass and mb is not None:
+            return mb, "mb", None, ws[0], None
+        K, e = self.n_classes, lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=device)
+        A_raw = e((K, n))
         if attention_only:
-            for k, w in enumerate(ws):
-                N.call("hipt_clam_sb_forward", C_.byref(w), N.ptr(bag), n, 1, N.ptr(A_raw[k]), None, None, None, None, N.ptr(scratch), scratch.numel(), st)
-            return A_raw
-        M = torch.empty((K, S1), dtype=torch.float32, device=dev)
-        logits = torch.empty((1, K), dtype=torch.float32, device=dev)
-        junk_p = torch.empty((K,), dtype=torch.float32, device=dev)      # (the one-class softmax / argmax of a branch: 1 and 0)
-        junk_y = torch.empty((K,), dtype=torch.int64, device=dev)
-        for k, w in enumerate(ws):
-            N.call("hipt_clam_sb_forward", C_.byref(w), N.ptr(bag), n, 0, N.ptr(A_raw[k]), N.ptr(M[k]), N.ptr(logits[0, k:k + 1]), N.ptr(junk_p[k:k + 1]),
-                   N.ptr(junk_y[k:k + 1]), N.ptr(scratch), scratch.numel(), st)
-        return self._multi_finish(logits, A_raw, M, ws, bag, n, label, instance_eval, return_features)
-
-    def _multi_finish(self, logits, A_raw, M, ws, bag, n, label, instance_eval, return_features):
-        dev, K, S1, st = bag.device, self.n_classes, self._sizes[1], N.stream_ptr(bag.device)
-        Y_hat = torch.topk(logits, 1, dim=1)[1]      # :251-252, on K numbers
-        Y_prob = F.softmax(logits, dim=1)
-        results = {}
-        if instance_eval:
-            # validate_clam (core_utils.py:506-560): top-k / bottom-k ids per branch on the device, only the selected h1 rows recomputed
-            if self.k_sample > n:
-                raise RuntimeError(f"selected index k out of range: k_sample={self.k_sample} > {n} rows (torch.topk, model_clam.py:120)")
-            ids = torch.empty((K, 2, self.k_sample), dtype=torch.int64, device=dev)
-            N.call("hipt_topk_rows", N.ptr(A_raw), K, n, self.k_sample, N.ptr(ids), st)
-            rows = torch.empty((K, 2, self.k_sample, S1), dtype=torch.float32, device=dev)
-            N.call("hipt_clam_gather_h1", C_.byref(ws[0]), N.ptr(bag), N.ptr(ids), 2 * K * self.k_sample, N.ptr(rows), st)
-            results = self._instance_branch(lambda b: (rows[b, 0], rows[b, 1]), label)
-        if return_features:
-            results.update({'features': M})
-        return logits, Y_prob, Y_hat, A_raw, results
+            return ws, "sb", [(A_raw[k], None, None, None, None) for k in range(K)], ws[0], (A_raw, None, None, None, None)
+        M, logits, junk_p, junk_y = e((K, self._sizes[1])), e((1, K)), e((K,)), e((K,), torch.int64)   # (junk: the one-class softmax / argmax of a branch, 1 and 0)
+        views = [(A_raw[k], M[k], logits[0, k:k + 1], junk_p[k:k + 1], junk_y[k:k + 1]) for k in range(K)]
+        return ws, "sb", views, ws[0], (A_raw, M, logits, None, None)
 
     def _bag_logits(self, M):  # :248-250
         logits = torch.empty(1, self.n_classes).float().to(M.device)
