@@ -71,6 +71,8 @@ _LAZY = {
     "saturation_u8": ("segment", "saturation_u8"), "median_blur_u8": ("segment", "median_blur_u8"),
     "otsu_threshold": ("segment", "otsu_threshold"), "morph_close_u8": ("segment", "morph_close_u8"),
     "contour_area": ("segment", "contour_area"), "filter_contours": ("segment", "filter_contours"),
+    # cv2.findContours(mask, RETR_CCOMP, CHAIN_APPROX_NONE) on the device: the step between the mask and the contour filter
+    "trace_contours": ("segment", "trace_contours"), "find_contours": ("segment", "find_contours"),
 }
 
 

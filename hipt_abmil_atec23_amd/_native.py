@@ -91,6 +91,7 @@ TILE_BASIC, TILE_CENTER, TILE_FOUR_PT, TILE_FOUR_PT_HARD = 0, 1, 2, 3           
 TILING_COORD_BOUND, TILING_EDGE_CHUNK, TILING_TILE, TILING_CONTOUR_INTS = 1 << 30, 1024, 256, 9   # HIPT_TILING_*
 RESIZE_ROUTE_AUTO, RESIZE_ROUTE_GENERAL, RESIZE_ROUTE_FUSED, RESIZE_MAX_KSIZE = 0, 1, 2, 512      # HIPT_RESIZE_*
 SEGMENT_MAX_MEDIAN, SEGMENT_MAX_CLOSE = 15, 128                                                   # HIPT_SEGMENT_MAX_*
+CONTOURS_MAX_PLANE, CONTOURS_MAX_BORDER_PIXELS, CONTOURS_MAX_BORDERS = 1 << 27, 1 << 24, 1 << 22                # HIPT_CONTOURS_MAX_*
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -207,6 +208,9 @@ SIGNATURES = {
     "hipt_segment_median": (_i, [_p, _i, _i, _i, _p, _p]),
     "hipt_segment_otsu": (_i, [_p, _i, _i, _p, _p, _p]),
     "hipt_segment_close": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
+    "hipt_contours_workspace_bytes": (_sz, [_i, _i]),
+    "hipt_contours_trace": (_i, [_p, _i, _i, _p, _p, _sz, _p]),
+    "hipt_contours_emit": (_i, [_i, _i, _p, _p, _i, _i, _p, _p, _sz, _p]),
 }
 
 _lib = None

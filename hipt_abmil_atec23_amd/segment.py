@@ -4,12 +4,16 @@
 calls -- ``cvtColor(RGB2HSV)``'s saturation, ``medianBlur``, ``threshold`` (fixed or Otsu), ``morphologyEx(MORPH_CLOSE)`` -- traces
 its contours and filters them by area.  The four pixel stages are 8-bit integer work (Otsu: integer counts and a short float64
 scan), restated from OpenCV's published implementation and run on the device: ``tissue_mask`` is one native call, the stage
-functions expose each step.  Contour tracing (``cv2.findContours``, a sequential border follower) stays on the host:
-``segment_tissue`` takes the tracer as ``find_contours=`` and imports cv2 only when none is given.  The area filter
-(``filter_contours``, ``contour_area``) is pure numpy.
+functions expose each step.  Contour tracing (``cv2.findContours(mask, RETR_CCOMP, CHAIN_APPROX_NONE)``) runs on the device too
+(csrc/contours.hip): ``trace_contours`` keeps the points there, ``find_contours`` returns cv2's format and is what to
+hand ``segment_tissue`` as ``find_contours=``; with None it imports cv2, as before.  The area filter (``filter_contours``,
+``contour_area``) is pure numpy.
 
 cv2 is not a dependency and was not available to compare against: agreement with cv2's own bytes is argued from OpenCV's source
 (DESIGN.md 26), not measured; the tests compare with a numpy restatement of the same definitions (tests/segment_ref.py).
+For the contours: the set of borders and every border's point sequence follow the published algorithm (Suzuki and Abe 1985) and
+equal a sequential restatement of it (tests/contour_ref.py); the ORDER of the list, and agreement with cv2's own return values,
+are argued from OpenCV's source and not measured.
 """
 from __future__ import annotations
 
@@ -108,6 +112,107 @@ def morph_close_u8(x, size, out=None, device=None):
     return out
 
 
+# ---- contours ------------------------------------------------------------------------------------------------------------------
+def _order_borders(start, kind, parent):
+    """The ONE place that decides the order of the list (argued from OpenCV's tree insertion, not measured against cv2): top-level
+    borders in descending raster order of their start pixel, each followed at once by its hole borders in descending raster order
+    of theirs.  ``start`` / ``parent`` are pixel numbers ``y * W + x`` (``parent``: the start of the outer border a hole lies on),
+    ``kind`` is 0 outer / 1 hole.  Returns the permutation: ``order[j]`` is the table row of the j-th border of the list."""
+    top = np.where(kind == 0, start, parent)
+    return np.lexsort((-start, kind, -top))
+
+
+def _hierarchy(kind) -> np.ndarray:
+    """int32 ``[C, 4]`` = ``[next, previous, first_child, parent]`` of a list in ``_order_borders``' order (``kind`` in that order):
+    two levels, siblings linked in list order, -1 for none."""
+    c = len(kind)
+    idx = np.arange(c)
+    hier = np.full((c, 4), -1, dtype=np.int32)
+    outer = np.flatnonzero(kind == 0)
+    hier[outer[:-1], 0] = outer[1:]
+    hier[outer[1:], 1] = outer[:-1]
+    hole = kind == 1
+    after_hole = np.append(hole[1:], False)    # the next border of the list is a hole
+    before_hole = np.insert(hole[:-1], 0, False)
+    hier[hole & after_hole, 0] = idx[hole & after_hole] + 1
+    hier[hole & before_hole, 1] = idx[hole & before_hole] - 1
+    hier[~hole & after_hole, 2] = idx[~hole & after_hole] + 1
+    hier[hole, 3] = np.maximum.accumulate(np.where(hole, -1, idx))[hole]
+    return hier
+
+
+def _check_mask(what: str, mask) -> None:
+    if not isinstance(mask, np.ndarray) and not F.is_tensor(mask):
+        raise ValueError(f"{what}: the mask is a numpy array or a device tensor, got {type(mask).__name__}")
+    shape = [int(v) for v in mask.shape]
+    if str(mask.dtype).replace("torch.", "") != "uint8" or len(shape) != 2:
+        raise ValueError(f"{what}: the mask is uint8 [H, W], got {mask.dtype} {shape}")
+    if shape[0] < 1 or shape[1] < 1 or (shape[0] + 2) * (shape[1] + 2) > N.CONTOURS_MAX_PLANE:
+        raise ValueError(f"{what}: a mask of {shape[0]} x {shape[1]}: at least one pixel, and (H + 2) * (W + 2) at most "
+                         f"{N.CONTOURS_MAX_PLANE} (8192 x 8192 is inside)")
+
+
+def trace_contours(mask, device=None):
+    """``cv2.findContours(mask, cv2.RETR_CCOMP, cv2.CHAIN_APPROX_NONE)`` with the result left on the device: ``(points int32 [P, 2]
+    of (x, y), offsets int64 [C + 1], hierarchy int32 [C, 4])``; contour ``j`` is ``points[offsets[j]:offsets[j + 1]]``, a row of
+    ``hierarchy`` is ``[next, previous, first_child, parent]``.  ``mask``: uint8 ``[H, W]``, a numpy array or a device tensor; any
+    non-zero byte is foreground, and foreground may touch the edge.  Suzuki-Abe border following, foreground 8-connected and
+    background 4-connected (the header states the rules); the same mask gives the same bytes in every run.  The set of borders and
+    every border's points follow the published algorithm; the order of the list (``_order_borders``) and agreement with cv2's own
+    return values are argued, not measured.  Two native calls on the current stream with ONE small read-back between them (the
+    table of borders), so the call synchronises and cannot be captured into a graph.  ValueError -- before any native call -- for
+    another dtype or rank, a CPU tensor, an empty plane or one with ``(H + 2) * (W + 2)`` above 2^27; RuntimeError after the
+    read-back for a plane of more than 2^22 pixels that holds more than 2^24 border pixels or 2^22 borders."""
+    import torch
+    what = "trace_contours"
+    _check_mask(what, mask)
+    x = F.as_device_u8(what, mask, device, dims=2)
+    h, w = (int(v) for v in x.shape)
+    dev = x.device
+    with torch.cuda.device(dev):
+        rows = min(h * w, N.CONTOURS_MAX_BORDERS) + 1
+        table = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+        ws, need = F.scratch("hipt_contours_workspace_bytes", h, w, dev=dev)
+        N.call("hipt_contours_trace", N.ptr(x), h, w, N.ptr(table), N.ptr(ws), need, N.stream_ptr(dev))
+        head = table[0].cpu().numpy()   # the read-back: (border pixels, borders, passes, unsettled)
+        nb, c = int(head[0]), int(head[1])
+        if nb > min(h * w, N.CONTOURS_MAX_BORDER_PIXELS) or c > rows - 1:
+            raise RuntimeError(f"{what}: {nb} border pixels / {c} borders in a mask of {h} x {w}: beyond the room of "
+                               f"{N.CONTOURS_MAX_BORDER_PIXELS} / {N.CONTOURS_MAX_BORDERS}")
+        if c == 0:
+            return (torch.empty((0, 2), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int64, device=dev),
+                    torch.empty((0, 4), dtype=torch.int32, device=dev))
+        tab = table[1:1 + c].cpu().numpy().astype(np.int64)
+        start, kind, length, parent = tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 3]
+        if (length < 1).any():
+            raise RuntimeError(f"{what}: a border of the {h} x {w} mask was not ranked (internal error)")
+        order = _order_borders(start, kind, parent)
+        offsets = np.zeros(c + 1, dtype=np.int64)
+        np.cumsum(length[order], out=offsets[1:])
+        p = int(offsets[-1])
+        where = np.empty(c, dtype=np.int32)
+        where[order] = offsets[:-1]
+        points = torch.empty((p, 2), dtype=torch.int32, device=dev)
+        where_dev = torch.from_numpy(where).to(dev)
+        N.call("hipt_contours_emit", h, w, N.ptr(table), N.ptr(where_dev), c, p, N.ptr(points), N.ptr(ws), need, N.stream_ptr(dev))
+        return points, torch.from_numpy(offsets).to(dev), torch.from_numpy(_hierarchy(kind[order])).to(dev)
+
+
+def find_contours(mask, device=None):
+    """``cv2.findContours(mask, cv2.RETR_CCOMP, cv2.CHAIN_APPROX_NONE)`` in cv2's return format, traced on the device
+    (``trace_contours``): ``(contours, hierarchy)``, a tuple of int32 ``[n, 1, 2]`` arrays and an int32 ``[1, C, 4]`` array; an empty
+    mask gives ``((), None)``.  Hand it to ``segment_tissue`` as ``find_contours=segment.find_contours``: the mask then stays on the
+    device.  What is argued and what is measured: see ``trace_contours``."""
+    points, offsets, hierarchy = trace_contours(mask, device)
+    if hierarchy.shape[0] == 0:
+        return (), None
+    pts, off = points.cpu().numpy(), offsets.cpu().numpy()
+    return tuple(pts[off[j]:off[j + 1]].reshape(-1, 1, 2) for j in range(len(off) - 1)), hierarchy.cpu().numpy()[None]
+
+
+find_contours.takes_device_mask = True   # segment_tissue hands such a tracer the device tensor, not the read-back copy
+
+
 # ---- host glue: pure numpy ------------------------------------------------------------------------------------------------------
 def contour_area(cont) -> float:
     """``cv2.contourArea(cont)``: the shoelace formula in float64 over the closed polygon ``cont`` (``[n, 1, 2]`` or ``[n, 2]``)."""
@@ -146,9 +251,9 @@ def _cv2_find_contours(mask):
     try:
         import cv2
     except ImportError:
-        raise ImportError("segment_tissue: cv2 is not installed and no tracer was given: pass find_contours=, a function that takes the "
-                          "uint8 mask [H, W] and returns (contours, hierarchy) as cv2.findContours(mask, cv2.RETR_CCOMP, "
-                          "cv2.CHAIN_APPROX_NONE) does") from None
+        raise ImportError("segment_tissue: cv2 is not installed and no tracer was given: pass find_contours=segment.find_contours, the "
+                          "device tracer of this package, or another function that takes the uint8 mask [H, W] and returns (contours, "
+                          "hierarchy) as cv2.findContours(mask, cv2.RETR_CCOMP, cv2.CHAIN_APPROX_NONE) does") from None
     return cv2.findContours(mask, cv2.RETR_CCOMP, cv2.CHAIN_APPROX_NONE)
 
 
@@ -157,12 +262,16 @@ def segment_tissue(wsi_object, seg_level=0, sthresh=20, sthresh_up=255, mthresh=
     """``WholeSlideImage.segmentTissue`` with the pixel stages on the device.  ``wsi_object`` has ``wsi.read_region``, ``level_dim``
     and ``level_downsamples`` as the reference's class does; its ``contours_tissue`` / ``holes_tissue`` are set, ready for
     ``tiling.process_contours_like``.  ``find_contours(mask)`` returns ``(contours, hierarchy)`` like ``cv2.findContours(mask,
-    cv2.RETR_CCOMP, cv2.CHAIN_APPROX_NONE)``; None imports cv2 and calls just that, or raises ImportError.  The mask is read back
-    once.  Bind it as the method with ``WholeSlideImage.segmentTissue = segment.segment_tissue``."""
+    cv2.RETR_CCOMP, cv2.CHAIN_APPROX_NONE)``; None imports cv2 and calls just that, or raises ImportError; ``segment.find_contours``
+    traces on the device and is handed the device mask (any tracer whose ``takes_device_mask`` attribute is true is), every other
+    tracer the mask read back once.  A tracer may return ``hierarchy`` None for no contours, as cv2 does.  Bind it as the method
+    with ``WholeSlideImage.segmentTissue = segment.segment_tissue``."""
     if find_contours is None:
         find_contours = _cv2_find_contours
     img = np.array(wsi_object.wsi.read_region((0, 0), seg_level, wsi_object.level_dim[seg_level]))
-    mask = tissue_mask(img, sthresh, sthresh_up, mthresh, close, use_otsu).cpu().numpy()
+    mask = tissue_mask(img, sthresh, sthresh_up, mthresh, close, use_otsu)
+    if not getattr(find_contours, "takes_device_mask", False):
+        mask = mask.cpu().numpy()
     scale = wsi_object.level_downsamples[seg_level]
     scaled_ref_patch_area = int(ref_patch_size ** 2 / (scale[0] * scale[1]))
     filter_params = dict(filter_params)
@@ -170,7 +279,7 @@ def segment_tissue(wsi_object, seg_level=0, sthresh=20, sthresh_up=255, mthresh=
         if key in filter_params:
             filter_params[key] = filter_params[key] * scaled_ref_patch_area
     contours, hierarchy = find_contours(mask)
-    hierarchy = np.asarray(hierarchy).reshape(-1, 4)[:, 2:]
+    hierarchy = np.zeros((0, 2), dtype=np.int32) if hierarchy is None else np.asarray(hierarchy).reshape(-1, 4)[:, 2:]
     foreground, holes = filter_contours(contours, hierarchy, filter_params)
     contours_tissue = [np.array(cont * scale, dtype="int32") for cont in foreground]
     holes_tissue = [[np.array(hole * scale, dtype="int32") for hole in hs] for hs in holes]

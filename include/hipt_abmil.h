@@ -36,7 +36,7 @@ extern "C" {
  * hipt_vit_mlp_unit added; formats 1 / HIPT_MLP32 are gone.
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
  * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) and the
- * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair, hipt_patch_render, the hipt_macenko_* five and the hipt_segment_* six were added later under the same
+ * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair, hipt_patch_render, the hipt_macenko_* five, the hipt_segment_* six and the hipt_contours_* three were added later under the same
  * number: additive, nothing existing changed. */
 #define HIPT_ABI_VERSION 6
 
@@ -982,7 +982,7 @@ int hipt_macenko_keys(const uint8_t* src, int interleaved, int R, int h, int w, 
 
 /* ----------------------------------------------------------------------------------
  * Tissue segmentation mask: the pixel stages of WholeSlideImage.segmentTissue (wsi_core/WholeSlideImage.py:111-203) up to the binary
- * mask.  Added under ABI 6: additive.  Contour tracing (cv2.findContours) stays on the host.
+ * mask.  Added under ABI 6: additive.  Contour tracing (cv2.findContours) is hipt_contours_* below.
  *
  * src: one uint8 image [h, w, channels], interleaved, channels 3 (RGB) or 4 (RGBA; the fourth channel is ignored).  Every plane below
  * is uint8 [h, w], contiguous.  The definitions, restated from OpenCV's published implementation:
@@ -1016,6 +1016,43 @@ int hipt_segment_saturation(const uint8_t* src, int h, int w, int channels, uint
 int hipt_segment_median(const uint8_t* src, int h, int w, int ksize, uint8_t* dst, void* stream);
 int hipt_segment_otsu(const uint8_t* src, int h, int w, int32_t* hist, int32_t* thresh, void* stream);
 int hipt_segment_close(const uint8_t* src, int h, int w, int close, uint8_t* dst, void* ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------
+ * Contour tracing: cv2.findContours(mask, RETR_CCOMP, CHAIN_APPROX_NONE) of a uint8 plane.  Added under ABI 6: additive.
+ *
+ * mask: uint8 [h, w], contiguous; any non-zero byte is foreground; the plane counts as surrounded by a one-pixel frame of zeros.
+ * Suzuki-Abe border following, foreground 8-connected, background 4-connected: one OUTER border per foreground component, from its
+ * raster-first pixel; one HOLE border per background component that does not reach the frame, from the foreground pixel west of the
+ * hole's raster-first pixel.  The first search runs clockwise on screen from the west (outer) or east (hole) neighbour and finds the
+ * border's LAST point; every later one runs counter-clockwise from just after the previous point; a point is listed once per visit.
+ *
+ * Two calls with ONE read-back of the caller's between them (the library itself never synchronises), so the pair cannot be
+ * captured into a graph:
+ *   hipt_contours_trace  labels, links and ranks every border on `stream` and writes `table`, int32 [1 + min(h w,
+ *                        HIPT_CONTOURS_MAX_BORDERS), 4], 16-byte aligned: row 0 = {border pixels B, borders C, ranking passes run,
+ *                        1 if the ranking did not settle}; row 1 + r, r < C, in raster order of the borders' root pixels =
+ *                        {start pixel y w + x, kind (0 outer, 1 hole), number of points, for a hole the start pixel of the outer
+ *                        border it lies on, else -1}.  A length of -1, or B / C above the room named below, means the request went
+ *                        beyond the envelope: the caller must not go on to hipt_contours_emit.
+ *   hipt_contours_emit   offsets int32 [n_borders]: where border r's points begin in the caller's order; n_borders = C, n_points = the
+ *                        sum of the lengths; writes points int32 [n_points, 2] = (x, y), 8-byte aligned.  `ws` is the workspace the
+ *                        trace call left, untouched in between.
+ * Envelope: (h + 2) (w + 2) <= HIPT_CONTOURS_MAX_PLANE (8192 x 8192 is inside), so every pixel index fits 27 bits and every state
+ * index (8 per border pixel) 31; room for min(h w, HIPT_CONTOURS_MAX_BORDER_PIXELS) border pixels and min(h w,
+ * HIPT_CONTOURS_MAX_BORDERS) borders, which no plane of up to 2^22 pixels can exceed.
+ * ws: hipt_contours_workspace_bytes(h, w) bytes (0 outside the envelope), 256-byte aligned.
+ * HIPT_E_BADARG before any launch for a missing pointer, a misaligned table / offsets / points, h or w < 1, counts outside the room;
+ * HIPT_E_UNSUPPORTED for a plane beyond the envelope; HIPT_E_WORKSPACE for a short or misaligned ws.
+ * Integers only; the only read-modify-write atomics are the labelling's atomicMin, whose result (a component's minimum index) does not
+ * depend on arrival order: the same mask gives the same bytes in every run.  No kernel follows a border point by point.
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_CONTOURS_MAX_PLANE 134217728
+#define HIPT_CONTOURS_MAX_BORDER_PIXELS 16777216
+#define HIPT_CONTOURS_MAX_BORDERS 4194304
+size_t hipt_contours_workspace_bytes(int h, int w);
+int hipt_contours_trace(const uint8_t* mask, int h, int w, int32_t* table, void* ws, size_t ws_bytes, void* stream);
+int hipt_contours_emit(int h, int w, const int32_t* table, const int32_t* offsets, int n_borders, int n_points, int32_t* points,
+                       const void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
