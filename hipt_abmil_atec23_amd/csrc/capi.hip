@@ -814,6 +814,27 @@ int hipt_vit_cls_block_unit(const hipt_vit_weights* w, const void* xn_img, const
     return HIPT_OK;
 }
 
+int hipt_vit_embed_unit(const hipt_vit_weights* w, const void* images, int input_kind, const hipt_image_layout* lay, int seq0, int nseq, float* x_out,
+                        void* xn_out_img, void* workspace, size_t ws_bytes, void* stream) {
+    int rc = check_vit(w);
+    if (rc) return rc;
+    HIPT_CHECK_ARG(images && lay && x_out && nseq > 0 && seq0 >= 0 && input_kind >= IMG_F32 && input_kind <= IMG_U8_HWC && (!xn_out_img || w->depth > 0),
+                   "vit_embed_unit: bad argument");
+    // the forwards' own question (vit256_forward_impl, hipt_vit256_forward_range_px), asked of a slot that is large enough: a short
+    // workspace is refused as a workspace below
+    if (!embed_fused_ok(w, images, lay, embed_px_slot_bytes(), input_kind) || (xn_out_img && ((int64_t)nseq * w->ntok) % 16 != 0)) {
+        hipt_set_error("vit_embed_unit: bf16, D = 384, 256 x 256 patches of 16 x 16-pixel tokens, 16-byte aligned pixel rows (uint8: strides %% 8 == 0, "
+                       "batch_stride = 3 * chan_stride), nseq * ntok %% 16 == 0 for the image outputs, and not under HIPT_GENERIC only");
+        return HIPT_E_UNSUPPORTED;
+    }
+    Carver c(workspace, workspace ? ws_bytes : 0);  // (a null workspace is refused like a short one)
+    void* slot = c.take(embed_px_slot_bytes());     // the packed Conv2d weight with the kernel's tile queue behind it
+    if ((rc = check_workspace(c, "vit_embed_unit"))) return rc;
+    hipStream_t st = S(stream);
+    if ((rc = hipt_embed32_pack_launch(w->embed_w, slot, st))) return rc;
+    return embed256_px(w, images, input_kind, lay, seq0, nseq, x_out, slot, xn_out_img, st);
+}
+
 // Format of the fused MLP's weight image: 2 = csrc/mlp16.hip (16x16x32 MFMAs), 0 = this shape has no packed form.  (Format 1 was a
 // 32x32x16 form, tools/experiments/mlp32_r4.hip, since retired -- DESIGN.md; an image packed as format 1 is refused by blocks_chain
 // and its model falls back to the generic kernels.)

@@ -37,7 +37,7 @@ extern "C" {
  * 6: hipt_bootstrap_metrics added (nothing else changed).  The heat-map entry points (hipt_heatmap_workspace_bytes, _overlay,
  * _render), hipt_vit_cls_block_unit, hipt_score_counts and the hierarchical heat-map pair (hipt_hier_ranks, hipt_hier_render) and the
  * tiling pair (hipt_point_polygon_test, hipt_tile_contours), the resize pair, hipt_patch_render, the hipt_macenko_* five, the hipt_segment_* six and the hipt_contours_* three were added later under the same
- * number: additive, nothing existing changed. */
+ * number: additive, nothing existing changed.  hipt_vit_embed_unit likewise. */
 #define HIPT_ABI_VERSION 6
 
 enum { HIPT_F32 = 0, HIPT_BF16 = 1 };
@@ -247,6 +247,23 @@ int hipt_vit_mlp_unit(const hipt_vit_weights* w, int block, float* x_img, const 
  * workspace >= hipt_vit_workspace_bytes(w, nseq), 256-byte aligned. */
 int hipt_vit_cls_block_unit(const hipt_vit_weights* w, const void* xn_img, const float* x_img, int nseq, float* xc_out, void* att_out,
                             void* workspace, size_t ws_bytes, void* stream);
+
+/* The pixel-reading patch embedding of a bf16 ViT-256 forward as that forward runs it (prepare_tokens, vision_transformer.py:235-246:
+ * patchify + Conv2d(3, 384, 16, 16) + bias + pos, the [CLS] rows = cls + pos[0]), exposed for the parity tests: the Conv2d weight is
+ * packed into the workspace, then the embedding kernel and the [CLS]-row kernel are launched exactly as the forwards launch them.
+ * images: sequences [seq0, seq0 + nseq) addressed through `lay`; input_kind 0: fp32, 1: uint8 planar [.., 3, W, H], 2: uint8
+ * interleaved [.., W, H, 3] (ToTensor + Normalize(0.5, 0.5) in registers; strides of `lay` in pixels of one channel, as for
+ * hipt_image_to_compute).  The images are not written.
+ * xn_out_img == NULL: x_out [nseq, 257, 384] fp32 row-major (what hipt_vit256_prepare_tokens returns).
+ * xn_out_img != NULL: x_out is the fp32 activation image of the [nseq * 257, 384] rows and xn_out_img the bf16 activation image of
+ * LayerNorm-1 of block 0 applied to them (what the first block of a whole forward receives); needs nseq * 257 % 16 == 0.
+ * HIPT_E_UNSUPPORTED wherever the forwards would not take this kernel: outside bf16 / D = 384 / 256 x 256 patches / 257 tokens, images
+ * not 16-byte aligned, strides not multiples of 4 (uint8: of 8, and batch_stride == 3 * chan_stride), under HIPT_GENERIC=1, and for the
+ * image outputs when nseq * 257 is not a multiple of 16.  Nothing is launched then.
+ * workspace >= 590 080 bytes (12 x 48 KiB of packed weight + 256 for the kernel's tile queue), 256-byte aligned; HIPT_E_WORKSPACE
+ * otherwise.  It need not be cleared between calls. */
+int hipt_vit_embed_unit(const hipt_vit_weights* w, const void* images, int input_kind, const hipt_image_layout* lay, int seq0, int nseq,
+                        float* x_out, void* xn_out_img, void* workspace, size_t ws_bytes, void* stream);
 
 /* [CLS] row of the last block's attention map: probs_cls[nseq, heads, ntok] fp32 =
  * get_last_selfattention(x)[:, :, 0, :] (vision_transformer.py:255-262 as consumed by the heat-maps,

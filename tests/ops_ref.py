@@ -68,13 +68,15 @@ def layernorm_kappa(x, eps):
     return np.sqrt((x * x).mean(-1) / (x.var(-1) + eps))
 
 
-def layernorm_bound(x, w, b, eps, out_bf16):
+def layernorm_bound(x, w, b, eps, out_bf16, chain=None):
     """two-pass bound: with L = D / 64 + 7 roundings in a lane's chain plus the 64-lane tree plus the division,
     t = L kappa u is the error of the mean in units of sqrt(var + eps);
-    |dy| <= |w| (t + |xhat| ((L / 2 + 9) u + t^2 / 2)) + u |y|  (+ 2^-8 |y| for a bf16 output)"""
+    |dy| <= |w| (t + |xhat| ((L / 2 + 9) u + t^2 / 2)) + u |y|  (+ 2^-8 |y| for a bf16 output)
+    chain: L of another kernel's summation (roundings between an element and the mean: its lane's serial adds, the cross-lane adds,
+    the division); None = ln_kernel's D / 64 + 7"""
     x, w, b = (np.asarray(v, np.float64) for v in (x, w, b))
     D = x.shape[-1]
-    L = D / 64 + 7
+    L = D / 64 + 7 if chain is None else float(chain)
     mean = x.mean(-1, keepdims=True)
     sig = np.sqrt(((x - mean) ** 2).mean(-1, keepdims=True) + eps)
     xh = (x - mean) / sig
