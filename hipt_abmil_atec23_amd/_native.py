@@ -145,6 +145,9 @@ SIGNATURES = {
     "hipt_clam_bags_supported": (_i, [_CW]),
     "hipt_clam_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
     "hipt_clam_sb_forward_bags": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hipt_clam_wide_bags_supported": (_i, [_CW]),
+    "hipt_clam_wide_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
+    "hipt_clam_sb_forward_bags_wide": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hipt_clam_narrow_bags_supported": (_i, [_CW]),
     "hipt_clam_narrow_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
     "hipt_clam_sb_forward_bags_narrow": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),

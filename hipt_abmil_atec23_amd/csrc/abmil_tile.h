@@ -156,7 +156,20 @@ template <typename F> bool visit_narrow(int dtype, int s1, int s2, F&& f) {
     return false;
 }
 
-// ---- the multi-bag tile passes (abmil_bags.hip, abmil_narrow.hip) ----
+// The WIDE set of the ragged multi-bag tile kernel of abmil_wide.hip (small_resnet18 / tiny [., 256, 64], small [., 512, 256], big
+// [., 512, 384]), each in both dtypes: again a table of its own.
+template <typename F> bool visit_wide(int dtype, int s1, int s2, F&& f) {
+#define HIPT_ABMIL_WD(TT, A, B) if (s1 == A && s2 == B) return f(Width<TT, A, B>{}), true;
+    if (dtype == HIPT_BF16) {
+        HIPT_ABMIL_WD(bf16_t, 256, 64) HIPT_ABMIL_WD(bf16_t, 512, 256) HIPT_ABMIL_WD(bf16_t, 512, 384)
+    } else if (dtype == HIPT_F32) {
+        HIPT_ABMIL_WD(float, 256, 64) HIPT_ABMIL_WD(float, 512, 256) HIPT_ABMIL_WD(float, 512, 384)
+    }
+#undef HIPT_ABMIL_WD
+    return false;
+}
+
+// ---- the multi-bag tile passes (abmil_bags.hip, abmil_narrow.hip, abmil_wide.hip) ----
 // A work unit: rows [m0, min(m0 + TM, end)) of the concatenated matrix; m0 < 0: no unit (the table is sized from an upper bound)
 struct BagUnit { int64_t m0, end; };
 

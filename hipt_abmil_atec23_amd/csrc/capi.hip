@@ -1180,11 +1180,12 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
     return HIPT_OK;
 }
 
-// ---- B bags in one call (abmil_bags.hip, abmil_narrow.hip): unit table | tile_start | one partial per unit and branch; no state ----
-// The call exists in three forms -- the wide single-branch heads, the narrow heads, the K = n_att branches of CLAM_MB -- which share
+// ---- B bags in one call (abmil_bags.hip, abmil_narrow.hip, abmil_wide.hip): unit table | tile_start | one partial per unit and branch; no state ----
+// The call exists in four forms -- the mid-width single-branch heads, the narrow heads, the wide heads, the K = n_att branches of CLAM_MB -- which share
 // every line of the host side but the four things a ClamBagsForm names.
 int hipt_clam_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && w->s0 > 0 && hipt_clam_fused_supported(w) ? 1 : 0; }
 int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_narrow_supported(w) ? 1 : 0; }
+int hipt_clam_wide_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_wide_supported(w) ? 1 : 0; }
 int hipt_clam_mb_bags_supported(const hipt_clam_weights* w) {
     return hipt_clam_bags_supported(w) && w->n_att >= 2 && w->n_att <= 4 && w->n_att == w->n_classes ? 1 : 0;
 }
@@ -1206,6 +1207,10 @@ static const ClamBagsForm BAGS_NARROW = {"clam_sb_forward_bags_narrow", hipt_cla
                                          hipt_clam_narrow_tiles_launch, hipt_clam_bags_combine_launch,
                                          "%s: [%d,%d,%d] is not a narrow head: (S1, S2) in {(8,4), (16,8), (32,8), (32,16)}, S0 a "
                                          "multiple of 32 (fp32) / 64 (bf16)"};
+static const ClamBagsForm BAGS_WIDE = {"clam_sb_forward_bags_wide", hipt_clam_wide_bags_supported, one_branch, hipt_clam_wide_tiles_launch,
+                                       hipt_clam_bags_combine_launch,
+                                       "%s: [%d,%d,%d] is not a wide head: (S1, S2) in {(256,64), (512,256), (512,384)}, S0 a multiple "
+                                       "of 32 (fp32) / 64 (bf16)"};
 static const ClamBagsForm BAGS_MB = {"clam_mb_forward_bags", hipt_clam_mb_bags_supported, att_branches, hipt_clam_bags_mb_tiles_launch,
                                      hipt_clam_bags_mb_combine_launch,
                                      "%s: no multi-bag form for [%d,%d,%d] with %d branches / %d classes in this dtype: call "
@@ -1266,6 +1271,7 @@ static int clam_bags_forward(const ClamBagsForm& f, const hipt_clam_weights* w, 
     }
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags, hipt_clam_bags_workspace_bytes, BAGS_SB)
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags_narrow, hipt_clam_narrow_bags_workspace_bytes, BAGS_NARROW)
+HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags_wide, hipt_clam_wide_bags_workspace_bytes, BAGS_WIDE)
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags, hipt_clam_mb_bags_workspace_bytes, BAGS_MB)
 #undef HIPT_CLAM_BAGS_ENTRY
 

@@ -234,6 +234,11 @@ int hipt_clam_bags_combine_launch(const float* partials, const int* tile_start, 
 bool hipt_clam_narrow_supported(const hipt_clam_weights* w);
 int hipt_clam_narrow_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
                                   int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
+// the tile pass for the wide heads (abmil_wide.hip; widths: abmil_tile.h visit_wide, S0 a multiple of 32 (fp32) / 64 (bf16)): the same unit
+// table in, the same partials out; a unit is walked as sub-tiles and folded into its one record
+bool hipt_clam_wide_supported(const hipt_clam_weights* w);
+int hipt_clam_wide_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
+                                int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
 // the same over w->n_att = 2..4 attention branches (CLAM_MB): A_raw [K, a_stride], K partials per unit, M [B, K, S1], logits / Y_prob [B, K]
 int hipt_clam_bags_mb_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
                                    int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);

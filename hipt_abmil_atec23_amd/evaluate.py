@@ -121,8 +121,13 @@ def _tally(preds, labels, n_classes):
     return acc, sum(d["count"] - d["correct"] for d in acc) / len(labels)
 
 
+def _wide(model, wide_one_call: bool) -> bool:
+    """``bags_wide`` of a split's call: asked for here, or already set on the model."""
+    return bool(wide_one_call) or bool(getattr(model, "bags_wide", False))
+
+
 def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
-                   max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True) -> SplitResult:
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True, wide_one_call: bool = False) -> SplitResult:
     """Evaluate ``model`` on every bag of a split.  ``bags_or_loader``: a sequence of ``[N_b, S0]`` tensors with ``labels``, or an
     iterable of ``(bag, label)`` pairs (a batch-size-1 loader) with ``labels=None``.  The bags go to the model's device and through
     ``model.forward_bags`` in runs of at most ``max_rows_per_call`` rows (a model without ``forward_bags`` is called bag by bag);
@@ -131,10 +136,13 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     A ``CLAM_SB`` model runs with ``bags_narrow = narrow_one_call`` for the duration of the call: for the narrow heads
     (``hipt_smaller``, ``hipt_smallest``, ...: ``hipt_clam_narrow_bags_supported``) the numbers then come from the one-call kernel
     ``hipt_clam_sb_forward_bags_narrow``.  They equal those of the loop over ``forward`` (``narrow_one_call=False``) within the
-    fp32 bar (1e-4); they are not bit-equal to it."""
+    fp32 bar (1e-4); they are not bit-equal to it.  ``wide_one_call=True`` likewise sets ``bags_wide`` for the duration of the call:
+    the wide heads (``tiny``, ``small``, ``big``, ``small_resnet18``: ``hipt_clam_wide_bags_supported``) then go through
+    ``hipt_clam_sb_forward_bags_wide``.  ``False`` (the default) leaves the model's own ``bags_wide`` in force -- which is how a caller of
+    ``dropin.install(evaluation=True)`` / ``(validation=True)`` opts in: ``model.bags_wide = True``."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     fb = getattr(model, "forward_bags", None)
-    with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call):
+    with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call), _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)):
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             part = [bags[i].to(dev) for i in run]
             if fb is not None:
@@ -163,19 +171,22 @@ class ValidationResult:
 
 
 def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
-                   max_rows_per_call: int = DEFAULT_MAX_ROWS, mb_one_call: bool = True, narrow_one_call: bool = True) -> ValidationResult:
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS, mb_one_call: bool = True, narrow_one_call: bool = True,
+                   wide_one_call: bool = False) -> ValidationResult:
     """The numbers of ``validate_clam`` for ``model`` on a split, with ``model.forward_bags(..., label=, instance_eval=True)`` called on
     runs of at most ``max_rows_per_call`` rows (``chunk_bags``) instead of ``model(bag, label=, instance_eval=True)`` once per slide.
     Arguments as :func:`evaluate_split`.  A ``CLAM_MB`` model runs with ``bags_one_call = mb_one_call`` for the duration of the call,
     a ``CLAM_SB`` with ``bags_narrow = narrow_one_call``: for the narrow heads (``hipt_smaller``, ``hipt_smallest``, ...) the numbers
     then come from the one-call kernel; they equal the loop's (``narrow_one_call=False``) within the fp32 bar (1e-4), not bit for bit.
+    ``wide_one_call`` as in :func:`evaluate_split` (the wide heads; the default keeps the model's own ``bags_wide``).
     The AUC stays with the caller (``labels`` and ``prob`` are its inputs).  The model is put in eval mode, as ``validate_clam`` does."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     n = len(bags)
     inst_loss = torch.empty((n,), dtype=torch.float32)
     inst = [{"count": 0, "correct": 0} for _ in range(n_classes)]
     model.eval()
-    with torch.no_grad(), _attr_for_call(model, "bags_one_call", mb_one_call), _attr_for_call(model, "bags_narrow", narrow_one_call):
+    with torch.no_grad(), _attr_for_call(model, "bags_one_call", mb_one_call), _attr_for_call(model, "bags_narrow", narrow_one_call), \
+            _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)):
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             out = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
             _copy_back(run, out, logits, probs, preds)

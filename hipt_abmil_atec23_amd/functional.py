@@ -153,13 +153,14 @@ _sb_shapes = lambda w, B, rows: ((rows,), (B, w.s1), (B, w.n_classes))
 _BAGS_FORMS = {
     "sb": ("hipt_clam_sb_forward_bags", "hipt_clam_bags_workspace_bytes", _sb_shapes),
     "narrow": ("hipt_clam_sb_forward_bags_narrow", "hipt_clam_narrow_bags_workspace_bytes", _sb_shapes),
+    "wide": ("hipt_clam_sb_forward_bags_wide", "hipt_clam_wide_bags_workspace_bytes", _sb_shapes),
     "mb": ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes",
            lambda w, B, rows: ((w.n_att, rows), (B, w.n_att, w.s1), (B, w.n_att))),
 }
 
 
 def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None, form: str = "sb"):
-    """The multi-bag CLAM forward in the form ``"sb"``, ``"narrow"`` or ``"mb"`` (include/hipt_abmil.h) on ``cat [rows, S0]``, already
+    """The multi-bag CLAM forward in the form ``"sb"``, ``"narrow"``, ``"wide"`` or ``"mb"`` (include/hipt_abmil.h) on ``cat [rows, S0]``, already
     in the dtype of the weight image ``w`` (an ``_native.ClamWeights``).  Returns ``(A_raw, M, logits, Y_prob, Y_hat)`` -- the last
     four ``None`` with ``attention_only``.  ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions,
     sentinels)."""
@@ -194,6 +195,12 @@ def clam_sb_forward_bags_narrow(w, cat: torch.Tensor, offsets: BagOffsets, atten
     """``hipt_clam_sb_forward_bags_narrow``: :func:`clam_sb_forward_bags` for the narrow heads (``hipt_clam_narrow_bags_supported``:
     ``(S1, S2)`` in {(8, 4), (16, 8), (32, 8), (32, 16)}, fp32 and bf16).  Arguments and results as there."""
     return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "narrow")
+
+
+def clam_sb_forward_bags_wide(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_sb_forward_bags_wide``: :func:`clam_sb_forward_bags` for the wide heads (``hipt_clam_wide_bags_supported``:
+    ``(S1, S2)`` in {(256, 64), (512, 256), (512, 384)}, fp32 and bf16).  Arguments and results as there."""
+    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "wide")
 
 
 def clam_mb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):

@@ -279,6 +279,7 @@ class CLAM_SB(WeightImageCache, nn.Module):
     ``[S0, S1, S2]`` list."""
 
     _multi = False
+    bags_wide = False    # forward_bags takes hipt_clam_sb_forward_bags_wide (all bags in one call) for the wide heads (tiny, small, big, small_resnet18); False: the loop over forward
     bags_narrow = False  # forward_bags takes hipt_clam_sb_forward_bags_narrow (all bags in one call) for the narrow heads the multi-bag kernel does not have; False: the loop over forward
 
     def __init__(self, gate=True, size_arg="small", dropout=0.0, k_sample=8, n_classes=2,
@@ -547,8 +548,10 @@ class CLAM_SB(WeightImageCache, nn.Module):
         w = self._pack(device)
         if lib.hipt_clam_bags_supported(C_.byref(w)):
             return w, "sb"   # (a width both kernels have keeps the wide one)
-        narrow = self.bags_narrow and lib.hipt_clam_narrow_bags_supported(C_.byref(w))   # hipt_smaller, hipt_smallest, ...: where asked for
-        return (w, "narrow") if narrow else None
+        if self.bags_narrow and lib.hipt_clam_narrow_bags_supported(C_.byref(w)):   # hipt_smaller, hipt_smallest, ...: where asked for
+            return w, "narrow"
+        wide = self.bags_wide and lib.hipt_clam_wide_bags_supported(C_.byref(w))         # tiny, small, big, small_resnet18: where asked for
+        return (w, "wide") if wide else None
 
     def forward_bags(self, bags, attention_only=False, return_features=False, label=None, instance_eval=False):
         """``forward`` over B bags at once, inference only (no autograd; dropout inactive as in ``eval()``).
@@ -563,7 +566,9 @@ class CLAM_SB(WeightImageCache, nn.Module):
         ``bags_route`` tells which.  The narrow heads (``hipt_smaller`` [192, 16, 8], ``hipt_smallest`` [192, 8, 4], (32, 8), bf16
         (32, 16): ``hipt_clam_narrow_bags_supported``) have a one-call kernel of their own, ``hipt_clam_sb_forward_bags_narrow``, taken
         by a ``CLAM_SB`` with ``bags_narrow`` set (default False: the loop, with the bits of ``forward``); its numbers equal the
-        loop's within the fp32 bar (1e-4), not bit for bit.  A width both kernels have keeps the first.
+        loop's within the fp32 bar (1e-4), not bit for bit.  A width both kernels have keeps the first.  The wide heads (``tiny``,
+        ``small``, ``big``, ``small_resnet18``: ``hipt_clam_wide_bags_supported``) likewise have ``hipt_clam_sb_forward_bags_wide``, taken
+        by a ``CLAM_SB`` with ``bags_wide`` set (default False: the loop, with the bits of ``forward``).
 
         ``instance_eval=True`` with ``label`` (B class ids: a list, a numpy array or a tensor) adds what ``forward(h, label=,
         instance_eval=True)`` returns per bag (validate_clam, utils/core_utils.py:506-560): ``instance_loss`` (a ``[B]`` tensor),

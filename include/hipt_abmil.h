@@ -387,9 +387,9 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
                          float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                          void* workspace, size_t ws_bytes, void* stream);
 
-/* CLAM forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).  The call exists in three
- * forms -- the wide gated heads, the narrow ones, the K branches of CLAM_MB -- each with its own <form>_supported, <form>_workspace_bytes and
- * forward entry point of one signature.  What holds for all three is stated here, once; each form below lists only what differs.
+/* CLAM forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).  The call exists in four
+ * forms -- the mid-width gated heads, the narrow ones, the wide ones, the K branches of CLAM_MB -- each with its own <form>_supported, <form>_workspace_bytes and
+ * forward entry point of one signature.  What holds for all four is stated here, once; each form below lists only what differs.
  * bags: the bags' rows concatenated, [total_rows, S0] in w->dtype, 16-byte aligned; offsets_dev: int64[B + 1] in DEVICE memory, offsets[0] = 0,
  * increasing, offsets[B] = total_rows: bag b is rows [offsets[b], offsets[b+1]).  Every bag has at least one row.  The CONTENTS of the offsets
  * are the caller's responsibility (check them on the host before the upload); a bag whose offsets break the rules is left unwritten.
@@ -420,6 +420,17 @@ size_t hipt_clam_narrow_bags_workspace_bytes(const hipt_clam_weights* w, int B, 
 int hipt_clam_sb_forward_bags_narrow(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
                                      int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                                      void* workspace, size_t ws_bytes, void* stream);
+
+/* The heads WIDER than the first form's (the reference's tiny, small, big and small_resnet18): (S1, S2) in {(256, 64), (512, 256), (512, 384)}
+ * in fp32 and in bf16, S0 a multiple of 32 (fp32) / 64 (bf16).  Outputs as the first form; the same unit table and per-bag combine, the tile
+ * pass is a kernel of its own that walks a 128-row unit as sub-tiles of 64 (bf16) / 32 (fp32) rows in a fixed order.  Rounding in bf16: the
+ * bag, W1, Wa and Wb are bf16; h1 is rounded to bf16 as the gate GEMM's operand only; ab, the gate and the pooling (on unrounded h1) are
+ * fp32 (the model of hipt_clam_sb_forward for these widths). */
+int hipt_clam_wide_bags_supported(const hipt_clam_weights* w);
+size_t hipt_clam_wide_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
+int hipt_clam_sb_forward_bags_wide(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                                   int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                   void* workspace, size_t ws_bytes, void* stream);
 
 /* CLAM_MB.forward (model_clam.py:226-264): the K = w->n_att attention branches of a hipt_clam_weights stacked as hipt_clam_mb_forward takes
  * it (wc [K, S2], bc [K], wcls [K, S1], bcls [K], n_classes = K; stream_pk and logit_bound are not read).  Supported: hipt_clam_bags_supported(w)
