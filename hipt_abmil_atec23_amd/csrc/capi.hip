@@ -734,25 +734,28 @@ int hipt_vit_attention_unit(const hipt_vit_weights* w, int block, const void* xn
         hipt_set_error("vit_attention_unit: bf16, D = 384, 6 heads, 257 tokens and nseq * 257 %% 16 == 0 only");
         return HIPT_E_UNSUPPORTED;
     }
-    Carver c(workspace, ws_bytes);
-    BlockScratch s = carve_blocks(c, w, nseq);
+    Carver c(workspace, workspace ? ws_bytes : 0);  // (a null workspace is refused like a short one)
+    BlockScratch s = carve_vit4k(c, w, nseq, false).s;  // hipt_vit_workspace_bytes' layout: the size the header asks for is the size checked
     if ((rc = check_workspace(c, "vit_attention_unit"))) return rc;
     hipStream_t st = S(stream);
     const hipt_block_weights& b = w->blocks[block];
     SeqGemmParams q = qkv_params(w, block, M, nullptr, s);
     qkv_from_xn(q, xn_img);
     HIPT_CHECK_ARG(b.qkv_pk != nullptr, "vit_attention_unit: blocks[%d].qkv_pk is NULL", block);
+    // (the launches are booked in the forward's categories: a test reads the route it got from the counts)
     if (fused) {
         HIPT_CHECK_ARG(b.qkv_att_pk != nullptr, "vit_attention_unit: blocks[%d].qkv_att_pk is NULL", block);
-        if ((rc = hipt_gather_cls_bf16_launch(xn_img, s.cls_xn, nseq, w->ntok, D, st, 1))) return rc;
+        PROF(PC_CLSROWS, hipt_gather_cls_bf16_launch(xn_img, s.cls_xn, nseq, w->ntok, D, st, 1));
         q.M = nseq; q.A = s.cls_xn; q.out = s.cls_qkv;
-        if ((rc = hipt_seqgemm_launch(q, false, 0, st))) return rc;
-        return hipt_qkv_attn_launch(xn_img, b.qkv_att_pk, b.qkv_b, s.cls_qkv, out_img, nseq, attn_scale(w), st);
+        PROF(PC_CLSROWS, hipt_seqgemm_launch(q, false, 0, st));
+        PROF(PC_QKVATT, hipt_qkv_attn_launch(xn_img, b.qkv_att_pk, b.qkv_b, s.cls_qkv, out_img, nseq, attn_scale(w), st));
+        return HIPT_OK;
     }
     const bool hm = (int64_t)M * 3 * D * 2 < ((int64_t)1 << 32) - 65536;
     q.img = 1 | (hm ? 4 : 0);
-    if ((rc = hipt_seqgemm_launch(q, false, 0, st))) return rc;
-    return hipt_attention_launch(s.qkv, out_img, nullptr, nseq, w->ntok, w->heads, D / w->heads, attn_scale(w), w->dtype, st, 1, hm ? 1 : 0);
+    PROF(PC_QKV, hipt_seqgemm_launch(q, false, 0, st));
+    PROF(PC_ATTN, hipt_attention_launch(s.qkv, out_img, nullptr, nseq, w->ntok, w->heads, D / w->heads, attn_scale(w), w->dtype, st, 1, hm ? 1 : 0));
+    return HIPT_OK;
 }
 
 int hipt_vit_mlp_unit(const hipt_vit_weights* w, int block, float* x_img, const void* att_img, int nseq, void* xn_out_img, void* workspace,
