@@ -73,6 +73,9 @@ _LAZY = {
     "contour_area": ("segment", "contour_area"), "filter_contours": ("segment", "filter_contours"),
     # cv2.findContours(mask, RETR_CCOMP, CHAIN_APPROX_NONE) on the device: the step between the mask and the contour filter
     "trace_contours": ("segment", "trace_contours"), "find_contours": ("segment", "find_contours"),
+    # WholeSlideImage.get_seg_mask: the contours filled on the device (cv2.drawContours, thickness=-1), the heat-maps' mask
+    "seg_mask": ("segment", "seg_mask"), "get_seg_mask_like": ("segment", "get_seg_mask_like"),
+    "scale_contours": ("segment", "scale_contours"), "scale_holes": ("segment", "scale_holes"),
 }
 
 

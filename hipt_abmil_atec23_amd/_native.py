@@ -92,6 +92,7 @@ TILING_COORD_BOUND, TILING_EDGE_CHUNK, TILING_TILE, TILING_CONTOUR_INTS = 1 << 3
 RESIZE_ROUTE_AUTO, RESIZE_ROUTE_GENERAL, RESIZE_ROUTE_FUSED, RESIZE_MAX_KSIZE = 0, 1, 2, 512      # HIPT_RESIZE_*
 SEGMENT_MAX_MEDIAN, SEGMENT_MAX_CLOSE = 15, 128                                                   # HIPT_SEGMENT_MAX_*
 CONTOURS_MAX_PLANE, CONTOURS_MAX_BORDER_PIXELS, CONTOURS_MAX_BORDERS = 1 << 27, 1 << 24, 1 << 22                # HIPT_CONTOURS_MAX_*
+FILL_MAX_DIM, FILL_MAX_POINTS, FILL_COORD_BOUND, FILL_MAX_COLS, FILL_COLLECTION_INTS = 65535, 1 << 27, 1 << 20, 3072, 5   # HIPT_FILL_*
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
@@ -215,6 +216,7 @@ SIGNATURES = {
     "hipt_contours_workspace_bytes": (_sz, [_i, _i]),
     "hipt_contours_trace": (_i, [_p, _i, _i, _p, _p, _sz, _p]),
     "hipt_contours_emit": (_i, [_i, _i, _p, _p, _i, _i, _p, _p, _sz, _p]),
+    "hipt_fill_contours": (_i, [_p, _i64, _p, _i, _p, _i, C.c_double, C.c_double, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -418,13 +418,15 @@ def compute_from_batches(model, feature_extractor, batches, clam_pred=None, ref_
 def vis_heatmap(wsi_object, scores, coords, vis_level=-1, top_left=None, bot_right=None, patch_size=(256, 256), blank_canvas=False,
                 canvas_color=(220, 20, 50), alpha=0.4, blur=False, overlap=0.0, segment=True, use_holes=True,
                 convert_to_percentiles=False, binarize=False, thresh=0.5, max_size=None, custom_downsample=1, cmap="coolwarm",
-                device=None):
+                device=None, device_mask=False):
     """``WholeSlideImage.visHeatmap`` with its keyword arguments and defaults; returns a ``PIL.Image``.
 
     ``wsi_object`` is used by duck typing: ``level_downsamples``, ``level_dim``, ``wsi.get_best_level_for_downsample``,
     ``wsi.read_region`` and (with ``segment``) ``get_seg_mask``.  The canvas is fetched with ONE ``read_region`` of the whole
     region (the reference reads it once for painting and again block by block for the blend, the same pixels).  ``canvas_color``
-    and ``overlap`` are accepted and unused, as in the reference with ``blur=False``.  The caller's ``scores`` are not modified."""
+    and ``overlap`` are accepted and unused, as in the reference with ``blur=False``.  The caller's ``scores`` are not modified.
+    ``device_mask=True`` (with ``segment``) builds the tissue mask on the device from ``contours_tissue`` / ``holes_tissue``
+    (``segment.get_seg_mask_like``; no cv2, no ``get_seg_mask`` method needed) and hands the tensor to ``render_heatmap``."""
     from PIL import Image
     if blur:
         raise NotImplementedError("vis_heatmap: blur=True is not supported (DESIGN.md 14)")
@@ -446,7 +448,11 @@ def vis_heatmap(wsi_object, scores, coords, vis_level=-1, top_left=None, bot_rig
     else:
         region_size = tuple(int(v) for v in wsi_object.level_dim[vis_level])
         top_left = (0, 0)
-    mask = wsi_object.get_seg_mask(region_size, scale, use_holes=use_holes, offset=tuple(top_left)) if segment else None
+    if segment and device_mask:
+        from .segment import get_seg_mask_like
+        mask = get_seg_mask_like(wsi_object, region_size, scale, use_holes=use_holes, offset=tuple(top_left), device=device)
+    else:
+        mask = wsi_object.get_seg_mask(region_size, scale, use_holes=use_holes, offset=tuple(top_left)) if segment else None
     canvas = None if blank_canvas else np.array(wsi_object.wsi.read_region(top_left, vis_level, region_size).convert("RGB"))
     img = render_heatmap(scores, coords, patch_size, scale, region_size, canvas=canvas, mask=mask, alpha=alpha, binarize=binarize,
                          thresh=threshold, convert_to_percentiles=convert_to_percentiles, cmap=cmap, device=device)

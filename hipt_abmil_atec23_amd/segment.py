@@ -223,6 +223,187 @@ def contour_area(cont) -> float:
     return float(abs(0.5 * np.sum(q[:, 0] * p[:, 1] - p[:, 0] * q[:, 1])))
 
 
+def scale_contours(contours, scale):
+    """``WholeSlideImage.scaleContourDim``: ``[np.array(cont * scale, dtype='int32') for cont in contours]`` -- a float64 product,
+    then truncation toward zero."""
+    return [np.array(cont * scale, dtype="int32") for cont in contours]
+
+
+def scale_holes(holes, scale):
+    """``WholeSlideImage.scaleHolesDim``: the same for the list of every contour's list of holes."""
+    return [[np.array(hole * scale, dtype="int32") for hole in hs] for hs in holes]
+
+
+def _draw_order(areas) -> np.ndarray:
+    """The ONE place that decides ``get_seg_mask``'s draw order: by area, descending, stable (equal areas keep their order; the
+    reference's ``sorted`` over ``zip(contours, holes)`` compares arrays on a tie and raises, so a tie has no behaviour to match)."""
+    return np.argsort(-np.asarray(areas, dtype=np.float64), kind="stable")
+
+
+def _int_points(what: str, cont) -> np.ndarray:
+    a = np.asarray(cont)
+    if a.dtype.kind not in "iu" or a.size % 2 or (a.size and (a.ndim < 2 or a.shape[-1] != 2)):
+        raise ValueError(f"{what}: a contour is an integer array [n, 1, 2] or [n, 2] of (x, y), got {a.dtype} {list(a.shape)}")
+    a = a.reshape(-1, 2)
+    if a.size and (a.min() < -(1 << 31) or a.max() >= 1 << 31):
+        raise ValueError(f"{what}: a contour's coordinates must fit int32")
+    return a.astype(np.int32)
+
+
+def _flatten_lists(what: str, contours, holes):
+    """cv2-style lists as one polygon list: every contour followed at once by its holes.  ``(points int32 [P, 2], offsets int64,
+    first [n]: the polygon index of contour i, n_holes [n])``."""
+    contours = list(contours)
+    holes = [[] for _ in contours] if holes is None else [list(hs) for hs in holes]
+    if len(holes) != len(contours):
+        raise ValueError(f"{what}: {len(contours)} contours but {len(holes)} lists of holes (one list per contour, possibly empty)")
+    polys, first, n_holes = [], [], []
+    for cont, hs in zip(contours, holes):
+        first.append(len(polys))
+        n_holes.append(len(hs))
+        polys.append(_int_points(what, cont))
+        polys += [_int_points(what, hole) for hole in hs]
+    offsets = np.zeros(len(polys) + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in polys], out=offsets[1:])
+    points = np.concatenate(polys) if polys else np.zeros((0, 2), np.int32)
+    return np.ascontiguousarray(points, dtype=np.int32), offsets, np.array(first, np.int64), np.array(n_holes, np.int64)
+
+
+def _split_traced(what: str, n_polys: int, hierarchy):
+    """``(first, n_holes)`` of a traced polygon list: without a hierarchy every polygon is a contour without holes; with one
+    (``[C, 4]``, column 3 the parent; read back if it is a device tensor) the polygons without a parent are the contours and each
+    one's holes are the polygons that follow it at once and name it as their parent -- the order ``trace_contours`` returns."""
+    if hierarchy is None:
+        return np.arange(n_polys, dtype=np.int64), np.zeros(n_polys, dtype=np.int64)
+    hier = hierarchy.cpu().numpy() if F.is_tensor(hierarchy) else np.asarray(hierarchy)
+    if hier.shape != (n_polys, 4):
+        raise ValueError(f"{what}: the hierarchy of {n_polys} polygons is [{n_polys}, 4], got {list(hier.shape)}")
+    parent = hier[:, 3].astype(np.int64)
+    first = np.flatnonzero(parent == -1)
+    owner = np.maximum.accumulate(np.where(parent == -1, np.arange(n_polys), -1))   # the last contour at or before each polygon
+    if n_polys and (parent[0] != -1 or not np.array_equal(np.where(parent == -1, -1, owner), parent)):
+        raise ValueError(f"{what}: every hole must follow its contour at once (the order trace_contours returns)")
+    return first, np.diff(np.append(first, n_polys)) - 1
+
+
+def seg_mask(contours, holes, region_size, scale, use_holes=False, offset=(0, 0), out=None, device=None, order=None, _max_cols=0):
+    """``WholeSlideImage.get_seg_mask`` (wsi_core/WholeSlideImage.py:741-757) on the device: the bool mask ``[h, w]`` (``region_size =
+    (w, h)``) of the contours scaled by ``scale`` (``(cont * scale).astype(int32)``) and moved by ``(offset * scale * -1)
+    .astype(int32)``, drawn in descending order of their scaled area as ``cv2.drawContours(..., thickness=-1)`` fills them -- each
+    contour with 1 and, with ``use_holes``, all its holes together with 0; later contours overwrite earlier ones.  One native call
+    (csrc/fill.hip); the same input gives the same bytes in every run.
+
+    ``contours`` / ``holes``: cv2-style lists -- integer arrays ``[n, 1, 2]`` or ``[n, 2]``, and one list of such arrays per contour
+    (``None``: no holes), what ``filter_contours`` and ``segment_tissue`` produce -- or, with ``holes=None``, a traced polygon list
+    ``(points int32 [P, 2], offsets int64 [C + 1])`` or ``(points, offsets, hierarchy)`` as ``trace_contours`` returns it, numpy
+    arrays or device tensors: with a hierarchy the polygons without a parent are the contours and their children the holes (the
+    small hierarchy is read back; hand it over as a numpy array to avoid that).  Device tensors are not copied to the host, and a
+    device tensor comes back either way (``out`` where given: a contiguous bool or uint8 ``[h, w]`` tensor, fully written).
+
+    The draw order needs every contour's scaled area: with ``order=None`` it is computed on the host from the same scaled integers
+    (a stable descending sort: equal areas keep their order, where the reference's ``sorted`` raises), which for device tensors
+    costs ONE read-back of the points and so synchronises -- the call cannot then be captured into a graph.  ``order``: a
+    precomputed draw order, a permutation of the contour indices; with it and device tensors the points stay where they are
+    (one scalar, the largest coordinate, is still read to check the envelope, and the small collection table is uploaded: the
+    native call itself is one launch that can be captured, this front-end is not) and every workgroup walks every collection,
+    as the rows a contour lies on are then unknown.
+
+    Agreement with cv2's own bytes is argued, not measured (DESIGN.md 32 lists what carries the risk); for contours whose points
+    are at most a pixel apart after scaling the mask does not depend on any of it.  No contours at all give an all-zero mask (the
+    reference raises).  ValueError -- before any native call -- for a malformed contour, a canvas side outside 1 ..
+    65 535, more than 2^27 points, scaled and moved coordinates beyond +-2^20, a CPU tensor, an ``order`` that is no permutation."""
+    import torch
+    what = "seg_mask"
+    w, h = (F.check_int(what, f"region_size[{k}]", v, 1, N.FILL_MAX_DIM) for k, v in enumerate(region_size))
+    _max_cols = F.check_int(what, "_max_cols", _max_cols, 0, N.FILL_MAX_COLS)
+    scale = np.broadcast_to(np.asarray(scale, dtype=np.float64), (2,))
+    if not np.isfinite(scale).all():
+        raise ValueError(f"{what}: scale must be finite, got {scale.tolist()}")
+    if np.shape(offset) != (2,):
+        raise ValueError(f"{what}: offset is (x, y), got {offset!r}")
+    off = (np.array(offset) * np.array(scale) * -1).astype(np.int32)     # the reference's expression, in its order
+    if isinstance(contours, tuple) and len(contours) in (2, 3) and (F.is_tensor(contours[0]) or np.asarray(contours[0]).ndim == 2
+                                                                    and np.asarray(contours[1]).ndim == 1):
+        if holes is not None:
+            raise ValueError(f"{what}: with a traced polygon list the holes come from its hierarchy; holes must be None")
+        points, offsets = F.as_array(contours[0]), F.as_array(contours[1])
+        kinds = (str(points.dtype).replace("torch.", ""), str(offsets.dtype).replace("torch.", ""))
+        if kinds != ("int32", "int64") or len(points.shape) != 2 or points.shape[1] != 2 or len(offsets.shape) != 1 or offsets.shape[0] < 1:
+            raise ValueError(f"{what}: a traced polygon list is (points int32 [P, 2], offsets int64 [C + 1]), got {kinds[0]} "
+                             f"{list(points.shape)}, {kinds[1]} {list(offsets.shape)}")
+        first, n_holes = _split_traced(what, int(offsets.shape[0]) - 1, contours[2] if len(contours) == 3 else None)
+    else:
+        points, offsets, first, n_holes = _flatten_lists(what, contours, holes)
+    n, n_polys, n_points = len(first), int(offsets.shape[0]) - 1, int(points.shape[0])
+    if n_points > N.FILL_MAX_POINTS:
+        raise ValueError(f"{what}: {n_points} points; at most {N.FILL_MAX_POINTS}")
+    if order is not None:
+        order = np.asarray(order, dtype=np.int64).reshape(-1)
+        if not np.array_equal(np.sort(order), np.arange(n)):
+            raise ValueError(f"{what}: order must be a permutation of the {n} contour indices")
+    on_device = F.is_tensor(points)
+    host = None   # (points, offsets) on the host, where they are there or have to be fetched
+    if not on_device:
+        host = (points, offsets)
+    elif order is None:
+        host = (points.cpu().numpy(), offsets.cpu().numpy())             # the read-back
+    y_lo = np.full(n_polys, -(1 << 31), dtype=np.int64)
+    y_hi = np.full(n_polys, (1 << 31) - 1, dtype=np.int64)
+    if host is not None:
+        hp, ho = host
+        if len(ho) != n_polys + 1 or ho[0] != 0 or ho[-1] != n_points or (np.diff(ho) < 0).any():
+            raise ValueError(f"{what}: offsets must rise from 0 to the number of points, {n_points}")
+        bound = int(np.abs(hp.astype(np.int64)).max()) if n_points else 0
+        scaled = np.array(hp * scale, dtype="int32") + off               # what the kernel computes where it loads a vertex
+        lens = np.diff(ho)
+        full = lens > 0
+        y_lo[:], y_hi[:] = 0, -1                                         # an empty polygon lies on no row
+        if full.any():
+            y_lo[full] = np.minimum.reduceat(scaled[:, 1], ho[:-1][full])
+            y_hi[full] = np.maximum.reduceat(scaled[:, 1], ho[:-1][full])
+        if order is None:
+            areas = np.array([contour_area(scaled[ho[p]:ho[p + 1]]) for p in first], dtype=np.float64)
+            order = _draw_order(areas)
+    else:
+        bound = int(points.abs().max()) if n_points else 0               # one scalar: the envelope is checked, never assumed
+    reach = bound * float(np.abs(scale).max()) + int(np.abs(off.astype(np.int64)).max())
+    if not reach <= N.FILL_COORD_BOUND:
+        raise ValueError(f"{what}: coordinates up to {bound} scaled by {scale.tolist()} and moved by {off.tolist()} leave the envelope of "
+                         f"+-{N.FILL_COORD_BOUND} canvas pixels")
+    dev = F.resolve_device(what, device, (points, offsets, out), exc=ValueError)
+    rows = []
+    for i in order:
+        p = int(first[i])
+        rows.append((p, p + 1, 1, y_lo[p], y_hi[p]))
+        if use_holes and n_holes[i] > 0:
+            q = p + 1 + int(n_holes[i])
+            rows.append((p + 1, q, 0, y_lo[p + 1:q].min(), y_hi[p + 1:q].max()))
+    table = np.clip(np.array(rows, dtype=np.int64).reshape(-1, N.FILL_COLLECTION_INTS), -(1 << 31), (1 << 31) - 1).astype(np.int32)
+    if out is not None and F.is_tensor(out) and out.dtype == torch.uint8:
+        out = F.check_out(what, out, (h, w), torch.uint8, dev)
+    else:
+        out = F.check_out(what, out, (h, w), torch.bool, dev)
+    with torch.cuda.device(dev):
+        pts_d, off_d = F.to_device(points, dev), F.to_device(offsets, dev)
+        table_d = torch.from_numpy(table).to(dev) if len(table) else None
+        _fill(pts_d, n_points, off_d, n_polys, table_d, len(table), scale, off, bound, h, w, _max_cols, out, dev)
+    return out
+
+
+def _fill(points, n_points, offsets, n_polys, table, n_collections, scale, off, bound, h, w, max_cols, out, dev):
+    """the native call of ``seg_mask``: everything resident, one launch on the current stream of ``dev``"""
+    N.call("hipt_fill_contours", N.ptr(points) if n_points else None, n_points, N.ptr(offsets), n_polys, N.ptr(table), n_collections,
+           float(scale[0]), float(scale[1]), int(off[0]), int(off[1]), bound, h, w, max_cols, N.ptr(out), N.stream_ptr(dev))
+
+
+def get_seg_mask_like(wsi_object, region_size, scale, use_holes=False, offset=(0, 0), out=None, device=None, order=None):
+    """``WholeSlideImage.get_seg_mask`` for an object with ``contours_tissue`` / ``holes_tissue`` (what ``segment_tissue`` sets): the
+    bool mask as a device tensor (``seg_mask``).  Bind it as the method with ``WholeSlideImage.get_seg_mask = lambda self, *a, **k:
+    segment.get_seg_mask_like(self, *a, **k).cpu().numpy()``, or hand the tensor to ``render_heatmap(mask=...)`` as it is."""
+    return seg_mask(wsi_object.contours_tissue, wsi_object.holes_tissue, region_size, scale, use_holes=use_holes, offset=offset, out=out,
+                    device=device, order=order)
+
+
 def filter_contours(contours, hierarchy, filter_params):
     """``segmentTissue``'s nested ``_filter_contours``: ``hierarchy`` is cv2's after the reference's ``[:, 2:]`` slice, so column 1
     is the parent.  A foreground contour (parent -1) stays if its area less its holes' areas is not 0 and strictly above

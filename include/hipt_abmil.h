@@ -1082,6 +1082,43 @@ int hipt_contours_trace(const uint8_t* mask, int h, int w, int32_t* table, void*
 int hipt_contours_emit(int h, int w, const int32_t* table, const int32_t* offsets, int n_borders, int n_points, int32_t* points,
                        const void* ws, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * Contour fill: the tissue mask of WholeSlideImage.get_seg_mask (wsi_core/WholeSlideImage.py:741-757), a sequence of
+ * cv2.drawContours(..., thickness=-1) calls.  Added under ABI 6: additive.
+ *
+ * points int32 [n_points, 2] = (x, y), 8-byte aligned; poly_off int64 [n_polys + 1]: polygon p is points[poly_off[p] : poly_off[p + 1]],
+ * closed (the edge from its last point to its first is its first edge).  collections int32 [n_collections,
+ * HIPT_FILL_COLLECTION_INTS], in DRAW ORDER, each what one drawContours call fills: {first polygon, one past the last polygon, value
+ * (0 / 1), y_min, y_max}; y_min .. y_max bound the rows the collection's scaled and moved points lie on -- a workgroup skips a
+ * collection whose range misses its rows, so a range that is too narrow gives a wrong mask (never an access out of bounds) and
+ * INT32_MIN .. INT32_MAX is always right.  All three live on the device.
+ * A coordinate becomes (int)((double)p * scale) + off, converted toward zero: the reference's (cont * scale).astype(int32) and offset.
+ * Per collection, for every polygon edge: (a) the 8-connected line between its end points (integer Bresenham, D = max(|dx|, |dy|),
+ * d = min, x the major axis on a tie, err = D - 2 d, each step: err < 0 ? minor step, err += 2 D; err -= 2 d; walked from the end point
+ * with the smaller x); (b) unless horizontal, an edge-table entry on the rows y_top <= y < y_bottom with x_fix = (x_top << 16) +
+ * (y - y_top) * (((x_bottom - x_top) << 16) / (y_bottom - y_top)), the division truncating toward zero; per row the entries are
+ * paired in sorted order and the columns (x_fix + 32768) >> 16 of a pair, both included, are filled.  The union of (a) and (b),
+ * clipped to the canvas, takes the collection's value; later collections overwrite earlier ones.
+ * mask: uint8 [h, w], contiguous, FULLY written with 0 / 1 (also with no collection at all).
+ * coord_bound: the caller's bound on |x|, |y| of the points.  Envelope: h, w <= HIPT_FILL_MAX_DIM; n_points <= HIPT_FILL_MAX_POINTS;
+ * coord_bound * max(|scale|) + max(|off|) <= HIPT_FILL_COORD_BOUND -- HIPT_E_UNSUPPORTED otherwise, nothing is clipped silently.  (The
+ * kernel clamps every scaled coordinate to the bound, so a caller that declares less than it hands over gets a wrong mask, not a
+ * fault.)  The crossing counters are 32 bits wide: no number of crossings on one pixel can wrap them.
+ * max_cols: columns per pass, 0 = HIPT_FILL_MAX_COLS, else a multiple of 64 up to it; a wider canvas is filled in column chunks, each
+ * counting the crossings left of it.  The mask does not depend on max_cols.
+ * HIPT_E_BADARG before the launch for a missing or misaligned pointer, h or w < 1, negative counts, a NaN scale, a bad max_cols.
+ * One launch on `stream`; no workspace, no allocation, no host synchronisation, no atomics on global memory (integer adds and ORs in
+ * LDS only, which commute): the same input gives the same bytes in every run, and the launch can be captured into a graph.
+ * ---------------------------------------------------------------------------------- */
+#define HIPT_FILL_MAX_DIM 65535
+#define HIPT_FILL_MAX_POINTS 134217728
+#define HIPT_FILL_COORD_BOUND 1048576
+#define HIPT_FILL_MAX_COLS 3072
+#define HIPT_FILL_COLLECTION_INTS 5
+int hipt_fill_contours(const int32_t* points, int64_t n_points, const int64_t* poly_off, int n_polys, const int32_t* collections,
+                       int n_collections, double scale_x, double scale_y, int off_x, int off_y, int coord_bound, int h, int w, int max_cols,
+                       uint8_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
