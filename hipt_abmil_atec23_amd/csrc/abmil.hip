@@ -171,9 +171,7 @@ __global__ __launch_bounds__(256, 2) void abmil_fused_kernel(const T* __restrict
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                float v = gate[i];
-                v += __shfl_xor(v, 16, 64);
-                v += __shfl_xor(v, 32, 64);
+                const float v = quad_sum(gate[i]);
                 if (g == 0) Ps[wn * TM + wm * 64 + i * 16 + li] = v;
             }
         }
@@ -256,8 +254,7 @@ __global__ __launch_bounds__(256, 2) void abmil_fused_kernel(const T* __restrict
         }
         // lsum: lane (g, li) summed the rows of its K slots; the 4 groups partition the tile's rows and
         // all 16 li lanes of a group hold the same value -> total = sum over g = 2 shuffles
-        lsum += __shfl_xor(lsum, 16, 64);
-        lsum += __shfl_xor(lsum, 32, 64);
+        lsum = quad_sum(lsum);
         l_run = l_run * resc + lsum;
 #pragma unroll
         for (int cf = 0; cf < 2; ++cf) accM[cf] = accM[cf] * resc + o[cf];

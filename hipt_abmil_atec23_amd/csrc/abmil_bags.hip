@@ -45,7 +45,7 @@ __global__ __launch_bounds__(1024) void bags_units_kernel(const int64_t* __restr
         const int t = tiles_of(b);
         cnt = cnt + t < max_units ? cnt + t : max_units;  // saturate: no overflow whatever the offsets hold
     }
-    int v = cnt;
+    int v = cnt;  // wave_incl_scan's ladder, but SATURATING at max_units (no overflow whatever the offsets hold): written out
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int n = __shfl_up(v, o, 64);
@@ -223,9 +223,7 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_kernel(const T* __restrict_
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                float v = gate[i];
-                v += __shfl_xor(v, 16, 64);
-                v += __shfl_xor(v, 32, 64);
+                const float v = quad_sum(gate[i]);
                 if (g == 0) Ps[wn * TM + wm * 64 + i * 16 + li] = v;
             }
         }
@@ -269,8 +267,7 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_kernel(const T* __restrict_
         }
         // lsum: lane (g, li) summed the rows of its K slots; the 4 groups partition the tile's rows and
         // all 16 li lanes of a group hold the same value -> total = sum over g = 2 shuffles
-        lsum += __shfl_xor(lsum, 16, 64);
-        lsum += __shfl_xor(lsum, 32, 64);
+        lsum = quad_sum(lsum);
         // ---------------- the unit's partial: (max, sum, acc[S1]) ----------------
         store_partial<S1>(L, partials + (int64_t)unit * (2 + S1), m_new, lsum, o);
     }
@@ -507,9 +504,7 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_mb_kernel(const T* __restri
             for (int k = 0; k < KMAX; ++k)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    float v = gate[k][i];
-                    v += __shfl_xor(v, 16, 64);
-                    v += __shfl_xor(v, 32, 64);
+                    const float v = quad_sum(gate[k][i]);
                     if (g == 0) Ps[(k * 2 + wn) * TM + wm * 64 + i * 16 + li] = v;
                 }
         }
@@ -564,8 +559,7 @@ __global__ __launch_bounds__(256, 2) void abmil_bags_mb_kernel(const T* __restri
                     }
                 }
             }
-            lsum += __shfl_xor(lsum, 16, 64);
-            lsum += __shfl_xor(lsum, 32, 64);
+            lsum = quad_sum(lsum);
             store_partial<S1>(L, partials + ((int64_t)unit * K + k) * (2 + S1), m_new, lsum, o);
         }
     }

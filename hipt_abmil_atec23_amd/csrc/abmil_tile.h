@@ -1,8 +1,9 @@
 // What the single-bag kernel (abmil.hip) and the ragged multi-bag kernel (abmil_bags.hip) of the fused CLAM_SB / ABMIL row tile share:
-// tile height, LDS budget and carve of one [T, S1, S2] instantiation, lane geometry, the swizzled h1 image, the gate's two
-// transcendental functions, tile_max and store_partial, bag_head (the tail of both combine kernels) and the one table of supported
+// tile height, LDS budget and carve of one [T, S1, S2] instantiation, lane geometry, the swizzled h1 image,
+// tile_max and store_partial, bag_head (the tail of both combine kernels) and the one table of supported
 // widths (visit_width); and, of the multi-bag tile passes (abmil_bags.hip, abmil_narrow.hip), the unit record and the grid.  The GEMM phases and the fp32 pooling are still written out in both kernels: lifted into functions here they
-// compiled to different, slower code.
+// compiled to different, slower code.  The gate's sigmoid_f / tanh_f and the shuffle reductions (wave_*, quad_sum)
+// are common.h's: the training step (clam_train.hip) recomputes the gate with the same two functions.
 #pragma once
 #include <cstdlib>
 
@@ -11,12 +12,6 @@
 namespace abmil_tile {
 
 constexpr int TM = 128;  // rows per tile
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float tanh_f(float x) {
-    // 1 - 2/(e^{2x}+1): exact limits at +-inf, abs error ~1e-7 elsewhere
-    return 1.0f - 2.0f / (expf(2.0f * x) + 1.0f);
-}
 
 template <typename T, int S1, int S2> struct AG {
     static constexpr int KB = Tr<T>::KB;

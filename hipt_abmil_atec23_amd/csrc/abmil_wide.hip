@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void abmil_wide_kernel(const T* __restrict__ b
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 float v = gate[i];
-                v += __shfl_xor(v, 16, 64);
+                v += __shfl_xor(v, 16, 64);  // (quad_sum of common.h, written out: the call compiles to different code here)
                 v += __shfl_xor(v, 32, 64);
                 if (g == 0) Ps[wave * R + i * 16 + li] = v;
             }

@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const T* __restrict__ qkv,
                 if (t * 16 + 4 * g + i >= ntok) s[t][i] = -INFINITY;
                 m = fmaxf(m, s[t][i]);
             }
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        m = quad_max(m);
         float l = 0.f;
 #pragma unroll
         for (int t = 0; t < NKT; ++t)
@@ -124,9 +123,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const T* __restrict__ qkv,
                 s[t][i] = exp2f((s[t][i] - m) * sl2e);
                 l += s[t][i];
             }
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / quad_sum(l);
 
         if constexpr (WRITE_P) {
             if (qvalid) {

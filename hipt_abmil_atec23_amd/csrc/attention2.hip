@@ -74,8 +74,7 @@ __device__ __forceinline__ void finish(f32x4 (&s)[NQ][NKT], bf16_t* __restrict__
             m = __builtin_fmaxf(__builtin_fmaxf(m, s[a][t][0]), s[a][t][1]);  // -> v_max3_f32
             m = __builtin_fmaxf(__builtin_fmaxf(m, s[a][t][2]), s[a][t][3]);
         }
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        m = quad_max(m);
         const float ms = -m * sl2e;
         const f32x2 sc2 = {sl2e, sl2e}, ms2 = {ms, ms};
         f32x2 l2 = {0.f, 0.f};
@@ -94,10 +93,7 @@ __device__ __forceinline__ void finish(f32x4 (&s)[NQ][NKT], bf16_t* __restrict__
                 s[a][t][2 * h + 1] = e[1];
             }
         }
-        float l = l2[0] + l2[1];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        inv[a] = 1.0f / l;
+        inv[a] = 1.0f / quad_sum(l2[0] + l2[1]);
     }
     // ---- O^T = V^T P^T: o[a][dt][i] = O[q = li][d = 16dt + 4g + i]; key tiles in pairs (K = 32 per MFMA) ----
     f32x4 o[NQ][DH / 16];

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void aug_sum_kernel(const uint8_t* __restrict_
             if (x0 + j < cols) s += lum(R[j], Gc[j], B[j]);
     }
     // <= 256 threads x 16 pixels x 255: a workgroup's sum fits 32 bits; one 64-bit atomic per workgroup
-#pragma unroll
+#pragma unroll  // (wave_sum of common.h, written out: the call compiles to different code here)
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     __shared__ uint32_t part[256 / 64];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;

@@ -22,15 +22,6 @@ constexpr int BS_THREADS = 256;
 constexpr int BS_WAVES = BS_THREADS / 64;
 constexpr int BS_MAX_K = HIPT_BOOTSTRAP_MAX_CLASSES;
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 // dynamic LDS: cnt int[n] | E int[n + 1] | lab uint8[n] (y | y_hat << 4)
 __global__ __launch_bounds__(BS_THREADS) void bootstrap_kernel(const int* __restrict__ Y, const int* __restrict__ Yh,
                                                                const int* __restrict__ order, const int* __restrict__ tie, int n, int K,
@@ -116,7 +107,7 @@ __global__ __launch_bounds__(BS_THREADS) void bootstrap_kernel(const int* __rest
                 acc += (long long)w * (long long)(E[lo] + E[hi]);
             }
         }
-#pragma unroll
+#pragma unroll  // (wave_sum of common.h, written out: on a 64-bit value the call compiles to different code)
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
         if (lane == 0) wnum[wave] = acc;
         __syncthreads();

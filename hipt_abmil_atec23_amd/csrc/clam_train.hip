@@ -32,8 +32,6 @@ constexpr int TR = 16;    // bag rows per workgroup tile
 constexpr int KMAX = 8;   // attention branches / classes handled on chip
 constexpr int JB = 8;     // output columns a thread accumulates at a time (x 16 column groups = 128 columns per pass)
 
-__device__ __forceinline__ float sigmoid_t(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float tanh_t(float x) { return 1.0f - 2.0f / (expf(2.0f * x) + 1.0f); }  // exact limits, ~1e-7 abs
 __device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) {
     return __builtin_fmaf(a[3], b[3], __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])));
 }
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(256) void clam_train_fwd_rows(const float* __restri
         for (int jj = 0; jj < JB; ++jj) {
             const int j = c0 + 16 * jj;
             if (j < S2) {
-                const float t = tanh_t(au[jj] + w.ba[j]), s = sigmoid_t(av[jj] + w.bb[j]);
+                const float t = tanh_f(au[jj] + w.ba[j]), s = sigmoid_f(av[jj] + w.bb[j]);  // the forward's own (common.h)
                 ts[r * pad4(S2) + j] = t;
                 ss[r * pad4(S2) + j] = s;
                 float g = t * s;

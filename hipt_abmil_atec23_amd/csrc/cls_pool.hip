@@ -130,8 +130,7 @@ __global__ __launch_bounds__(CP_THREADS, 2) void cls_pool_kernel(const ClsPoolPa
                 s[r] = 16 * kb + 4 * g + r < CP_NTOK ? s[r] * p.scale : -INFINITY;
                 bm = fmaxf(bm, s[r]);
             }
-            bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-            bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+            bm = quad_max(bm);
             const float mn = fmaxf(m, bm);  // (finite: every block holds a valid token)
             const float alpha = __expf(m - mn);
             bf16x4 pb;
@@ -141,8 +140,7 @@ __global__ __launch_bounds__(CP_THREADS, 2) void cls_pool_kernel(const ClsPoolPa
                 pb[r] = (bf16_t)__expf(s[r] - mn);
                 ps += (float)pb[r];
             }
-            ps += __shfl_xor(ps, 16, 64);
-            ps += __shfl_xor(ps, 32, 64);
+            ps = quad_sum(ps);
             l = l * alpha + ps;
             m = mn;
 #pragma unroll

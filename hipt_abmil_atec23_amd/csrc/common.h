@@ -1,4 +1,6 @@
-// Shared device helpers for the gfx950 kernels (wave64, MFMA 16x16, LDS tiles of 128-byte rows).
+// Shared device helpers for the gfx950 kernels (wave64, MFMA 16x16, LDS tiles of 128-byte rows): vector types and the per-type MFMA
+// traits, bf16 packing and stores, the shuffle reductions and the wave scan (wave_*, quad_*, half_*), the gate's sigmoid_f / tanh_f,
+// LDS-DMA and the "invisible" LDS accesses, wait_vm<N>, blend_u8, xcd_remap; then the host-side error and environment helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,7 +77,12 @@ __device__ __forceinline__ float gelu_erf(float x) {  // nn.GELU() default (exac
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ---- wave-level reductions and scans ------------------------------------------------
+// THE one definition of each: the order of the xor steps is part of a kernel's bits (fp32 sums), so a kernel that needs another
+// order writes it out locally and says why.  All return the result in every participating lane.  A few sites keep the steps written
+// out because the call compiled to other code there (each says so); the 64-bit wave_sum sites are all among them.
+// wave_sum / wave_max: all 64 lanes, xor 32, 16, 8, 4, 2, 1.
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -84,6 +91,42 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+// quad_sum / quad_max: across the four 16-lane groups (the lanes that share lane & 15: one row of an MFMA fragment), xor 16 then 32.
+// (fp contract off in the sums: the pragma holds per function body, so a caller's own does not reach in here)
+__device__ __forceinline__ float quad_sum(float v) {
+#pragma clang fp contract(off)
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+__device__ __forceinline__ float quad_max(float v) {
+    v = fmaxf(v, __shfl_xor(v, 16, 64));
+    v = fmaxf(v, __shfl_xor(v, 32, 64));
+    return v;
+}
+// half_sum / half_max: across the two 32-lane halves (32x32 MFMA fragments), xor 32.
+__device__ __forceinline__ float half_sum(float v) {
+#pragma clang fp contract(off)
+    return v + __shfl_xor(v, 32, 64);
+}
+__device__ __forceinline__ float half_max(float v) { return fmaxf(v, __shfl_xor(v, 32, 64)); }
+// inclusive scan over the lanes of a wave (lane = threadIdx & 63): lane l gets v_0 + .. + v_l.  T: int, unsigned.
+template <typename T> __device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// The gate's two transcendental functions (CLAM / ABMIL forward and the training step's recomputation: the gradients are held
+// against the forward's bits, so both use THESE).
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float tanh_f(float x) {
+    // 1 - 2/(e^{2x}+1): exact limits at +-inf, abs error ~1e-7 elsewhere
+    return 1.0f - 2.0f / (expf(2.0f * x) + 1.0f);
 }
 
 // async global -> LDS, 16 bytes per lane; LDS destination = wave-uniform base + lane*16
@@ -115,7 +158,9 @@ __device__ __forceinline__ u32x2 lds_ld_tr64(uint32_t a) {  // ds_read_b64_tr_b1
 __device__ __forceinline__ void lds_st32(uint32_t a, float v) { asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(v) : "memory"); }
 __device__ __forceinline__ void lds_st64(uint32_t a, u32x2 v) { asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(v) : "memory"); }
 
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// wait until at most N of this wave's vector-memory operations (loads, LDS-DMA, stores) are still in flight
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void wait_vm0() { wait_vm<0>(); }
 
 // The heat-maps' blend with the slide (heatmap.hip, hier_heatmap.hip): sat_u8(rint(float32(img) * a + float32(canvas) * b)),
 // a = float32(alpha), b = float32(1 - alpha) -- cv2.addWeighted's formula.  Both files are built with -ffp-contract=off: the two

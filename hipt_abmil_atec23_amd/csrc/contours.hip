@@ -194,7 +194,7 @@ __global__ __launch_bounds__(CT_SCAN_THREADS) void ct_scan(uint2* bcnt, int nblk
     for (int base = 0; base < nblk; base += CT_SCAN_THREADS) {
         const int idx = base + tid;
         const uint2 v = idx < nblk ? bcnt[idx] : make_uint2(0u, 0u);
-        uint2 inc = v;
+        uint2 inc = v;  // (wave_incl_scan of common.h on a pair, written out: two calls compile to different code)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const unsigned ax = __shfl_up(inc.x, o, 64), ay = __shfl_up(inc.y, o, 64);

@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void embed32_kernel(const EmbedParams p) {
                         sum += v;
                     }
             });
-            sum += __shfl_xor(sum, 32, 64);
+            sum += __shfl_xor(sum, 32, 64);  // (half_sum of common.h, written out here and below: the call compiles to different code)
             const float mean = sum / (float)D;
             float var = 0.f;
             sfor<0, NOT>([&](auto O_) __attribute__((always_inline)) {

@@ -89,10 +89,6 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, int m, int n, f32x
         store4<T>((T*)p.out + orow * p.ldc + n, v);
 }
 
-template <int N> __device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <typename T, int ALOAD, int FLAGS>
 __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -386,7 +382,7 @@ __global__ __launch_bounds__(64) void lngemm_small_kernel(const GemmParams p) {
     for (int s = 0; s < nk; ++s)
 #pragma unroll
         for (int e = 0; e < EPC; ++e) sum += v[s][e];
-    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 16, 64);  // (quad_sum of common.h compiles to a different register allocation here)
     sum += __shfl_xor(sum, 32, 64);
     const float mean = sum / (float)K;
     float q = 0.f;

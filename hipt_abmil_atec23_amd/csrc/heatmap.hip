@@ -73,15 +73,6 @@ __device__ __forceinline__ int4 hm_clip(int x, int y, int pw, int ph, int w, int
     return r;
 }
 
-__device__ __forceinline__ int hm_wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 // steps 1 and 3: FILL = false counts, FILL = true appends (list start = offs + boff of the tile's segment)
 template <bool FILL>
 __global__ __launch_bounds__(256) void hm_bin_kernel(const int* __restrict__ xy, int N, int pw, int ph, int w, int h, int ntx,
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(HM_SCAN) void hm_scan_local_kernel(const int* __res
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int i = blockIdx.x * HM_SCAN + t;
     const int v = i < nt ? cnt[i] : 0;
-    const int incl = hm_wave_incl_scan(v, lane);
+    const int incl = wave_incl_scan(v, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     int base = 0;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(HM_SCAN) void hm_scan_blocks_kernel(int* __restrict
     for (int b0 = 0; b0 < nb; b0 += HM_SCAN) {
         const int i = b0 + t;
         const int v = i < nb ? bsum[i] : 0;
-        const int incl = hm_wave_incl_scan(v, lane);
+        const int incl = wave_incl_scan(v, lane);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
         int base = carry, total = 0;

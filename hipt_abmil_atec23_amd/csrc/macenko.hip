@@ -142,7 +142,7 @@ template <bool IL> __global__ __launch_bounds__(MK_THREADS) void mk_cov_kernel(c
     // a fixed tree: lanes of a wave, then the four waves in order
 #pragma unroll
     for (int i = 0; i < MK_SLAB; ++i) {
-#pragma unroll
+#pragma unroll  // (wave_sum of common.h, written out: on a double the call compiles to different code)
         for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o, 64);
     }
     if ((threadIdx.x & 63) == 0) {

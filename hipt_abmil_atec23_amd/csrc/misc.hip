@@ -88,15 +88,11 @@ __global__ __launch_bounds__(64) void cls_init_img_kernel(float* __restrict__ x,
         v[j] = cls[lane + 64 * j] + pos[lane + 64 * j];
         sum += v[j];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum / (float)D;
+    const float mean = wave_sum(sum) / (float)D;
     float var = 0.f;
 #pragma unroll
     for (int j = 0; j < 6; ++j) var = __builtin_fmaf(v[j] - mean, v[j] - mean, var);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-    const float rstd = 1.0f / sqrtf(var / (float)D + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)D + eps);
     const int64_t R = (int64_t)s * ntok, F = R >> 4;
     const int li = (int)(R & 15);
 #pragma unroll

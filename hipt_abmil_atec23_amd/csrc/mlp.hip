@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "launch.h"
 #include "mlp_common.h"
+#include "pipe_common.h"  // ln_rows, LGKM
 
 namespace {
 
@@ -30,23 +31,22 @@ constexpr int TMR = 128;               // rows per full workgroup
 constexpr int SLAB_BYTES = 128 * 128;  // 128 weight rows x 64 bf16
 constexpr int NSLOT = 8;
 
-template <int N> __device__ __forceinline__ void wait_vm_n() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 template <int U> __device__ __forceinline__ void wait_units(int units) {  // 4*U DMA instructions per unit per wave
     if constexpr (U == 2) {
         switch (units) {
-            case 0: wait_vm_n<0>(); break;
-            case 1: wait_vm_n<8>(); break;
-            default: wait_vm_n<16>(); break;
+            case 0: wait_vm<0>(); break;
+            case 1: wait_vm<8>(); break;
+            default: wait_vm<16>(); break;
         }
     } else {
         switch (units) {
-            case 0: wait_vm_n<0>(); break;
-            case 1: wait_vm_n<4>(); break;
-            case 2: wait_vm_n<8>(); break;
-            case 3: wait_vm_n<12>(); break;
-            case 4: wait_vm_n<16>(); break;
-            case 5: wait_vm_n<20>(); break;
-            default: wait_vm_n<24>(); break;
+            case 0: wait_vm<0>(); break;
+            case 1: wait_vm<4>(); break;
+            case 2: wait_vm<8>(); break;
+            case 3: wait_vm<12>(); break;
+            case 4: wait_vm<16>(); break;
+            case 5: wait_vm<20>(); break;
+            default: wait_vm<24>(); break;
         }
     }
 }
@@ -215,10 +215,10 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
 #pragma unroll
             for (int nf = 0; nf < NF2; ++nf) acc2[mf][nf] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+// this kernel's reads take the offset as TEXT (an expression the assembler folds), not as pipe_common.h's immediate operand
+#undef DSR128
+#undef DSR64
 #define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define LGKM(n)                                             \
-    asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0)
 // before slab j of chunk c: if it opens a ring unit, wait until that unit has landed (at most the NUS-2
 // later units in flight; 4*U DMA instructions per unit per wave), barrier, refill the slot freed by the
 // previous unit (with the matching unit of the next pass once this pass is fully issued)
@@ -348,7 +348,6 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
         MSTAMP(3);
         if (HIPT_STAMPS_ON(p.stamps) && threadIdx.x == 0 && seq == 0) p.stamps[(size_t)blockIdx.x * 16 + 9] = __builtin_amdgcn_s_memtime();
 #undef DSR128
-#undef LGKM
 #undef SLAB_SYNC
 #undef SLAB_ADDR
 

@@ -1,5 +1,5 @@
-// Device helpers shared by the fused-MLP kernels (mlp.hip: generic persistent kernel; mlp16.hip: the streaming
-// D = 384 kernel on its packed weight image).
+// The GELU forms of the fused-MLP kernels (mlp.hip: generic persistent kernel; mlp16.hip: the streaming
+// D = 384 kernel on its packed weight image): gelu2, gelu1, gelu1s.  Their LayerNorm-2 is ln_rows / ln_rows_lds of pipe_common.h.
 #pragma once
 #include "common.h"
 
@@ -56,48 +56,3 @@ __device__ __forceinline__ float gelu1s(float xs) {
     const float d = __builtin_amdgcn_exp2f(xs * q) + 1.0f;
     return xs * __builtin_amdgcn_rcpf(d);
 }
-
-template <int NCH>
-__device__ __forceinline__ void ln_rows(f32x4 (&v)[NCH][2], const float* gam, const float* bet, int K, float eps, int g,
-                                        u32x4 (&out)[NCH]) {
-#pragma clang fp contract(off)
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s += v[c][0][e] + v[c][1][e];
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mean = s / (float)K;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float a = v[c][0][e] - mean, b = v[c][1][e] - mean;
-            q = __builtin_fmaf(a, a, q);
-            q = __builtin_fmaf(b, b, q);
-        }
-    q += __shfl_xor(q, 16, 64);
-    q += __shfl_xor(q, 32, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)K + eps);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int k0 = (g + 4 * c) * 8;
-        const f32x4 g0 = *(const f32x4*)(gam + k0), g1 = *(const f32x4*)(gam + k0 + 4);
-        const f32x4 b0 = *(const f32x4*)(bet + k0), b1 = *(const f32x4*)(bet + k0 + 4);
-        f32x4 y0, y1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y0[e] = __builtin_fmaf((v[c][0][e] - mean) * rstd, g0[e], b0[e]);
-            y1[e] = __builtin_fmaf((v[c][1][e] - mean) * rstd, g1[e], b1[e]);
-        }
-        u32x4 o;
-        o[0] = pack_bf16x2(y0[0], y0[1]);
-        o[1] = pack_bf16x2(y0[2], y0[3]);
-        o[2] = pack_bf16x2(y1[0], y1[1]);
-        o[3] = pack_bf16x2(y1[2], y1[3]);
-        out[c] = o;
-    }
-}
-

@@ -530,7 +530,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
             float mc = s8;
 #pragma unroll
             for (int i = 0; i < 16; ++i) mc = fmaxf(mc, Sc[0][i]);
-            mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
+            mc = half_max(mc);
             const float mcs = -mc * p.sl2e;
             float lc = 0.f;
 #pragma unroll
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
             }
             const float e8 = __builtin_amdgcn_exp2f(__builtin_fmaf(s8, p.sl2e, mcs));
             lc += e8;
-            lc += __shfl_xor(lc, 32, 64);
+            lc = half_sum(lc);
             const u32x4 pc0 = pack8<0>(Sc[0]), pc1 = pack8<1>(Sc[0]);
             const u32x4 pc8 = {pack_bf16x2(e8, 0.f), 0u, 0u, 0u};
             f32x16 Oc[2];
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
         // tile 8 holds one key (register 0 of lane half 0): the rest is padding and gets probability 0 without an exponential
         const float s8m = hh == 0 ? S[8][0] : -INFINITY;
         m = fmaxf(m, s8m);
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        m = half_max(m);
         const float ms = -m * p.sl2e;
         auto exp_quarter = [&](auto KT_, auto Q_) __attribute__((always_inline)) {  // registers 4 q ..+3 of tile kt -> probabilities
             constexpr int kt = decltype(KT_)::value, q = decltype(Q_)::value;
@@ -698,8 +698,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
         QSTAMP(5);
         // store: registers 4 q ..+3 of tile t = dims 32 t + 8 q + 4 hh ..+3 = chunk 8 hs + 4 t + q, bytes 8 hh ..+7
         if constexpr (!CLSONLY) {
-            l += __shfl_xor(l, 32, 64);
-            const float inv = 1.0f / l;
+            const float inv = 1.0f / half_sum(l);
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "launch.h"
+#include "pipe_common.h"  // ln_rows, LGKM
 
 namespace {
 
@@ -33,17 +34,16 @@ constexpr int GB_BYTES = 2 * 384 * 4;  // gamma | beta staging (K <= 384)
 constexpr int MAXN = 2048;             // bias staging (floats)
 constexpr int SEQ_LDS = NSLOT * SLAB_BYTES + GB_BYTES + MAXN * 4;
 
-template <int N> __device__ __forceinline__ void wait_vm_n() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // wait until at most `slabs` later slabs (4 DMA instructions each, per wave) are still in flight
 __device__ __forceinline__ void wait_slabs(int slabs) {
     switch (slabs) {
-        case 0: wait_vm_n<0>(); break;
-        case 1: wait_vm_n<4>(); break;
-        case 2: wait_vm_n<8>(); break;
-        case 3: wait_vm_n<12>(); break;
-        case 4: wait_vm_n<16>(); break;
-        case 5: wait_vm_n<20>(); break;
-        default: wait_vm_n<24>(); break;
+        case 0: wait_vm<0>(); break;
+        case 1: wait_vm<4>(); break;
+        case 2: wait_vm<8>(); break;
+        case 3: wait_vm<12>(); break;
+        case 4: wait_vm<16>(); break;
+        case 5: wait_vm<20>(); break;
+        default: wait_vm<24>(); break;
     }
 }
 
@@ -61,52 +61,6 @@ __device__ __forceinline__ void seq_epilogue(const SeqGemmParams& p, uint32_t bi
         }
     }
     store4<bf16_t>((bf16_t*)p.out + row * p.ldc + n, v);
-}
-
-// LayerNorm of one row held by the 4 lanes (lane>>4 = 0..3) that share lane&15: lane owns chunks
-// g + 4c (8 elements each).  Two-pass statistics (mean, centred variance) as torch; output bf16 fragments.
-template <int NCH>
-__device__ __forceinline__ void ln_rows(f32x4 (&v)[NCH][2], const float* gam, const float* bet, int K, float eps, int g,
-                                        u32x4 (&out)[NCH]) {
-#pragma clang fp contract(off)  // every multiply-add written out: all unrolled instances must round alike (pipe_common.h)
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s += v[c][0][e] + v[c][1][e];
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mean = s / (float)K;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float a = v[c][0][e] - mean, b = v[c][1][e] - mean;
-            q = __builtin_fmaf(a, a, q);
-            q = __builtin_fmaf(b, b, q);
-        }
-    q += __shfl_xor(q, 16, 64);
-    q += __shfl_xor(q, 32, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)K + eps);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int k0 = (g + 4 * c) * 8;
-        const f32x4 g0 = *(const f32x4*)(gam + k0), g1 = *(const f32x4*)(gam + k0 + 4);
-        const f32x4 b0 = *(const f32x4*)(bet + k0), b1 = *(const f32x4*)(bet + k0 + 4);
-        f32x4 y0, y1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y0[e] = __builtin_fmaf((v[c][0][e] - mean) * rstd, g0[e], b0[e]);
-            y1[e] = __builtin_fmaf((v[c][1][e] - mean) * rstd, g1[e], b1[e]);
-        }
-        u32x4 o;
-        o[0] = pack_bf16x2(y0[0], y0[1]);
-        o[1] = pack_bf16x2(y0[2], y0[3]);
-        o[2] = pack_bf16x2(y1[0], y1[1]);
-        o[3] = pack_bf16x2(y1[2], y1[3]);
-        out[c] = o;
-    }
 }
 
 #define STAMP(k)                                                                                   \
@@ -233,9 +187,6 @@ __global__ __launch_bounds__(256, 1) void seqgemm_kernel(const SeqGemmParams p) 
             const uint32_t a1 = lbase + (i % NSLOT) * SLAB_BYTES + foff[1];
             u32x4 wa0, wa1, wb0, wb1;
 #define DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define LGKM(n)                                          \
-    asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0)
 #define MMA8(w0, w1, ks, pr)                                                 \
     _Pragma("unroll") for (int mf = 0; mf < 4; ++mf) {                       \
         Tr<bf16_t>::mma16(acc[mf][2 * (pr)], w0, af[mf][kt * 2 + (ks)]);     \
@@ -259,7 +210,6 @@ __global__ __launch_bounds__(256, 1) void seqgemm_kernel(const SeqGemmParams p) 
             LGKM(2); MMA8(wa0, wa1, 1, 2);
             LGKM(0); MMA8(wb0, wb1, 1, 3);
 #undef DSR
-#undef LGKM
 #undef MMA8
         }
         if (t == 0) STAMP(3);

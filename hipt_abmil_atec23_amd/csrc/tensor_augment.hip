@@ -137,7 +137,7 @@ __device__ __forceinline__ void fetch(const uint8_t* __restrict__ src, const TaG
 
 // the sum of a workgroup's values, the same in every thread; a fixed tree: the same bits whatever runs beside it
 __device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
+#pragma unroll  // (wave_sum of common.h, written out: on a double the call compiles to different code)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
     __syncthreads();
