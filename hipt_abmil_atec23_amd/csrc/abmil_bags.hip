@@ -607,13 +607,12 @@ __global__ __launch_bounds__(1024) void abmil_bags_mb_combine_kernel(const float
         float L = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) L += red[i];
-        {
-            const int c = tid & 127, part = tid >> 7;
-            if (c < S1) {
-                float a = 0.f;
-                for (int t = part; t < T; t += 8) a += P[t * tstride + 2 + c] * expf(P[t * tstride] - mx);
-                Cs[part * S1 + c] = a;
-            }
+        // 128 columns x 8 parts = 1024 threads at a time (S1 <= 128: one round; the wide heads of abmil_wide_mb.hip: 2 or 4)
+        for (int c = tid & 127; c < S1; c += 128) {
+            const int part = tid >> 7;
+            float a = 0.f;
+            for (int t = part; t < T; t += 8) a += P[t * tstride + 2 + c] * expf(P[t * tstride] - mx);
+            Cs[part * S1 + c] = a;
         }
         __syncthreads();
         for (int c = tid; c < S1; c += 1024) {

@@ -245,6 +245,10 @@ int hipt_clam_bags_mb_tiles_launch(const hipt_clam_weights* w, const void* bags,
 int hipt_clam_bags_mb_combine_launch(const float* partials, const int* tile_start, int max_units, int B,
                                      const hipt_clam_weights* w, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                                      hipStream_t st);
+// the K-branch tile pass for the wide heads (abmil_wide_mb.hip; widths: visit_wide, w->n_att = 2..4): abmil_wide.hip's sub-tile walk with K
+// scores and K running records; the partials in the layout of hipt_clam_bags_mb_tiles_launch, for hipt_clam_bags_mb_combine_launch
+int hipt_clam_wide_mb_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
+                                   int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
 
 // ---- bootstrapped evaluation metrics (bootstrap.hip) ----
 size_t hipt_bootstrap_lds_bytes(int n);

@@ -139,7 +139,9 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     fp32 bar (1e-4); they are not bit-equal to it.  ``wide_one_call=True`` likewise sets ``bags_wide`` for the duration of the call:
     the wide heads (``tiny``, ``small``, ``big``, ``small_resnet18``: ``hipt_clam_wide_bags_supported``) then go through
     ``hipt_clam_sb_forward_bags_wide``.  ``False`` (the default) leaves the model's own ``bags_wide`` in force -- which is how a caller of
-    ``dropin.install(evaluation=True)`` / ``(validation=True)`` opts in: ``model.bags_wide = True``."""
+    ``dropin.install(evaluation=True)`` / ``(validation=True)`` opts in: ``model.bags_wide = True``.  A ``CLAM_MB`` at the wide widths
+    needs ``bags_one_call`` as well to take ``hipt_clam_mb_forward_bags_wide``; this function sets only ``bags_wide``, so the model's own
+    ``bags_one_call`` (default False: the loop) governs here."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     fb = getattr(model, "forward_bags", None)
     with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call), _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)):
@@ -178,7 +180,9 @@ def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     Arguments as :func:`evaluate_split`.  A ``CLAM_MB`` model runs with ``bags_one_call = mb_one_call`` for the duration of the call,
     a ``CLAM_SB`` with ``bags_narrow = narrow_one_call``: for the narrow heads (``hipt_smaller``, ``hipt_smallest``, ...) the numbers
     then come from the one-call kernel; they equal the loop's (``narrow_one_call=False``) within the fp32 bar (1e-4), not bit for bit.
-    ``wide_one_call`` as in :func:`evaluate_split` (the wide heads; the default keeps the model's own ``bags_wide``).
+    ``wide_one_call`` as in :func:`evaluate_split` (the wide heads; the default keeps the model's own ``bags_wide``).  A ``CLAM_MB`` at
+    the wide widths with 2 to 4 classes takes ``hipt_clam_mb_forward_bags_wide`` when both hold: ``mb_one_call`` (set here, default True)
+    and ``bags_wide`` (``wide_one_call=True`` or the model's own); its numbers equal the loop's within the fp32 bar in fp32, not bit for bit.
     The AUC stays with the caller (``labels`` and ``prob`` are its inputs).  The model is put in eval mode, as ``validate_clam`` does."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     n = len(bags)

@@ -150,13 +150,15 @@ class BagOffsets:
 
 # form -> (native call, its workspace size, shapes of (A_raw, M, logits / Y_prob) for B bags of `rows` rows in all); Y_hat is [B]
 _sb_shapes = lambda w, B, rows: ((rows,), (B, w.s1), (B, w.n_classes))
+_mb_shapes = lambda w, B, rows: ((w.n_att, rows), (B, w.n_att, w.s1), (B, w.n_att))
 _BAGS_FORMS = {
     "sb": ("hipt_clam_sb_forward_bags", "hipt_clam_bags_workspace_bytes", _sb_shapes),
     "narrow": ("hipt_clam_sb_forward_bags_narrow", "hipt_clam_narrow_bags_workspace_bytes", _sb_shapes),
     "wide": ("hipt_clam_sb_forward_bags_wide", "hipt_clam_wide_bags_workspace_bytes", _sb_shapes),
-    "mb": ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes",
-           lambda w, B, rows: ((w.n_att, rows), (B, w.n_att, w.s1), (B, w.n_att))),
+    "mb": ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes", _mb_shapes),
+    "mb_wide": ("hipt_clam_mb_forward_bags_wide", "hipt_clam_mb_wide_bags_workspace_bytes", _mb_shapes),
 }
+BAGS_FORMS_K = ("mb", "mb_wide")  # the forms with K = w.n_att rows of A_raw and K pooled vectors per bag
 
 
 def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None, form: str = "sb"):
@@ -208,6 +210,12 @@ def clam_mb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_on
     Returns ``(A_raw [K, rows], M [B, K, S1], logits [B, K], Y_prob [B, K], Y_hat [B])``; bag ``b`` is the columns
     ``[offsets[b], offsets[b+1])`` of ``A_raw``."""
     return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb")
+
+
+def clam_mb_forward_bags_wide(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_mb_forward_bags_wide``: :func:`clam_mb_forward_bags` for the wide heads (``hipt_clam_mb_wide_bags_supported``:
+    ``(S1, S2)`` in {(256, 64), (512, 256), (512, 384)}, fp32 and bf16, 2 to 4 branches).  Arguments and results as there."""
+    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb_wide")
 
 
 def topk_segments(A: torch.Tensor, offsets: BagOffsets, k: int, want_global: bool = True):

@@ -279,7 +279,7 @@ class CLAM_SB(WeightImageCache, nn.Module):
     ``[S0, S1, S2]`` list."""
 
     _multi = False
-    bags_wide = False    # forward_bags takes hipt_clam_sb_forward_bags_wide (all bags in one call) for the wide heads (tiny, small, big, small_resnet18); False: the loop over forward
+    bags_wide = False    # forward_bags takes hipt_clam_sb_forward_bags_wide (all bags in one call) for the wide heads (tiny, small, big, small_resnet18); False: the loop over forward.  CLAM_MB: together with bags_one_call, hipt_clam_mb_forward_bags_wide
     bags_narrow = False  # forward_bags takes hipt_clam_sb_forward_bags_narrow (all bags in one call) for the narrow heads the multi-bag kernel does not have; False: the loop over forward
 
     def __init__(self, gate=True, size_arg="small", dropout=0.0, k_sample=8, n_classes=2,
@@ -544,7 +544,10 @@ class CLAM_SB(WeightImageCache, nn.Module):
         lib = N.lib()
         if self._multi:
             w = self._pack_stacked(device) if self.bags_one_call else None
-            return (w, "mb") if w is not None and lib.hipt_clam_mb_bags_supported(C_.byref(w)) else None
+            if w is not None and lib.hipt_clam_mb_bags_supported(C_.byref(w)):
+                return w, "mb"
+            wide = w is not None and self.bags_wide and lib.hipt_clam_mb_wide_bags_supported(C_.byref(w))   # tiny, small, big, small_resnet18, K = 2..4: where asked for
+            return (w, "mb_wide") if wide else None
         w = self._pack(device)
         if lib.hipt_clam_bags_supported(C_.byref(w)):
             return w, "sb"   # (a width both kernels have keeps the wide one)
@@ -568,7 +571,10 @@ class CLAM_SB(WeightImageCache, nn.Module):
         by a ``CLAM_SB`` with ``bags_narrow`` set (default False: the loop, with the bits of ``forward``); its numbers equal the
         loop's within the fp32 bar (1e-4), not bit for bit.  A width both kernels have keeps the first.  The wide heads (``tiny``,
         ``small``, ``big``, ``small_resnet18``: ``hipt_clam_wide_bags_supported``) likewise have ``hipt_clam_sb_forward_bags_wide``, taken
-        by a ``CLAM_SB`` with ``bags_wide`` set (default False: the loop, with the bits of ``forward``).
+        by a ``CLAM_SB`` with ``bags_wide`` set (default False: the loop, with the bits of ``forward``).  A ``CLAM_MB`` at those widths
+        (``CLAM_MB()`` is built with ``small``) with 2 to 4 classes takes ``hipt_clam_mb_forward_bags_wide`` when BOTH ``bags_one_call``
+        and ``bags_wide`` are set (``hipt_clam_mb_wide_bags_supported``); with either off it keeps the loop and its bits.  The results
+        have the K-branch structure above.
 
         ``instance_eval=True`` with ``label`` (B class ids: a list, a numpy array or a tensor) adds what ``forward(h, label=,
         instance_eval=True)`` returns per bag (validate_clam, utils/core_utils.py:506-560): ``instance_loss`` (a ``[B]`` tensor),
@@ -594,7 +600,7 @@ class CLAM_SB(WeightImageCache, nn.Module):
             self._bags_route = "bags"
             x = Fn.as_compute(cat, w.dtype)
             A_raw, M, logits, Y_prob, Y_hat = Fn.clam_forward_bags(w, x, off, attention_only, form=form)
-            A2 = A_raw if form == "mb" else A_raw.view(1, -1)          # [K, rows] / [1, rows]
+            A2 = A_raw if form in Fn.BAGS_FORMS_K else A_raw.view(1, -1)   # [K, rows] / [1, rows]
             views = [A2[:, host[b]:host[b + 1]] for b in range(len(off))]
             if attention_only:
                 return views

@@ -387,9 +387,9 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
                          float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                          void* workspace, size_t ws_bytes, void* stream);
 
-/* CLAM forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).  The call exists in four
- * forms -- the mid-width gated heads, the narrow ones, the wide ones, the K branches of CLAM_MB -- each with its own <form>_supported, <form>_workspace_bytes and
- * forward entry point of one signature.  What holds for all four is stated here, once; each form below lists only what differs.
+/* CLAM forward over B bags in ONE call (the loop over slides of utils/eval_utils.py:115-179 and validate_clam).  The call exists in five
+ * forms -- the mid-width gated heads, the narrow ones, the wide ones, the K branches of CLAM_MB at the mid and at the wide widths -- each with its own
+ * <form>_supported, <form>_workspace_bytes and forward entry point of one signature.  What holds for all five is stated here, once; each form below lists only what differs.
  * bags: the bags' rows concatenated, [total_rows, S0] in w->dtype, 16-byte aligned; offsets_dev: int64[B + 1] in DEVICE memory, offsets[0] = 0,
  * increasing, offsets[B] = total_rows: bag b is rows [offsets[b], offsets[b+1]).  Every bag has at least one row.  The CONTENTS of the offsets
  * are the caller's responsibility (check them on the host before the upload); a bag whose offsets break the rules is left unwritten.
@@ -443,6 +443,19 @@ size_t hipt_clam_mb_bags_workspace_bytes(const hipt_clam_weights* w, int B, int6
 int hipt_clam_mb_forward_bags(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
                               int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                               void* workspace, size_t ws_bytes, void* stream);
+
+/* The same K-branch call for the heads WIDER than that form's (tiny, small -- what CLAM_MB() is built with by default --, big,
+ * small_resnet18).  Supported: hipt_clam_wide_bags_supported(w) -- (S1, S2) in {(256, 64), (512, 256), (512, 384)}, fp32 and bf16, S0 a
+ * multiple of 32 (fp32) / 64 (bf16) -- and 2 <= n_att <= 4 and n_att == n_classes.  Inputs, outputs and the K partials per work unit as
+ * hipt_clam_mb_forward_bags; the same unit table and per-bag combine; the tile pass is the wide form's sub-tile walk (64 rows in bf16,
+ * 32 in fp32, in a fixed order) with phase 1, the gate GEMM and tanh * sigmoid done once per sub-tile and K scores, K poolings and K
+ * running records behind them.  Rounding per branch as the wide form: in bf16 the bag, W1, Wa and Wb are bf16 and h1 is rounded to bf16 as
+ * the gate GEMM's operand only; the gate, the scores and the poolings (on unrounded h1) are fp32. */
+int hipt_clam_mb_wide_bags_supported(const hipt_clam_weights* w);
+size_t hipt_clam_mb_wide_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
+int hipt_clam_mb_forward_bags_wide(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                                   int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                   void* workspace, size_t ws_bytes, void* stream);
 
 /* CLAM_MB.forward (model_clam.py:226-264), inference, with ONE pass over the bag for all K = w->n_att attention branches (2 <= K <= 4; W1 and
  * [Wa; Wb] are shared by the branches, only wc / bc / the classifier rows differ):  A_raw[K, N] = the K logits of every row;
