@@ -158,6 +158,9 @@ SIGNATURES = {
     "hipt_clam_mb_wide_bags_supported": (_i, [_CW]),
     "hipt_clam_mb_wide_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
     "hipt_clam_mb_forward_bags_wide": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hipt_clam_mb_many_bags_supported": (_i, [_CW]),
+    "hipt_clam_mb_many_bags_workspace_bytes": (_sz, [_CW, _i, _i64]),
+    "hipt_clam_mb_forward_bags_many": (_i, [_CW, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hipt_clam_mb_supported": (_i, [_CW]),
     "hipt_clam_mb_workspace_bytes": (_sz, [_CW, _i]),
     "hipt_clam_mb_forward": (_i, [_CW, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),

@@ -1183,9 +1183,9 @@ int hipt_clam_sb_forward(const hipt_clam_weights* w, const void* bag, int N, int
     return HIPT_OK;
 }
 
-// ---- B bags in one call (abmil_bags.hip, abmil_narrow.hip, abmil_wide.hip, abmil_wide_mb.hip): unit table | tile_start | one partial per unit and branch; no state ----
-// The call exists in five forms -- the mid-width single-branch heads, the narrow heads, the wide heads, the K = n_att branches of CLAM_MB at the
-// mid widths and at the wide ones -- which share every line of the host side but the four things a ClamBagsForm names.
+// ---- B bags in one call (abmil_bags.hip, abmil_narrow.hip, abmil_wide.hip, abmil_wide_mb.hip, abmil_bags_mb8.hip): unit table | tile_start | one partial per unit and branch; no state ----
+// The call exists in six forms -- the mid-width single-branch heads, the narrow heads, the wide heads, the K = n_att branches of CLAM_MB at the
+// mid widths (2..4 branches; 5..8 branches) and at the wide ones -- which share every line of the host side but the four things a ClamBagsForm names.
 int hipt_clam_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && w->s0 > 0 && hipt_clam_fused_supported(w) ? 1 : 0; }
 int hipt_clam_narrow_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_narrow_supported(w) ? 1 : 0; }
 int hipt_clam_wide_bags_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_wide_supported(w) ? 1 : 0; }
@@ -1194,6 +1194,9 @@ int hipt_clam_mb_bags_supported(const hipt_clam_weights* w) {
 }
 int hipt_clam_mb_wide_bags_supported(const hipt_clam_weights* w) {
     return hipt_clam_wide_bags_supported(w) && w->n_att >= 2 && w->n_att <= 4 && w->n_att == w->n_classes ? 1 : 0;
+}
+int hipt_clam_mb_many_bags_supported(const hipt_clam_weights* w) {
+    return hipt_clam_bags_supported(w) && w->n_att >= 5 && w->n_att <= 8 && w->n_att == w->n_classes ? 1 : 0;
 }
 
 struct ClamBagsForm {
@@ -1226,6 +1229,11 @@ static const ClamBagsForm BAGS_MB_WIDE = {"clam_mb_forward_bags_wide", hipt_clam
                                           "%s: [%d,%d,%d] with %d branches / %d classes is not a wide K-branch head: (S1, S2) in {(256,64), "
                                           "(512,256), (512,384)}, S0 a multiple of 32 (fp32) / 64 (bf16), 2 <= branches <= 4, branches == "
                                           "classes"};
+static const ClamBagsForm BAGS_MB_MANY = {"clam_mb_forward_bags_many", hipt_clam_mb_many_bags_supported, att_branches,
+                                          hipt_clam_bags_mb8_tiles_launch, hipt_clam_bags_mb_combine_launch,
+                                          "%s: [%d,%d,%d] with %d branches / %d classes is not a many-branch head: the widths of "
+                                          "hipt_clam_sb_forward_bags, 5 <= branches <= 8, branches == classes (2..4 branches: "
+                                          "hipt_clam_mb_forward_bags)"};
 
 // units of a call: sum_b ceil(N_b / 128) <= total_rows / 128 + B, known without reading the offsets back
 static int64_t clam_bags_max_units(int B, int64_t total_rows) { return (total_rows + 127) / 128 + B; }
@@ -1285,6 +1293,7 @@ HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags_narrow, hipt_clam_narrow_bags_wor
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_sb_forward_bags_wide, hipt_clam_wide_bags_workspace_bytes, BAGS_WIDE)
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags, hipt_clam_mb_bags_workspace_bytes, BAGS_MB)
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags_wide, hipt_clam_mb_wide_bags_workspace_bytes, BAGS_MB_WIDE)
+HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags_many, hipt_clam_mb_many_bags_workspace_bytes, BAGS_MB_MANY)
 #undef HIPT_CLAM_BAGS_ENTRY
 
 int hipt_clam_mb_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_mb_stream_supported(w) ? 1 : 0; }

@@ -249,6 +249,10 @@ int hipt_clam_bags_mb_combine_launch(const float* partials, const int* tile_star
 // scores and K running records; the partials in the layout of hipt_clam_bags_mb_tiles_launch, for hipt_clam_bags_mb_combine_launch
 int hipt_clam_wide_mb_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
                                    int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
+// the K-branch tile pass for w->n_att = 5..8 at the widths of hipt_clam_bags_mb_tiles_launch (abmil_bags_mb8.hip): the branches in groups of
+// four behind one gate GEMM, each branch in that kernel's order of operations; the same partials, for hipt_clam_bags_mb_combine_launch
+int hipt_clam_bags_mb8_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
+                                    int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
 
 // ---- bootstrapped evaluation metrics (bootstrap.hip) ----
 size_t hipt_bootstrap_lds_bytes(int n);

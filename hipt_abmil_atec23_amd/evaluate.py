@@ -9,6 +9,7 @@ function of the per-slide logits alone and those do not depend on how the split 
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence
 
@@ -126,8 +127,15 @@ def _wide(model, wide_one_call: bool) -> bool:
     return bool(wide_one_call) or bool(getattr(model, "bags_wide", False))
 
 
+def _many(model, many_one_call: bool) -> dict:
+    """The switches of a split's call for ``CLAM_MB`` with 5 to 8 classes: asked for here -- ``bags_one_call`` and ``bags_many`` both
+    set --, or the model's own ``bags_many`` left in force."""
+    return {"bags_one_call": True, "bags_many": True} if many_one_call else {}
+
+
 def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
-                   max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True, wide_one_call: bool = False) -> SplitResult:
+                   max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True, wide_one_call: bool = False,
+                   many_one_call: bool = False) -> SplitResult:
     """Evaluate ``model`` on every bag of a split.  ``bags_or_loader``: a sequence of ``[N_b, S0]`` tensors with ``labels``, or an
     iterable of ``(bag, label)`` pairs (a batch-size-1 loader) with ``labels=None``.  The bags go to the model's device and through
     ``model.forward_bags`` in runs of at most ``max_rows_per_call`` rows (a model without ``forward_bags`` is called bag by bag);
@@ -141,10 +149,16 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     ``hipt_clam_sb_forward_bags_wide``.  ``False`` (the default) leaves the model's own ``bags_wide`` in force -- which is how a caller of
     ``dropin.install(evaluation=True)`` / ``(validation=True)`` opts in: ``model.bags_wide = True``.  A ``CLAM_MB`` at the wide widths
     needs ``bags_one_call`` as well to take ``hipt_clam_mb_forward_bags_wide``; this function sets only ``bags_wide``, so the model's own
-    ``bags_one_call`` (default False: the loop) governs here."""
+    ``bags_one_call`` (default False: the loop) governs here.  ``many_one_call=True`` sets ``bags_one_call`` AND ``bags_many`` for the
+    duration of the call: a ``CLAM_MB`` with 5 to 8 classes at the widths of ``hipt_clam_mb_forward_bags``
+    (``hipt_clam_mb_many_bags_supported``) then goes through ``hipt_clam_mb_forward_bags_many``; its numbers equal the loop's within
+    the fp32 bar in fp32, not bit for bit.  ``False`` (the default) leaves the model's own ``bags_many`` in force."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     fb = getattr(model, "forward_bags", None)
-    with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call), _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)):
+    with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call), \
+            _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)), contextlib.ExitStack() as many:
+        for name, value in _many(model, many_one_call).items():
+            many.enter_context(_attr_for_call(model, name, value))
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             part = [bags[i].to(dev) for i in run]
             if fb is not None:
@@ -174,7 +188,7 @@ class ValidationResult:
 
 def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
                    max_rows_per_call: int = DEFAULT_MAX_ROWS, mb_one_call: bool = True, narrow_one_call: bool = True,
-                   wide_one_call: bool = False) -> ValidationResult:
+                   wide_one_call: bool = False, many_one_call: bool = False) -> ValidationResult:
     """The numbers of ``validate_clam`` for ``model`` on a split, with ``model.forward_bags(..., label=, instance_eval=True)`` called on
     runs of at most ``max_rows_per_call`` rows (``chunk_bags``) instead of ``model(bag, label=, instance_eval=True)`` once per slide.
     Arguments as :func:`evaluate_split`.  A ``CLAM_MB`` model runs with ``bags_one_call = mb_one_call`` for the duration of the call,
@@ -183,6 +197,9 @@ def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     ``wide_one_call`` as in :func:`evaluate_split` (the wide heads; the default keeps the model's own ``bags_wide``).  A ``CLAM_MB`` at
     the wide widths with 2 to 4 classes takes ``hipt_clam_mb_forward_bags_wide`` when both hold: ``mb_one_call`` (set here, default True)
     and ``bags_wide`` (``wide_one_call=True`` or the model's own); its numbers equal the loop's within the fp32 bar in fp32, not bit for bit.
+    ``many_one_call`` as in :func:`evaluate_split`: ``True`` sets ``bags_one_call`` and ``bags_many`` for the call, whatever ``mb_one_call``
+    says, and a ``CLAM_MB`` with 5 to 8 classes at the widths of ``hipt_clam_mb_forward_bags`` takes ``hipt_clam_mb_forward_bags_many``;
+    the default keeps the model's own ``bags_many`` (default False: the loop).
     The AUC stays with the caller (``labels`` and ``prob`` are its inputs).  The model is put in eval mode, as ``validate_clam`` does."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     n = len(bags)
@@ -190,7 +207,9 @@ def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     inst = [{"count": 0, "correct": 0} for _ in range(n_classes)]
     model.eval()
     with torch.no_grad(), _attr_for_call(model, "bags_one_call", mb_one_call), _attr_for_call(model, "bags_narrow", narrow_one_call), \
-            _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)):
+            _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)), contextlib.ExitStack() as many:
+        for name, value in _many(model, many_one_call).items():   # (inside bags_one_call = mb_one_call: many_one_call overrides it, and is undone first)
+            many.enter_context(_attr_for_call(model, name, value))
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             out = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
             _copy_back(run, out, logits, probs, preds)

@@ -157,12 +157,14 @@ _BAGS_FORMS = {
     "wide": ("hipt_clam_sb_forward_bags_wide", "hipt_clam_wide_bags_workspace_bytes", _sb_shapes),
     "mb": ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes", _mb_shapes),
     "mb_wide": ("hipt_clam_mb_forward_bags_wide", "hipt_clam_mb_wide_bags_workspace_bytes", _mb_shapes),
+    "mb_many": ("hipt_clam_mb_forward_bags_many", "hipt_clam_mb_many_bags_workspace_bytes", _mb_shapes),
 }
-BAGS_FORMS_K = ("mb", "mb_wide")  # the forms with K = w.n_att rows of A_raw and K pooled vectors per bag
+BAGS_FORMS_K = ("mb", "mb_wide", "mb_many")  # the forms with K = w.n_att rows of A_raw and K pooled vectors per bag
 
 
 def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None, form: str = "sb"):
-    """The multi-bag CLAM forward in the form ``"sb"``, ``"narrow"``, ``"wide"`` or ``"mb"`` (include/hipt_abmil.h) on ``cat [rows, S0]``, already
+    """The multi-bag CLAM forward in a form of ``_BAGS_FORMS`` (``"sb"``, ``"narrow"``, ``"wide"``, ``"mb"``, ``"mb_wide"``, ``"mb_many"``;
+    include/hipt_abmil.h) on ``cat [rows, S0]``, already
     in the dtype of the weight image ``w`` (an ``_native.ClamWeights``).  Returns ``(A_raw, M, logits, Y_prob, Y_hat)`` -- the last
     four ``None`` with ``attention_only``.  ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions,
     sentinels)."""
@@ -216,6 +218,13 @@ def clam_mb_forward_bags_wide(w, cat: torch.Tensor, offsets: BagOffsets, attenti
     """``hipt_clam_mb_forward_bags_wide``: :func:`clam_mb_forward_bags` for the wide heads (``hipt_clam_mb_wide_bags_supported``:
     ``(S1, S2)`` in {(256, 64), (512, 256), (512, 384)}, fp32 and bf16, 2 to 4 branches).  Arguments and results as there."""
     return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb_wide")
+
+
+def clam_mb_forward_bags_many(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+    """``hipt_clam_mb_forward_bags_many``: :func:`clam_mb_forward_bags` for 5 to 8 branches (``hipt_clam_mb_many_bags_supported``: the
+    widths of :func:`clam_sb_forward_bags`, fp32 and bf16).  Arguments and results as there; branch ``k`` has the bits that
+    :func:`clam_mb_forward_bags` gives it on weights made of a subset of the branches."""
+    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb_many")
 
 
 def topk_segments(A: torch.Tensor, offsets: BagOffsets, k: int, want_global: bool = True):

@@ -546,6 +546,8 @@ class CLAM_SB(WeightImageCache, nn.Module):
             w = self._pack_stacked(device) if self.bags_one_call else None
             if w is not None and lib.hipt_clam_mb_bags_supported(C_.byref(w)):
                 return w, "mb"
+            if w is not None and self.bags_many and lib.hipt_clam_mb_many_bags_supported(C_.byref(w)):   # the same widths, K = 5..8: where asked for
+                return w, "mb_many"
             wide = w is not None and self.bags_wide and lib.hipt_clam_mb_wide_bags_supported(C_.byref(w))   # tiny, small, big, small_resnet18, K = 2..4: where asked for
             return (w, "mb_wide") if wide else None
         w = self._pack(device)
@@ -573,8 +575,10 @@ class CLAM_SB(WeightImageCache, nn.Module):
         ``small``, ``big``, ``small_resnet18``: ``hipt_clam_wide_bags_supported``) likewise have ``hipt_clam_sb_forward_bags_wide``, taken
         by a ``CLAM_SB`` with ``bags_wide`` set (default False: the loop, with the bits of ``forward``).  A ``CLAM_MB`` at those widths
         (``CLAM_MB()`` is built with ``small``) with 2 to 4 classes takes ``hipt_clam_mb_forward_bags_wide`` when BOTH ``bags_one_call``
-        and ``bags_wide`` are set (``hipt_clam_mb_wide_bags_supported``); with either off it keeps the loop and its bits.  The results
-        have the K-branch structure above.
+        and ``bags_wide`` are set (``hipt_clam_mb_wide_bags_supported``); with either off it keeps the loop and its bits.  A ``CLAM_MB``
+        with 5 to 8 classes at the widths of ``hipt_clam_mb_forward_bags`` takes ``hipt_clam_mb_forward_bags_many`` when BOTH
+        ``bags_one_call`` and ``bags_many`` are set (``hipt_clam_mb_many_bags_supported``); with either off it keeps the loop and its
+        bits.  The results have the K-branch structure above.
 
         ``instance_eval=True`` with ``label`` (B class ids: a list, a numpy array or a tensor) adds what ``forward(h, label=,
         instance_eval=True)`` returns per bag (validate_clam, utils/core_utils.py:506-560): ``instance_loss`` (a ``[B]`` tensor),
@@ -736,6 +740,7 @@ class CLAM_MB(CLAM_SB):
     _multi = True
     one_pass = True  # inference takes the "mb" form of functional.clam_forward (one pass over the bag for all branches) where the library has it; False: branch by branch
     bags_one_call = False  # forward_bags takes hipt_clam_mb_forward_bags (all bags, all branches in one call) where the library has it; False: the loop over forward
+    bags_many = False      # together with bags_one_call: forward_bags takes hipt_clam_mb_forward_bags_many for 5 to 8 classes at the widths of hipt_clam_mb_forward_bags; False: the loop over forward
 
     def __init__(self, gate=True, size_arg="small", dropout=0.0, k_sample=8, n_classes=2,
                  instance_loss_fn=nn.CrossEntropyLoss(), subtyping=False):

@@ -457,6 +457,18 @@ int hipt_clam_mb_forward_bags_wide(const hipt_clam_weights* w, const void* bags,
                                    int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
                                    void* workspace, size_t ws_bytes, void* stream);
 
+/* The same K-branch call for MANY branches: 5 <= K <= 8 (the reference's ovarian_5class and wider tasks) at the widths of
+ * hipt_clam_mb_forward_bags.  Supported: hipt_clam_bags_supported(w) and 5 <= n_att <= 8 and n_att == n_classes.  Inputs, outputs and the K
+ * partials per work unit as hipt_clam_mb_forward_bags; the same unit table and per-bag combine; the tile pass is a kernel of its own that
+ * walks the branches in groups of four behind one gate GEMM.  Every branch is computed operation for operation as that form computes a
+ * branch: branch k of a call has the bits of the same branch in a hipt_clam_mb_forward_bags call on weights made of a subset of the
+ * branches (logits[b, k] and M[b, k] included; Y_prob and Y_hat depend on all K logits). */
+int hipt_clam_mb_many_bags_supported(const hipt_clam_weights* w);
+size_t hipt_clam_mb_many_bags_workspace_bytes(const hipt_clam_weights* w, int B, int64_t total_rows);
+int hipt_clam_mb_forward_bags_many(const hipt_clam_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                                   int attention_only, float* A_raw, float* M, float* logits, float* Y_prob, int64_t* Y_hat,
+                                   void* workspace, size_t ws_bytes, void* stream);
+
 /* CLAM_MB.forward (model_clam.py:226-264), inference, with ONE pass over the bag for all K = w->n_att attention branches (2 <= K <= 4; W1 and
  * [Wa; Wb] are shared by the branches, only wc / bc / the classifier rows differ):  A_raw[K, N] = the K logits of every row;
  * M[K, S1] = softmax_N(A_raw[k]) h1;  logits[K]: logits[k] = wcls[k] . M[k] + bcls[k] (:248-250; Y_prob / Y_hat are K numbers: the caller's).
