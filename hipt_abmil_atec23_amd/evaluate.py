@@ -65,27 +65,35 @@ def _split(bags_or_loader, labels):
     return [b.reshape(-1, b.shape[-1]) for b in bags], labels
 
 
-class _attr_for_call:
-    """``model.<name> = value`` for the length of a ``with`` block where the model's CLASS has that switch; afterwards the instance
-    is as it was (its own value, or none: back to the class attribute), also after an exception."""
-
-    def __init__(self, model, name: str, value: bool):
-        self.model, self.name, self.value = model, name, bool(value)
-        self.had = hasattr(type(model), name)
-
-    def __enter__(self):
-        if self.had:
-            self.before = self.model.__dict__.get(self.name, None)
-            setattr(self.model, self.name, self.value)
-        return self
-
-    def __exit__(self, *exc):
-        if self.had:
-            if self.before is None:
-                delattr(self.model, self.name)
+@contextlib.contextmanager
+def _switches(model, values: dict):
+    """``model.<name> = value`` for every pair of ``values`` whose switch the model's CLASS has, for the length of a ``with`` block;
+    afterwards the instance is exactly as it was (its own value put back, or none: the attribute deleted, back to the class's), also
+    after an exception."""
+    values = {k: bool(v) for k, v in values.items() if hasattr(type(model), k)}
+    absent = object()
+    before = {k: model.__dict__.get(k, absent) for k in values}
+    for k, v in values.items():
+        setattr(model, k, v)
+    try:
+        yield
+    finally:
+        for k, v in before.items():
+            if v is absent:
+                delattr(model, k)
             else:
-                setattr(self.model, self.name, self.before)
-        return False
+                setattr(model, k, v)
+
+
+def _split_switches(narrow_one_call, wide_one_call, many_one_call) -> dict:
+    """The model switches both split functions set: ``bags_narrow`` as asked; ``bags_wide`` and ``bags_many`` only where asked for --
+    otherwise the model's own value stays in force --, ``many_one_call`` together with ``bags_one_call``."""
+    s = {"bags_narrow": narrow_one_call}
+    if wide_one_call:
+        s["bags_wide"] = True
+    if many_one_call:
+        s.update(bags_one_call=True, bags_many=True)
+    return s
 
 
 def _prepare(model, bags_or_loader, labels, n_classes, loss_fn):
@@ -122,17 +130,6 @@ def _tally(preds, labels, n_classes):
     return acc, sum(d["count"] - d["correct"] for d in acc) / len(labels)
 
 
-def _wide(model, wide_one_call: bool) -> bool:
-    """``bags_wide`` of a split's call: asked for here, or already set on the model."""
-    return bool(wide_one_call) or bool(getattr(model, "bags_wide", False))
-
-
-def _many(model, many_one_call: bool) -> dict:
-    """The switches of a split's call for ``CLAM_MB`` with 5 to 8 classes: asked for here -- ``bags_one_call`` and ``bags_many`` both
-    set --, or the model's own ``bags_many`` left in force."""
-    return {"bags_one_call": True, "bags_many": True} if many_one_call else {}
-
-
 def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_fn: Optional[Callable] = None,
                    max_rows_per_call: int = DEFAULT_MAX_ROWS, narrow_one_call: bool = True, wide_one_call: bool = False,
                    many_one_call: bool = False) -> SplitResult:
@@ -155,10 +152,7 @@ def evaluate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     the fp32 bar in fp32, not bit for bit.  ``False`` (the default) leaves the model's own ``bags_many`` in force."""
     bags, labels, loss_fn, dev, (logits, probs, preds) = _prepare(model, bags_or_loader, labels, n_classes, loss_fn)
     fb = getattr(model, "forward_bags", None)
-    with torch.no_grad(), _attr_for_call(model, "bags_narrow", narrow_one_call), \
-            _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)), contextlib.ExitStack() as many:
-        for name, value in _many(model, many_one_call).items():
-            many.enter_context(_attr_for_call(model, name, value))
+    with torch.no_grad(), _switches(model, _split_switches(narrow_one_call, wide_one_call, many_one_call)):
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             part = [bags[i].to(dev) for i in run]
             if fb is not None:
@@ -206,10 +200,8 @@ def validate_split(model, bags_or_loader, labels=None, n_classes: int = 2, loss_
     inst_loss = torch.empty((n,), dtype=torch.float32)
     inst = [{"count": 0, "correct": 0} for _ in range(n_classes)]
     model.eval()
-    with torch.no_grad(), _attr_for_call(model, "bags_one_call", mb_one_call), _attr_for_call(model, "bags_narrow", narrow_one_call), \
-            _attr_for_call(model, "bags_wide", _wide(model, wide_one_call)), contextlib.ExitStack() as many:
-        for name, value in _many(model, many_one_call).items():   # (inside bags_one_call = mb_one_call: many_one_call overrides it, and is undone first)
-            many.enter_context(_attr_for_call(model, name, value))
+    # (bags_one_call = mb_one_call first: many_one_call overrides it)
+    with torch.no_grad(), _switches(model, {"bags_one_call": mb_one_call, **_split_switches(narrow_one_call, wide_one_call, many_one_call)}):
         for run in chunk_bags([b.shape[0] for b in bags], max_rows_per_call):
             out = model.forward_bags([bags[i].to(dev) for i in run], label=[labels[i] for i in run], instance_eval=True)
             _copy_back(run, out, logits, probs, preds)

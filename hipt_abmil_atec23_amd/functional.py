@@ -7,6 +7,7 @@ forwards go through the coarse entry points (one C call per ViT / region / bag).
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -148,27 +149,43 @@ class BagOffsets:
         return len(self.host) - 1
 
 
-# form -> (native call, its workspace size, shapes of (A_raw, M, logits / Y_prob) for B bags of `rows` rows in all); Y_hat is [B]
-_sb_shapes = lambda w, B, rows: ((rows,), (B, w.s1), (B, w.n_classes))
-_mb_shapes = lambda w, B, rows: ((w.n_att, rows), (B, w.n_att, w.s1), (B, w.n_att))
-_BAGS_FORMS = {
-    "sb": ("hipt_clam_sb_forward_bags", "hipt_clam_bags_workspace_bytes", _sb_shapes),
-    "narrow": ("hipt_clam_sb_forward_bags_narrow", "hipt_clam_narrow_bags_workspace_bytes", _sb_shapes),
-    "wide": ("hipt_clam_sb_forward_bags_wide", "hipt_clam_wide_bags_workspace_bytes", _sb_shapes),
-    "mb": ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes", _mb_shapes),
-    "mb_wide": ("hipt_clam_mb_forward_bags_wide", "hipt_clam_mb_wide_bags_workspace_bytes", _mb_shapes),
-    "mb_many": ("hipt_clam_mb_forward_bags_many", "hipt_clam_mb_many_bags_workspace_bytes", _mb_shapes),
-}
-BAGS_FORMS_K = ("mb", "mb_wide", "mb_many")  # the forms with K = w.n_att rows of A_raw and K pooled vectors per bag
+# One row per form of the multi-bag call, in routing priority (``CLAM_SB._bags_form`` walks the rows of the model's kind in this order and
+# takes the first whose switches are all set on the model and whose predicate answers 1): the C entry point, its workspace size, its
+# ``*_supported`` predicate, whether the outputs have the K-branch shapes, the model kind, the model switches the form needs, and the
+# heads it serves (documentation: the predicate decides).
+BagsForm = namedtuple("BagsForm", "name entry ws_bytes supported multi kind switches heads")
+_BAGS_FORMS = {f.name: f for f in (
+    BagsForm("sb", "hipt_clam_sb_forward_bags", "hipt_clam_bags_workspace_bytes", "hipt_clam_bags_supported", False, "CLAM_SB", (),
+             "S1 in {128, 64}, in fp32 also 32, with S2 in {64, 32, 16}"),
+    BagsForm("narrow", "hipt_clam_sb_forward_bags_narrow", "hipt_clam_narrow_bags_workspace_bytes", "hipt_clam_narrow_bags_supported", False, "CLAM_SB",
+             ("bags_narrow",), "the narrow heads, (S1, S2) in {(8, 4), (16, 8), (32, 8), (32, 16)}"),
+    BagsForm("wide", "hipt_clam_sb_forward_bags_wide", "hipt_clam_wide_bags_workspace_bytes", "hipt_clam_wide_bags_supported", False, "CLAM_SB",
+             ("bags_wide",), "the wide heads, (S1, S2) in {(256, 64), (512, 256), (512, 384)}"),
+    BagsForm("mb", "hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes", "hipt_clam_mb_bags_supported", True, "CLAM_MB",
+             ("bags_one_call",), "2 to 4 branches at the widths of ``hipt_clam_sb_forward_bags``"),
+    BagsForm("mb_many", "hipt_clam_mb_forward_bags_many", "hipt_clam_mb_many_bags_workspace_bytes", "hipt_clam_mb_many_bags_supported", True, "CLAM_MB",
+             ("bags_one_call", "bags_many"), "5 to 8 branches at the widths of ``hipt_clam_sb_forward_bags``; branch ``k`` has the bits that "
+             "``hipt_clam_mb_forward_bags`` gives it on weights made of a subset of the branches"),
+    BagsForm("mb_wide", "hipt_clam_mb_forward_bags_wide", "hipt_clam_mb_wide_bags_workspace_bytes", "hipt_clam_mb_wide_bags_supported", True, "CLAM_MB",
+             ("bags_one_call", "bags_wide"), "2 to 4 branches at the widths of ``hipt_clam_sb_forward_bags_wide``"),
+)}
+BAGS_FORMS_OF = {kind: tuple(f for f in _BAGS_FORMS.values() if f.kind == kind) for kind in ("CLAM_SB", "CLAM_MB")}  # a kind's rows, in routing order
+BAGS_FORMS_K = tuple(f.name for f in _BAGS_FORMS.values() if f.multi)  # the forms with K = w.n_att rows of A_raw and K pooled vectors per bag
+
+
+def bags_shapes(form: str, w, B: int, rows: int) -> tuple:
+    """Shapes of ``(A_raw, M, logits / Y_prob)`` of a multi-bag call in ``form`` for B bags of ``rows`` rows in all; ``Y_hat`` is ``[B]``."""
+    if _BAGS_FORMS[form].multi:
+        return (w.n_att, rows), (B, w.n_att, w.s1), (B, w.n_att)
+    return (rows,), (B, w.s1), (B, w.n_classes)
 
 
 def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None, form: str = "sb"):
-    """The multi-bag CLAM forward in a form of ``_BAGS_FORMS`` (``"sb"``, ``"narrow"``, ``"wide"``, ``"mb"``, ``"mb_wide"``, ``"mb_many"``;
-    include/hipt_abmil.h) on ``cat [rows, S0]``, already
+    """The multi-bag CLAM forward in a form of ``_BAGS_FORMS`` (include/hipt_abmil.h) on ``cat [rows, S0]``, already
     in the dtype of the weight image ``w`` (an ``_native.ClamWeights``).  Returns ``(A_raw, M, logits, Y_prob, Y_hat)`` -- the last
     four ``None`` with ``attention_only``.  ``out`` / ``ws``: buffers to write into instead of fresh ones (tests: guard regions,
     sentinels)."""
-    sym, ws_sym, shapes = _BAGS_FORMS[form]
+    sym, ws_sym = _BAGS_FORMS[form].entry, _BAGS_FORMS[form].ws_bytes
     what = sym[len("hipt_"):]
     N.require_cuda(cat, what)
     dev, B, rows = cat.device, len(offsets), cat.shape[0]
@@ -182,7 +199,7 @@ def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only:
         ws = workspace(dev, getattr(N.lib(), ws_sym)(C.byref(w), B, rows), ("clam_bags", st.value))
     if out is None:
         e = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        a, m, l = shapes(w, B, rows)
+        a, m, l = bags_shapes(form, w, B, rows)
         out = (e(a), None, None, None, None) if attention_only else (e(a), e(m), e(l), e(l), e((B,), torch.int64))
     A_raw, M, logits, Y_prob, Y_hat = out
     N.call(sym, C.byref(w), N.ptr(cat), N.ptr(offsets.dev), B, rows, 1 if attention_only else 0, N.ptr(A_raw), N.ptr(M), N.ptr(logits),
@@ -190,41 +207,27 @@ def clam_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only:
     return out
 
 
-def clam_sb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_sb_forward_bags``: returns ``(A_raw [rows], M [B, S1], logits [B, C], Y_prob [B, C], Y_hat [B])``."""
-    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "sb")
+def _bags_wrapper(form: str):
+    """``clam_forward_bags`` in one form, under the name of its entry point and with the form's heads and result shapes as its docstring"""
+    f = _BAGS_FORMS[form]
+
+    def call(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
+        return clam_forward_bags(w, cat, offsets, attention_only, out, ws, form)
+
+    shapes = ("``(A_raw [K, rows], M [B, K, S1], logits [B, K], Y_prob [B, K], Y_hat [B])`` for the ``K = w.n_att`` branches of a stacked ``CLAM_MB`` "
+              "weight image; bag ``b`` is the columns ``[offsets[b], offsets[b+1])`` of ``A_raw``" if f.multi else
+              "``(A_raw [rows], M [B, S1], logits [B, C], Y_prob [B, C], Y_hat [B])``")
+    call.__name__ = call.__qualname__ = f.entry[len("hipt_"):]
+    call.__doc__ = f"``{f.entry}`` for {f.heads} (``{f.supported}``; fp32 and bf16).  Returns {shapes}."
+    return call
 
 
-def clam_sb_forward_bags_narrow(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_sb_forward_bags_narrow``: :func:`clam_sb_forward_bags` for the narrow heads (``hipt_clam_narrow_bags_supported``:
-    ``(S1, S2)`` in {(8, 4), (16, 8), (32, 8), (32, 16)}, fp32 and bf16).  Arguments and results as there."""
-    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "narrow")
-
-
-def clam_sb_forward_bags_wide(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_sb_forward_bags_wide``: :func:`clam_sb_forward_bags` for the wide heads (``hipt_clam_wide_bags_supported``:
-    ``(S1, S2)`` in {(256, 64), (512, 256), (512, 384)}, fp32 and bf16).  Arguments and results as there."""
-    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "wide")
-
-
-def clam_mb_forward_bags(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_mb_forward_bags``: :func:`clam_sb_forward_bags` for the ``K = w.n_att`` branches of a stacked ``CLAM_MB`` weight image.
-    Returns ``(A_raw [K, rows], M [B, K, S1], logits [B, K], Y_prob [B, K], Y_hat [B])``; bag ``b`` is the columns
-    ``[offsets[b], offsets[b+1])`` of ``A_raw``."""
-    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb")
-
-
-def clam_mb_forward_bags_wide(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_mb_forward_bags_wide``: :func:`clam_mb_forward_bags` for the wide heads (``hipt_clam_mb_wide_bags_supported``:
-    ``(S1, S2)`` in {(256, 64), (512, 256), (512, 384)}, fp32 and bf16, 2 to 4 branches).  Arguments and results as there."""
-    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb_wide")
-
-
-def clam_mb_forward_bags_many(w, cat: torch.Tensor, offsets: BagOffsets, attention_only: bool = False, out=None, ws=None):
-    """``hipt_clam_mb_forward_bags_many``: :func:`clam_mb_forward_bags` for 5 to 8 branches (``hipt_clam_mb_many_bags_supported``: the
-    widths of :func:`clam_sb_forward_bags`, fp32 and bf16).  Arguments and results as there; branch ``k`` has the bits that
-    :func:`clam_mb_forward_bags` gives it on weights made of a subset of the branches."""
-    return clam_forward_bags(w, cat, offsets, attention_only, out, ws, "mb_many")
+clam_sb_forward_bags = _bags_wrapper("sb")
+clam_sb_forward_bags_narrow = _bags_wrapper("narrow")
+clam_sb_forward_bags_wide = _bags_wrapper("wide")
+clam_mb_forward_bags = _bags_wrapper("mb")
+clam_mb_forward_bags_many = _bags_wrapper("mb_many")
+clam_mb_forward_bags_wide = _bags_wrapper("mb_wide")
 
 
 def topk_segments(A: torch.Tensor, offsets: BagOffsets, k: int, want_global: bool = True):

@@ -538,25 +538,18 @@ class CLAM_SB(WeightImageCache, nn.Module):
 
     def _bags_form(self, device):
         """``(weight image, form)`` of the one ``functional.clam_forward_bags`` call that serves ``forward_bags`` on ``device``, or
-        None: the loop over ``forward``."""
+        None: the loop over ``forward``.  The rows of ``functional._BAGS_FORMS`` of this model's kind, in order: the first whose switches
+        are all set and whose predicate holds.  The weight image is packed when the first row gets as far as its predicate."""
         if not self._gate or device.type != "cuda":
             return None
-        lib = N.lib()
-        if self._multi:
-            w = self._pack_stacked(device) if self.bags_one_call else None
-            if w is not None and lib.hipt_clam_mb_bags_supported(C_.byref(w)):
-                return w, "mb"
-            if w is not None and self.bags_many and lib.hipt_clam_mb_many_bags_supported(C_.byref(w)):   # the same widths, K = 5..8: where asked for
-                return w, "mb_many"
-            wide = w is not None and self.bags_wide and lib.hipt_clam_mb_wide_bags_supported(C_.byref(w))   # tiny, small, big, small_resnet18, K = 2..4: where asked for
-            return (w, "mb_wide") if wide else None
-        w = self._pack(device)
-        if lib.hipt_clam_bags_supported(C_.byref(w)):
-            return w, "sb"   # (a width both kernels have keeps the wide one)
-        if self.bags_narrow and lib.hipt_clam_narrow_bags_supported(C_.byref(w)):   # hipt_smaller, hipt_smallest, ...: where asked for
-            return w, "narrow"
-        wide = self.bags_wide and lib.hipt_clam_wide_bags_supported(C_.byref(w))         # tiny, small, big, small_resnet18: where asked for
-        return (w, "wide") if wide else None
+        w = None
+        for f in Fn.BAGS_FORMS_OF["CLAM_MB" if self._multi else "CLAM_SB"]:
+            if all(getattr(self, s) for s in f.switches):
+                if w is None:
+                    w, lib = self._pack_stacked(device) if self._multi else self._pack(device), N.lib()
+                if getattr(lib, f.supported)(C_.byref(w)):
+                    return w, f.name
+        return None
 
     def forward_bags(self, bags, attention_only=False, return_features=False, label=None, instance_eval=False):
         """``forward`` over B bags at once, inference only (no autograd; dropout inactive as in ``eval()``).
@@ -564,21 +557,21 @@ class CLAM_SB(WeightImageCache, nn.Module):
         ``bags``: a sequence of ``[N_b, S0]`` tensors, or ``(cat [sum N_b, S0], offsets)`` with the B+1 row offsets as a list, a
         tensor or a ``functional.BagOffsets``.  Returns ``logits [B, C]``, ``Y_prob [B, C]``, ``Y_hat [B, 1]``, ``A_raw`` as a
         list of ``[1, N_b]`` views of one buffer and ``{'features': M [B, S1]}`` when asked (``attention_only``: the list alone).
-        Where the library has the multi-bag form (``hipt_clam_bags_supported``; for ``CLAM_MB`` with ``bags_one_call`` set,
-        ``hipt_clam_mb_bags_supported``: ``A_raw`` is then a list of ``[K, N_b]`` views and the features are ``[B, K, S1]``) this is
-        ONE native call whose per-bag results do not depend on the other bags; elsewhere -- other widths, ``CLAM_MB`` without
-        ``bags_one_call``, the ungated head, CPU tensors -- it loops over ``forward`` and returns the same structure.
-        ``bags_route`` tells which.  The narrow heads (``hipt_smaller`` [192, 16, 8], ``hipt_smallest`` [192, 8, 4], (32, 8), bf16
-        (32, 16): ``hipt_clam_narrow_bags_supported``) have a one-call kernel of their own, ``hipt_clam_sb_forward_bags_narrow``, taken
-        by a ``CLAM_SB`` with ``bags_narrow`` set (default False: the loop, with the bits of ``forward``); its numbers equal the
-        loop's within the fp32 bar (1e-4), not bit for bit.  A width both kernels have keeps the first.  The wide heads (``tiny``,
-        ``small``, ``big``, ``small_resnet18``: ``hipt_clam_wide_bags_supported``) likewise have ``hipt_clam_sb_forward_bags_wide``, taken
-        by a ``CLAM_SB`` with ``bags_wide`` set (default False: the loop, with the bits of ``forward``).  A ``CLAM_MB`` at those widths
-        (``CLAM_MB()`` is built with ``small``) with 2 to 4 classes takes ``hipt_clam_mb_forward_bags_wide`` when BOTH ``bags_one_call``
-        and ``bags_wide`` are set (``hipt_clam_mb_wide_bags_supported``); with either off it keeps the loop and its bits.  A ``CLAM_MB``
-        with 5 to 8 classes at the widths of ``hipt_clam_mb_forward_bags`` takes ``hipt_clam_mb_forward_bags_many`` when BOTH
-        ``bags_one_call`` and ``bags_many`` are set (``hipt_clam_mb_many_bags_supported``); with either off it keeps the loop and its
-        bits.  The results have the K-branch structure above.
+        The rule: the first form of this model's kind in ``functional._BAGS_FORMS`` whose switches are all set on the model and whose
+        ``*_supported`` predicate holds is taken, as ONE native call whose per-bag results do not depend on the other bags; otherwise
+        -- also for the ungated head and CPU tensors -- it loops over ``forward`` and returns the same structure.  ``bags_route`` tells which.
+
+            kind     form     switches (default False)      heads
+            CLAM_SB  sb       -                             S1 in {128, 64}, fp32 also 32; S2 in {64, 32, 16}
+            CLAM_SB  narrow   bags_narrow                   hipt_smaller [192, 16, 8], hipt_smallest [192, 8, 4], (32, 8), (32, 16)
+            CLAM_SB  wide     bags_wide                     tiny, small, big, small_resnet18
+            CLAM_MB  mb       bags_one_call                 the widths of sb, 2 to 4 classes
+            CLAM_MB  mb_many  bags_one_call, bags_many      the widths of sb, 5 to 8 classes
+            CLAM_MB  mb_wide  bags_one_call, bags_wide      the widths of wide, 2 to 4 classes (``CLAM_MB()`` is built with ``small``)
+
+        A width both kernels have keeps the first.  With a switch of its form off a model keeps the loop, with the bits of ``forward``;
+        the numbers of a one-call form equal the loop's within the fp32 bar (1e-4), not bit for bit.  The ``CLAM_MB`` forms return
+        ``A_raw`` as a list of ``[K, N_b]`` views and features ``[B, K, S1]``.
 
         ``instance_eval=True`` with ``label`` (B class ids: a list, a numpy array or a tensor) adds what ``forward(h, label=,
         instance_eval=True)`` returns per bag (validate_clam, utils/core_utils.py:506-560): ``instance_loss`` (a ``[B]`` tensor),

@@ -1,25 +1,21 @@
-"""Host tests (no GPU) of the multi-bag CLAM_SB call: the three entry points exist in the library, the header and the binding; the
-workspace size follows B and the row count; every argument error comes back before anything is dereferenced or launched (all
-pointers here are fake addresses); the Python layer checks the offsets before any native call; and ``evaluate_split`` repeats the
-arithmetic of the reference's ``summary()`` (utils/eval_utils.py:115-179) whatever the chunking."""
+"""Host tests (no GPU) of the multi-bag CLAM_SB call: the envelope of ``hipt_clam_bags_supported``; the Python layer checks the offsets
+before any native call; and ``evaluate_split`` repeats the arithmetic of the reference's ``summary()`` (utils/eval_utils.py:115-179)
+whatever the chunking.  What the form shares with the other five (symbols, argument errors, workspace sizes) is stated in
+tests/clam_bags_util.py and run here on this form's cases."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ROOT
+from clam_bags_util import ARGUMENT_CASES, W, check_argument_error, check_attention_only_needs_no_pooled_outputs, check_outside, check_workspace_grows
 from hipt_abmil_atec23_amd import CLAM_SB, _native as N
 from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd.evaluate import chunk_bags, evaluate_split
 
 FAKE = 1 << 20            # a non-null, 4 KiB-aligned address that no call dereferences before its checks
-E_BADARG, E_UNSUPPORTED = -1, -4
-NAMES = ("hipt_clam_bags_supported", "hipt_clam_bags_workspace_bytes", "hipt_clam_sb_forward_bags")
 
 
 def weights(dtype=N.HIPT_F32, s0=384, s1=128, s2=64, n_classes=2):
@@ -27,25 +23,6 @@ def weights(dtype=N.HIPT_F32, s0=384, s1=128, s2=64, n_classes=2):
     for name in ("w1", "b1", "wab", "bab", "wc", "bc", "wcls", "bcls"):
         setattr(w, name, FAKE)
     return w
-
-
-def forward(lib, w, bags=FAKE, offsets=FAKE, B=7, rows=1000, attention_only=0, A_raw=FAKE, M=FAKE, logits=FAKE, Y_prob=FAKE, Y_hat=FAKE,
-            ws=FAKE, nbytes=None):
-    if nbytes is None:
-        nbytes = lib.hipt_clam_bags_workspace_bytes(C.byref(w), B, rows)
-    return lib.hipt_clam_sb_forward_bags(C.byref(w) if w is not None else None, bags, offsets, B, rows, attention_only, A_raw, M, logits, Y_prob,
-                                         Y_hat, ws, nbytes, None)
-
-
-def test_symbols_are_exported_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "hipt_abmil.h")).read()
-    declared = set(re.findall(r"\b(hipt_[a-z0-9_]+)\s*\(", hdr))
-    lib = N.lib()
-    for name in NAMES:
-        assert name in declared and name in N.SIGNATURES and hasattr(lib, name), name
-    # the three are new symbols beside the old ones (nothing existing changed its signature), so the version stays where other
-    # tests of this suite pin it; header, library and binding agree on it
-    assert lib.hipt_abi_version() == N.ABI_VERSION and re.search(rf"#define HIPT_ABI_VERSION {N.ABI_VERSION}\b", hdr)
 
 
 def test_supported_is_the_fused_envelope():
@@ -57,48 +34,22 @@ def test_supported_is_the_fused_envelope():
     assert lib.hipt_clam_bags_supported(None) == 0
 
 
+# ---- the checks every form shares (tests/clam_bags_util.py), on this form's cases ----
 def test_workspace_grows_with_bags_and_rows():
-    lib = N.lib()
-    w = weights()
-    size = lambda B, rows: lib.hipt_clam_bags_workspace_bytes(C.byref(w), B, rows)
-    base = size(7, 1000)
-    assert base > 0 and base % 256 == 0
-    assert size(64, 1000) > base and size(7, 100_000) > base and size(1, 1) > 0
-    for B, rows in ((1, 1), (1, 129), (64, 14_400), (3, 100_000)):
-        assert size(B, rows) % 256 == 0
-        units = (rows + 127) // 128 + B      # upper bound of sum ceil(N_b / 128): what the host can know without reading the offsets
-        assert size(B, rows) >= units * (16 + 4 * (2 + 128)) + 4 * (B + 1)
-    assert size(0, 10) == 0 and size(5, 4) == 0 and size(-1, 10) == 0
-    assert lib.hipt_clam_bags_workspace_bytes(C.byref(weights(s1=512, s2=256, s0=1024)), 7, 1000) == 0
-    assert lib.hipt_clam_bags_workspace_bytes(None, 7, 1000) == 0
+    check_workspace_grows("sb", W(384, 128, 64))
 
 
-@pytest.mark.parametrize("case,kw", [
-    ("null weights", dict(w=None, nbytes=1 << 20)), ("null bags", dict(bags=None)), ("null offsets", dict(offsets=None)),
-    ("null A_raw", dict(A_raw=None)), ("null M", dict(M=None)), ("null logits", dict(logits=None)), ("null Y_prob", dict(Y_prob=None)),
-    ("null Y_hat", dict(Y_hat=None)), ("null workspace", dict(ws=None)), ("misaligned bags", dict(bags=FAKE + 8)),
-    ("no bag", dict(B=0, nbytes=1 << 20)), ("negative B", dict(B=-3, nbytes=1 << 20)), ("fewer rows than bags", dict(B=7, rows=6, nbytes=1 << 20)),
-    ("short workspace", dict(nbytes="short")), ("misaligned workspace", dict(ws=FAKE + 16)),
-])
+@pytest.mark.parametrize("case,kw", ARGUMENT_CASES)
 def test_argument_errors_come_back_before_any_device_work(case, kw):
-    lib = N.lib()
-    kw = dict(kw)
-    w = kw.pop("w", weights())
-    if kw.get("nbytes") == "short":
-        kw["nbytes"] = lib.hipt_clam_bags_workspace_bytes(C.byref(w), 7, 1000) - 1
-    assert forward(lib, w, **kw) == E_BADARG, case
-    assert lib.hipt_last_error().decode() != ""
+    check_argument_error("sb", case, kw)
 
 
 def test_attention_only_needs_no_pooled_outputs_and_other_widths_are_unsupported():
-    lib = N.lib()
-    # attention_only: M .. Y_hat may be NULL -- the call gets past its checks (a short workspace is then what stops it)
-    assert forward(lib, weights(), attention_only=1, M=None, logits=None, Y_prob=None, Y_hat=None, nbytes=256) == E_BADARG
-    assert "workspace" in lib.hipt_last_error().decode()
-    assert forward(lib, weights(s0=1024, s1=512, s2=256), nbytes=1 << 24) == E_UNSUPPORTED
-    assert forward(lib, weights(dtype=N.HIPT_BF16, s0=192, s1=32, s2=16), nbytes=1 << 24) == E_UNSUPPORTED
+    check_attention_only_needs_no_pooled_outputs("sb")
+    check_outside("sb", [W(1024, 512, 256), W(192, 32, 16, dtype=N.HIPT_BF16)])
 
 
+# ---- the Python layer ----
 @pytest.mark.parametrize("offsets,rows,what", [([0, 5, 3, 9], 9, "decrease"), ([0, 3, 3, 9], 9, "empty"), ([0, 3, 8, 10], 9, "end at 10"),
                                                ([1, 3, 9], 9, "starting at 0"), ([0], 0, "B\\+1")])
 def test_python_checks_the_offsets_before_any_native_call(offsets, rows, what):

@@ -1,22 +1,15 @@
-"""Host tests (no GPU) of the multi-bag CLAM_MB call for the wide heads (csrc/abmil_wide_mb.hip): the three entry points exist in the
-library, the header, the export map and the binding; ``hipt_clam_mb_wide_bags_supported`` answers yes for exactly (S1, S2) in
-{(256, 64), (512, 256), (512, 384)} x {fp32, bf16} x K in {2, 3, 4} with K classes and S0 a multiple of the K-slab; the workspace is the
-sum of the three carves; a refusal names the widths and the K range; ``CLAM_MB`` takes the form only on the device and only with both
-switches set; and the forms that existed before answer as they did.  All pointers here are fake addresses."""
+"""Host tests (no GPU) of the multi-bag CLAM_MB call for the wide heads (csrc/abmil_wide_mb.hip): ``hipt_clam_mb_wide_bags_supported``
+answers yes for exactly (S1, S2) in {(256, 64), (512, 256), (512, 384)} x {fp32, bf16} x K in {2, 3, 4} with K classes and S0 a multiple
+of the K-slab; the workspace is the sum of the three carves; a refusal names the widths and the K range; and the forms that existed
+before answer as they did.  All pointers here are fake addresses.  What the form shares with the other five (symbols, argument errors,
+the switches, the routing) is in tests/test_clam_bags_forms_host.py."""
 import ctypes as C
-import os
-import re
-
 import pytest
-import torch
 
-from conftest import ROOT
-from hipt_abmil_atec23_amd import CLAM_MB, _native as N
-from hipt_abmil_atec23_amd import functional as Fn
+from hipt_abmil_atec23_amd import _native as N
 
 FAKE = 1 << 20            # a non-null, 4 KiB-aligned address that no call dereferences before its checks
 E_BADARG, E_UNSUPPORTED = -1, -4
-NAMES = ("hipt_clam_mb_wide_bags_supported", "hipt_clam_mb_wide_bags_workspace_bytes", "hipt_clam_mb_forward_bags_wide")
 PREFIX = "clam_mb_forward_bags_wide: "
 F32, BF16 = N.HIPT_F32, N.HIPT_BF16
 PAIRS = ((256, 64), (512, 256), (512, 384))
@@ -33,21 +26,6 @@ def forward(lib, w, B=7, rows=1000, nbytes=None, attention_only=0):
     if nbytes is None:
         nbytes = lib.hipt_clam_mb_wide_bags_workspace_bytes(C.byref(w), B, rows)
     return lib.hipt_clam_mb_forward_bags_wide(C.byref(w), FAKE, FAKE, B, rows, attention_only, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, nbytes, None)
-
-
-def test_symbols_are_exported_declared_mapped_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "hipt_abmil.h")).read()
-    declared = set(re.findall(r"\b(hipt_[a-z0-9_]+)\s*\(", hdr))
-    vmap = open(os.path.join(ROOT, "hipt_abmil_atec23_amd", "csrc", "hipt_abmil.map")).read()
-    globs = re.search(r"global:\s*([^;]+);", vmap).group(1).split()
-    lib = N.lib()
-    for name in NAMES:
-        assert name in declared and name in N.SIGNATURES and hasattr(lib, name), name
-        assert any(re.fullmatch(g.replace("*", ".*"), name) for g in globs), (name, globs)     # the export map lets it out
-    assert N.SIGNATURES[NAMES[2]] == N.SIGNATURES["hipt_clam_mb_forward_bags"]
-    assert N.SIGNATURES[NAMES[1]] == N.SIGNATURES["hipt_clam_mb_bags_workspace_bytes"]
-    assert Fn._BAGS_FORMS["mb_wide"][:2] == NAMES[:0:-1] and callable(Fn.clam_mb_forward_bags_wide)
-    assert lib.hipt_abi_version() == N.ABI_VERSION   # additive: the version stays
 
 
 def test_supported_is_the_wide_table_times_two_to_four_branches():
@@ -100,41 +78,8 @@ def test_a_refusal_names_the_widths_and_the_branch_range():
     assert forward(lib, w, B=0, nbytes=1 << 20) == E_BADARG and lib.hipt_last_error().decode().startswith(PREFIX)
 
 
-def test_a_cpu_model_and_the_default_switches_keep_the_loop():
-    assert CLAM_MB.bags_one_call is False and CLAM_MB.bags_wide is False
-    torch.manual_seed(0)
-    m = CLAM_MB(size_arg=[64, 256, 64]).eval()
-    assert "bags_wide" not in m.__dict__ and "bags_one_call" not in m.__dict__
-    assert m._bags_form(torch.device("cpu")) is None
-    bags = [torch.randn(n, 64) for n in (1, 5, 3)]
-    want = m.forward_bags(bags)
-    assert m.bags_route == "per_bag"
-    m.bags_one_call = m.bags_wide = True
-    assert m._bags_form(torch.device("cpu")) is None
-    before = N.calls
-    got = m.forward_bags(bags)
-    assert m.bags_route == "per_bag" and N.calls == before
-    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(got[2], want[2])
-
-
-def test_the_default_switches_never_reach_the_library(monkeypatch):
-    """On a device the default flags return None before any weight image is packed or the library is asked."""
-    torch.manual_seed(0)
-    m = CLAM_MB(size_arg=[64, 256, 64]).eval()
-    asked = []
-    monkeypatch.setattr(m, "_pack_stacked", lambda device: asked.append(device))
-    assert m._bags_form(torch.device("cuda", 0)) is None and asked == []
-    m.bags_wide = True                                  # bags_wide alone: still the loop
-    assert m._bags_form(torch.device("cuda", 0)) is None and asked == []
-
-
 def test_the_other_forms_answer_as_before():
     lib = N.lib()
-    assert Fn._BAGS_FORMS["mb"][:2] == ("hipt_clam_mb_forward_bags", "hipt_clam_mb_bags_workspace_bytes")
-    assert Fn._BAGS_FORMS["wide"][:2] == ("hipt_clam_sb_forward_bags_wide", "hipt_clam_wide_bags_workspace_bytes")
-    w = weights(F32, 1024, 512, 256, 3)
-    assert Fn._BAGS_FORMS["mb"][2](w, 7, 1000) == Fn._BAGS_FORMS["mb_wide"][2](w, 7, 1000) == ((3, 1000), (7, 3, 512), (7, 3))
-    assert Fn._BAGS_FORMS["wide"][2](w, 7, 1000) == ((1000,), (7, 512), (7, 3))
     for dt in (F32, BF16):
         for s1, s2 in PAIRS:
             for K in (1, 2, 4, 5):

@@ -3,7 +3,8 @@
 The row counts of a call are ``ROWS`` (1 687 rows, 17 work units; the last bag alone is 1 000 rows = 8 tiles): bags of one and two
 rows between larger ones, a bag that ends one row short of a 128-row tile, one that fills a tile exactly and one that runs one row
 past it, so that bag boundaries fall before, on and after the boundaries a tiling of the concatenated rows would have.  ``B = 1``
-runs with 129 rows (a full tile and a one-row tile)."""
+runs with 129 rows (a full tile and a one-row tile).  What this form shares with the others is stated
+once in tests/clam_bags_util.py; graph capture and the two input forms run from tests/test_gpu_clam_forms.py."""
 import ctypes as C
 
 import numpy as np
@@ -11,10 +12,9 @@ import pytest
 import torch
 
 import clam_bags_util as U
-from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
+from clam_bags_util import DEV, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
 from conftest import golden
 from hipt_abmil_atec23_amd import CLAM_MB, CLAM_SB, _native as N
-from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd import synth
 from hipt_abmil_atec23_amd.evaluate import evaluate_split
 
@@ -49,10 +49,7 @@ def reference(size, seed, rounded=False, rows=tuple(ROWS)):
 
 
 def run_bags(m, bags):
-    logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True)
-    assert m.bags_route == "bags"
-    torch.cuda.synchronize()
-    return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
+    return U.run_form(m, "sb", bags)
 
 
 # ---------------------------------------------------------------- 1. fp32 parity
@@ -77,9 +74,7 @@ def test_fp32_parity_s1_32_through_the_binding():
     w = m._pack(torch.device(DEV))
     assert N.lib().hipt_clam_bags_supported(C.byref(w)) == 1
     bags = bags_of(192, 5, rows)
-    cat = torch.cat(bags, dim=0)
-    off = Fn.BagOffsets(np.cumsum([0, *rows]), cat.shape[0], cat.device)
-    A_raw, M, logits, Y_prob, Y_hat = Fn.clam_sb_forward_bags(w, cat, off)
+    (A_raw, M, logits, Y_prob, Y_hat), _, off = U.direct("sb", w, bags, rows)
     out = {"A_raw": [A_raw[off.host[b]:off.host[b + 1]].view(1, -1) for b in range(len(rows))], "M": M, "logits": logits, "Y_prob": Y_prob,
            "Y_hat": Y_hat.view(-1, 1)}
     worst, wrong = errors(out, reference(size, 5, False, rows))
@@ -103,24 +98,7 @@ def test_fp32_golden_bags_among_others(size, names):
         assert np.array_equal(got["Y_hat"].cpu().numpy(), g["Y_hat"])
 
 
-# ---------------------------------------------------------------- 2. bitwise batch invariance
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_a_bag_does_not_see_its_neighbours(dtype, monkeypatch):
-    size = (384, 128, 64)
-    m = make(size, dtype)
-    bags = bags_of(384, 9)
-    full = run_bags(m, bags)
-    rev = run_bags(m, bags[::-1])
-    monkeypatch.setenv("HIPT_BAGS_MAX_WG", "3")     # 17 units over 3 workgroups (6 + 6 + 5) instead of one each
-    few = run_bags(m, bags)
-    monkeypatch.delenv("HIPT_BAGS_MAX_WG")
-    B = len(bags)
-    for b in range(B):
-        assert_same_bits(per_bag(full, b), per_bag(run_bags(m, [bags[b]]), 0), f"bag {b} alone")
-        assert_same_bits(per_bag(full, b), per_bag(rev, B - 1 - b), f"bag {b} reversed order")
-        assert_same_bits(per_bag(full, b), per_bag(few, b), f"bag {b} small grid")
-
-
+# ---------------------------------------------------------------- 2. the split function
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_evaluate_split_does_not_depend_on_the_chunking(dtype):
     m = make((384, 128, 64), dtype)
@@ -167,13 +145,7 @@ def test_tile_is_the_fused_kernels_tile(size, dtype):
 def measure_bf16(route, size):
     m = make(size, "bf16")
     bags = bags_of(size[0], BF16_SEED)
-    if route == "bags":
-        out = run_bags(m, bags)
-    else:
-        with torch.no_grad():   # (with gradients enabled forward() takes the fp32 training kernels)
-            outs = [m(b, return_features=True) for b in bags]
-        out = {"A_raw": [o[3] for o in outs], "M": torch.cat([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
-               "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
+    out = run_bags(m, bags) if route == "bags" else U.run_loop(m, bags)
     refs = reference(size, BF16_SEED, True)
     worst, wrong = errors(out, refs)
     return worst, wrong, refs
@@ -193,28 +165,7 @@ def test_bf16_parity_per_bag(size):
     assert [b for b in wrong if b in decided] == []
 
 
-# ---------------------------------------------------------------- 4. attention_only
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_attention_only_writes_a_raw_alone(dtype):
-    size = (384, 128, 64)
-    m = make(size, dtype)
-    bags = bags_of(384, 9)
-    full = run_bags(m, bags)
-    views = m.forward_bags(list(bags), attention_only=True)
-    assert [bits(v) for v in views] == [bits(a) for a in full["A_raw"]]
-    w = m._pack(torch.device(DEV))
-    cat = Fn.as_compute(torch.cat(bags, dim=0), w.dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), cat.shape[0], cat.device)
-    B = len(ROWS)
-    sent = lambda *shape: torch.full(shape, -7.25, dtype=torch.float32, device=DEV)
-    out = (sent(cat.shape[0]), sent(B, 128), sent(B, 2), sent(B, 2), torch.full((B,), -7, dtype=torch.int64, device=DEV))
-    Fn.clam_sb_forward_bags(w, cat, off, attention_only=True, out=out)
-    torch.cuda.synchronize()
-    assert bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-    assert all(bool((t == -7.25).all()) for t in out[1:4]) and bool((out[4] == -7).all())
-
-
-# ---------------------------------------------------------------- 5. fallback route
+# ---------------------------------------------------------------- 4. fallback route
 @pytest.mark.parametrize("cls,size", [(CLAM_SB, (1024, 512, 256)), (CLAM_MB, (192, 128, 64))])
 def test_other_configurations_loop_over_forward(cls, size):
     m = make(size, "fp32", cls)
@@ -231,62 +182,17 @@ def test_other_configurations_loop_over_forward(cls, size):
     assert [bits(a) for a in att] == [bits(a) for a in a_raw]
 
 
-# ---------------------------------------------------------------- 6. graph capture
-def test_one_call_is_captured_and_replayed():
-    """The call is three launches on the capturing stream and nothing else (no copy, no synchronisation, no second stream), so the
-    captured graph is a chain; replays on new contents of the same shape equal an eager call bit for bit."""
-    size = (384, 128, 64)
-    m = make(size)
-    static = torch.cat(bags_of(384, 9), dim=0).clone()
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), static.shape[0], static.device)   # checked and uploaded BEFORE the capture
-    call = lambda: m.forward_bags((static, off), return_features=True)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        call()                                        # weight image, workspace and per-device kernel setup exist before the capture
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        logits, y_prob, y_hat, a_raw, res = call()
-    for seed in (31, 32):
-        fresh = torch.cat(bags_of(384, seed), dim=0)
-        static.copy_(fresh)
-        g.replay()
-        torch.cuda.synchronize()
-        got = {"A_raw": torch.cat(a_raw, dim=1), "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
-        eager = run_bags(m, bags_of(384, seed))
-        eager["A_raw"] = torch.cat(eager["A_raw"], dim=1)
-        assert_same_bits(got, eager, f"replay on seed {seed}")
+# ---------------------------------------------------------------- the checks every form shares (clam_bags_util), on this form's cases
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_a_bag_does_not_see_its_neighbours(dtype, monkeypatch):
+    U.check_neighbours("sb", (384, 128, 64), 2, dtype, monkeypatch)
 
 
-# ---------------------------------------------------------------- 7. guard bytes
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_attention_only_writes_a_raw_alone(dtype):
+    U.check_attention_only("sb", (384, 128, 64), 2, dtype)
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_outputs_and_workspace_stay_inside_their_buffers(dtype):
-    size = (384, 128, 64)
-    m = make(size, dtype)
-    w = m._pack(torch.device(DEV))
-    bags = bags_of(384, 9)
-    cat = Fn.as_compute(torch.cat(bags, dim=0), w.dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), cat.shape[0], cat.device)
-    B, rows = len(ROWS), cat.shape[0]
-    need = N.lib().hipt_clam_bags_workspace_bytes(C.byref(w), B, rows)
-    assert need > 0 and need % 256 == 0
-    fenced = []
-
-    def buf(nbytes, dt=torch.uint8):
-        raw = torch.full((nbytes + 2 * FENCE,), FILL, dtype=torch.uint8, device=DEV)
-        assert raw.data_ptr() % 256 == 0
-        fenced.append((raw, nbytes))
-        return raw[FENCE:FENCE + nbytes].view(dt)
-
-    out = (buf(rows * 4, torch.float32), buf(B * 128 * 4, torch.float32).view(B, 128), buf(B * 2 * 4, torch.float32).view(B, 2),
-           buf(B * 2 * 4, torch.float32).view(B, 2), buf(B * 8, torch.int64))
-    Fn.clam_sb_forward_bags(w, cat, off, out=out, ws=buf(need))
-    torch.cuda.synchronize()
-    for raw, n in fenced:
-        assert bool((raw[:FENCE] == FILL).all()) and bool((raw[FENCE + n:] == FILL).all()), "a write outside a buffer"
-    full = run_bags(m, bags)
-    assert bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-    assert bits(out[1]) == bits(full["M"]) and bits(out[2]) == bits(full["logits"]) and bits(out[3]) == bits(full["Y_prob"])
-    assert bits(out[4]) == bits(full["Y_hat"])
+    U.check_fences("sb", (384, 128, 64), 2, dtype)

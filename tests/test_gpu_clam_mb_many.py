@@ -12,26 +12,26 @@ models take without this kernel -- was measured on one MI355X (MEASURED[dtype][o
 run); the bar is twice the loop's figure, the factor covering the different fold order, and in fp32 never above the project's 1e-4.
 SEED was chosen on the host from the fp64 reference alone: of seeds 21..32 the one whose smallest gap between a bag's two largest
 reference logits, over CASES, both rounding modes and all bags, is largest (1.96e-2); tests/test_clam_mb_many_host.py holds that gap
-against 4x the logits bars.  Each test prints its figures before it asserts."""
+against 4x the logits bars.  Each test prints its figures before it asserts.
+
+What this form shares with the others is stated once in tests/clam_bags_util.py; graph capture, the two input forms and either
+switch off run from tests/test_gpu_clam_forms.py."""
 import ctypes as C
-import os
-import subprocess
-import sys
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import clam_bags_util as U
-from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
+from clam_bags_util import DEV, OUTS, TOL, as_out, bits, errors, md, run_loop
 from clam_wide_mb_ref import logit_gap
-from conftest import ROOT
 from hipt_abmil_atec23_amd import CLAM_MB, _native as N, synth
-from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd.evaluate import validate_split
 
 pytestmark = pytest.mark.gpu
 ROWS = (1, 2, 15, 17, 127, 128, 129, 300)
+assert ROWS == U.FORMS["mb_many"].rows
 CASES = [((64, 128, 64), 5), ((64, 128, 64), 8), ((192, 128, 64), 6), ((128, 64, 16), 7), ((64, 32, 16), 5)]
 PARITY = [(s, K, dt) for dt in ("fp32", "bf16") for s, K in CASES if not (dt == "bf16" and s[1] == 32)]   # (32, .) is fp32 only
 SEED = 29
@@ -43,51 +43,15 @@ MEASURED = {
 BARS = {dt: {k: (min(2.0 * v[1], TOL) if dt == "fp32" else 2.0 * v[1]) for k, v in d.items()} for dt, d in MEASURED.items()}
 
 
-def make(size, dtype="fp32", K=5):
-    return U.make(size, dtype, CLAM_MB, K, False)
+make = functools.partial(U.model, "mb_many")
 
 
 def bags_of(s0, seed=SEED, rows=ROWS):
     return U.bags_of(s0, seed, rows)
 
 
-def as_out(ret):
-    logits, y_prob, y_hat, a_raw, res = ret
-    return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat, "res": res}
-
-
-def run_bags(m, bags, flags=("bags_one_call", "bags_many"), route="bags", **kw):
-    """forward_bags with the given switches set for the call"""
-    for f in flags:
-        setattr(m, f, True)
-    try:
-        pair = len(bags) == 2 and isinstance(bags[1], Fn.BagOffsets)      # (cat, offsets) instead of a sequence of bags
-        ret = m.forward_bags(bags if pair else list(bags), return_features=True, **kw)
-        assert m.bags_route == route, (flags, m.bags_route)
-    finally:
-        for f in flags:
-            delattr(m, f)
-    torch.cuda.synchronize()
-    return as_out(ret)
-
-
-def run_loop(m, bags):
-    with torch.no_grad():   # (with gradients enabled forward() takes the fp32 training kernels)
-        outs = [m(b, return_features=True) for b in bags]
-    torch.cuda.synchronize()
-    return {"A_raw": [o[3] for o in outs], "M": torch.stack([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
-            "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
-
-
-def direct(w, bags, rows, **kw):
-    cat = Fn.as_compute(torch.cat(list(bags), dim=0), w.dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *rows]), cat.shape[0], cat.device)
-    return Fn.clam_mb_forward_bags_many(w, cat, off, **kw), cat, off
-
-
-def a_bits(views):
-    """the [K, rows] score matrix of a call, from its per-bag views"""
-    return bits(torch.cat(list(views), dim=1))
+def run_bags(m, bags, **kw):
+    return U.run_form(m, "mb_many", bags, **kw)
 
 
 def parity_figures(size, K, dtype):
@@ -168,156 +132,21 @@ def test_a_branch_has_the_bits_of_the_k_le_4_kernel(size, K, groups, dtype):
             assert bits(full["logits"][:, k]) == bits(sub["logits"][:, k - lo]), f"logits of branch {k} (group {lo}:{hi})"
 
 
-# ---------------------------------------------------------------- 3. the switches
+# ---------------------------------------------------------------- the checks every form shares (clam_bags_util), on this form's cases
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_either_switch_off_keeps_the_loop_and_its_bits(dtype):
-    size, K = (64, 128, 64), 5
-    m = make(size, dtype, K)
-    assert CLAM_MB.bags_one_call is False and CLAM_MB.bags_many is False
-    bags = bags_of(size[0], 13, (1, 129, 300))
-    want = run_loop(m, bags)
-    for flags in ((), ("bags_one_call",), ("bags_many",)):
-        got = run_bags(m, bags, flags, "per_bag")
-        assert a_bits(got["A_raw"]) == a_bits(want["A_raw"]), flags
-        for k in ("M", "logits", "Y_prob", "Y_hat"):
-            assert got[k].shape == want[k].shape and bits(got[k]) == bits(want[k]), (flags, k)
+@pytest.mark.parametrize("size,K", U.FORMS["mb_many"].invariance)
+def test_a_bag_does_not_see_its_neighbours(size, K, dtype, monkeypatch):
+    U.check_neighbours("mb_many", size, K, dtype, monkeypatch)      # (the small grid: all 11 units on ONE workgroup)
 
 
-# ---------------------------------------------------------------- 4. bitwise independence
-CHILD = """
-import sys
-sys.path[:0] = [{root!r}, {tests!r}]
-import numpy as np, torch
-import test_gpu_clam_mb_many as T
-out = {{}}
-for dtype in ("fp32", "bf16"):
-    for size, K in T.INVARIANCE:
-        got = T.run_bags(T.make(size, dtype, K), T.bags_of(size[0], 9))
-        got["A_raw"] = torch.cat(list(got["A_raw"]), dim=1)
-        for k in (*T.OUTS, "Y_hat"):
-            out[f"{{dtype}}/{{size}}/{{K}}/{{k}}"] = got[k].cpu().numpy()
-np.savez(sys.argv[1], **out)
-"""
-INVARIANCE = [((64, 128, 64), 5), ((128, 64, 16), 7)]
-
-
-@pytest.fixture(scope="module")
-def one_workgroup(tmp_path_factory):
-    """The calls of the independence test under HIPT_BAGS_MAX_WG=1 (all 11 units on one workgroup), made in a fresh child process"""
-    path = str(tmp_path_factory.mktemp("mb_many") / "one_wg.npz")
-    env = dict(os.environ, HIPT_BAGS_MAX_WG="1")
-    code = CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
-    r = subprocess.run([sys.executable, "-c", code, path], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return dict(np.load(path))
-
-
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size,K", INVARIANCE)
-def test_a_bag_does_not_see_its_neighbours(size, K, dtype, one_workgroup):
-    assert "HIPT_BAGS_MAX_WG" not in os.environ
-    m = make(size, dtype, K)
-    bags = bags_of(size[0], 9)
-    B = len(bags)
-    assert B == 8
-    full = run_bags(m, bags)
-    rev = run_bags(m, bags[::-1])
-    mid = run_bags(m, [bags[(b + 1) % B] for b in range(B)])      # every bag one place earlier: the first goes last
-    for b in range(B):
-        assert_same_bits(per_bag(full, b, True), per_bag(run_bags(m, [bags[b]]), 0, True), f"bag {b} alone (B = 1)")
-        assert_same_bits(per_bag(full, b, True), per_bag(rev, B - 1 - b, True), f"bag {b} reversed order")
-        assert_same_bits(per_bag(full, b, True), per_bag(mid, (b - 1) % B, True), f"bag {b} shifted")
-    A = torch.cat(list(full["A_raw"]), dim=1)
-    for k, t in (("A_raw", A), *((k, full[k]) for k in ("M", "logits", "Y_prob", "Y_hat"))):
-        child = one_workgroup[f"{dtype}/{size}/{K}/{k}"]
-        assert child.shape == tuple(t.shape) and child.tobytes() == bits(t), f"{k}: one workgroup for all units"
-
-
-# ---------------------------------------------------------------- 5., 6. attention_only and the buffers' edges
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("size,K", [((64, 128, 64), 8), ((128, 64, 16), 7)])
 def test_attention_only_writes_a_raw_alone_and_nothing_leaves_its_buffer(size, K, dtype):
-    m = make(size, dtype, K)
-    bags = bags_of(size[0], 9)
-    full = run_bags(m, bags)
-    m.bags_one_call = m.bags_many = True
-    try:
-        views = m.forward_bags(list(bags), attention_only=True)
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_one_call, m.bags_many
-    assert [tuple(v.shape) for v in views] == [(K, n) for n in ROWS] and a_bits(views) == a_bits(full["A_raw"])
-    w = m._pack_stacked(torch.device(DEV))
-    B, total, S1 = len(ROWS), sum(ROWS), size[1]
-    need = N.lib().hipt_clam_mb_many_bags_workspace_bytes(C.byref(w), B, total)
-    assert need > 0 and need % 256 == 0
-    fenced = []
-
-    def buf(nbytes, dt=torch.uint8):
-        raw = torch.full((nbytes + 2 * FENCE,), FILL, dtype=torch.uint8, device=DEV)
-        assert raw.data_ptr() % 256 == 0
-        fenced.append((raw, nbytes))
-        return raw[FENCE:FENCE + nbytes].view(dt)
-
-    def fences_hold():
-        for raw, n in fenced:
-            assert bool((raw[:FENCE] == FILL).all()) and bool((raw[FENCE + n:] == FILL).all()), "a write outside a buffer"
-
-    out = (buf(K * total * 4, torch.float32).view(K, total), buf(B * K * S1 * 4, torch.float32).view(B, K, S1),
-           buf(B * K * 4, torch.float32).view(B, K), buf(B * K * 4, torch.float32).view(B, K), buf(B * 8, torch.int64))
-    ws = buf(need)                                                  # exactly workspace_bytes between its guard regions
-    direct(w, bags, ROWS, attention_only=True, out=out, ws=ws)
-    torch.cuda.synchronize()
-    fences_hold()
-    assert bits(out[0]) == a_bits(full["A_raw"])
-    assert all(bool((t.contiguous().view(torch.uint8) == FILL).all()) for t in out[1:]), "attention_only wrote a pooled output"
-    direct(w, bags, ROWS, out=out, ws=ws)
-    torch.cuda.synchronize()
-    fences_hold()
-    assert bits(out[0]) == a_bits(full["A_raw"]) and bits(out[1]) == bits(full["M"]) and bits(out[2]) == bits(full["logits"])
-    assert bits(out[3]) == bits(full["Y_prob"]) and bits(out[4]) == bits(full["Y_hat"])
-    # the workspace carries no state: a second call on the used workspace gives the same bits
-    direct(w, bags, ROWS, out=out, ws=ws)
-    torch.cuda.synchronize()
-    assert bits(out[1]) == bits(full["M"]) and bits(out[0]) == a_bits(full["A_raw"])
-    with pytest.raises(RuntimeError):                               # a shorter workspace: refused before anything is launched
-        direct(w, bags, ROWS, out=out, ws=ws[:need - 256])
-    fences_hold()
+    U.check_attention_only("mb_many", size, K, dtype)
+    U.check_fences("mb_many", size, K, dtype)
 
 
-# ---------------------------------------------------------------- 7. graph capture
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_one_call_is_captured_and_replayed_twice(dtype):
-    size, K = (64, 128, 64), 5
-    m = make(size, dtype, K)
-    static = torch.cat(bags_of(64, 9), dim=0).clone()
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), static.shape[0], static.device)   # checked and uploaded BEFORE the capture
-    m.bags_one_call = m.bags_many = True
-    try:
-        call = lambda: m.forward_bags((static, off), return_features=True)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            call()                                    # weight image, workspace and per-device kernel setup exist before the capture
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):                     # one capture on a single stream
-            logits, y_prob, y_hat, a_raw, res = call()
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_one_call, m.bags_many
-    for seed in (31, 32):                             # two replays, each on new bags
-        static.copy_(torch.cat(bags_of(64, seed), dim=0))
-        g.replay()
-        torch.cuda.synchronize()
-        got = {"A_raw": torch.cat(a_raw, dim=1), "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
-        eager = run_bags(m, bags_of(64, seed))
-        eager["A_raw"] = torch.cat(eager["A_raw"], dim=1)
-        assert_same_bits(got, eager, f"replay on seed {seed}")
-
-
-# ---------------------------------------------------------------- 8. validation of a split
+# ---------------------------------------------------------------- 3. validation of a split
 def test_validate_split_in_one_call_agrees_with_the_loop():
     size, K = (64, 128, 64), 5
     m = CLAM_MB(size_arg=list(size), n_classes=K, k_sample=2)

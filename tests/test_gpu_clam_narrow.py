@@ -3,15 +3,18 @@
 
 Weights and bags are made as in tests/test_gpu_clam_bags.py.  The row counts of a call are ``ROWS`` (1 851 rows, 19 work units):
 bags of one and two rows, bags one row short of and one row past a 32-row wave block, bags that end before, on and after a 128-row
-tile, and a bag of 1 100 rows = 9 tiles, so that the combine's ``t + 8`` stride has a second term."""
+tile, and a bag of 1 100 rows = 9 tiles, so that the combine's ``t + 8`` stride has a second term.  What this form shares with the
+others is stated once in tests/clam_bags_util.py; graph capture, the two input forms and the default switch run from
+tests/test_gpu_clam_forms.py."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import clam_bags_util as U
-from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
+from clam_bags_util import DEV, OUTS, TOL, bits, errors, md, per_bag, run_loop
 from conftest import golden
 from hipt_abmil_atec23_amd import CLAM_SB, _native as N
 from hipt_abmil_atec23_amd import functional as Fn
@@ -20,6 +23,7 @@ from hipt_abmil_atec23_amd.evaluate import evaluate_split, validate_split
 
 pytestmark = pytest.mark.gpu
 ROWS = (1, 2, 31, 33, 127, 128, 129, 300, 1100)
+assert ROWS == U.FORMS["narrow"].rows
 ROWS_I = (8, 31, 33, 127, 128, 129, 300, 1100)      # the instance branch needs k_sample = 8 rows per bag
 SHAPES = [(192, 16, 8), (192, 8, 4), (512, 32, 8), (1024, 32, 8)]
 SHAPES_BF16 = SHAPES + [(192, 32, 16)]
@@ -28,8 +32,7 @@ SHAPES_BF16 = SHAPES + [(192, 32, 16)]
 BF16_SEED = 26
 
 
-def make(size, dtype="fp32", subtyping=False):
-    return U.make(size, dtype, CLAM_SB, 2, subtyping)
+make = functools.partial(U.model, "narrow")
 
 
 def bags_of(s0, seed, rows=ROWS):
@@ -41,30 +44,7 @@ def reference(size, seed, rounded=False, rows=ROWS):
 
 
 def run_narrow(m, bags, **kw):
-    """forward_bags with the switch set, on the one-call route"""
-    m.bags_narrow = True
-    try:
-        logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True, **kw)
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_narrow
-    torch.cuda.synchronize()
-    return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat, "res": res}
-
-
-def run_loop(m, bags):
-    with torch.no_grad():   # (with gradients enabled forward() takes the fp32 training kernels)
-        outs = [m(b, return_features=True) for b in bags]
-    torch.cuda.synchronize()
-    return {"A_raw": [o[3] for o in outs], "M": torch.cat([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
-            "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
-
-
-def direct(w, bags, rows, narrow=True, **kw):
-    cat = Fn.as_compute(torch.cat(list(bags), dim=0), w.dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *rows]), cat.shape[0], cat.device)
-    call = Fn.clam_sb_forward_bags_narrow if narrow else Fn.clam_sb_forward_bags
-    return call(w, cat, off, **kw), cat, off
+    return U.run_form(m, "narrow", bags, **kw)
 
 
 # ---------------------------------------------------------------- 1. fp32 parity
@@ -131,32 +111,14 @@ def test_bf16_parity_per_bag(size):
     assert wrong == []
 
 
-# ---------------------------------------------------------------- 4. bitwise independence
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size", [(192, 16, 8), (192, 8, 4), (1024, 32, 8)])
-def test_a_bag_does_not_see_its_neighbours(size, dtype, monkeypatch):
-    m = make(size, dtype)
-    bags = bags_of(size[0], 9)
-    full = run_narrow(m, bags)
-    rev = run_narrow(m, bags[::-1])
-    monkeypatch.setenv("HIPT_BAGS_MAX_WG", "3")     # 19 units over 3 workgroups instead of one each
-    few = run_narrow(m, bags)
-    monkeypatch.delenv("HIPT_BAGS_MAX_WG")
-    B = len(bags)
-    for b in range(B):
-        assert_same_bits(per_bag(full, b), per_bag(run_narrow(m, [bags[b]]), 0), f"bag {b} alone")
-        assert_same_bits(per_bag(full, b), per_bag(rev, B - 1 - b), f"bag {b} reversed order")
-        assert_same_bits(per_bag(full, b), per_bag(few, b), f"bag {b} small grid")
-
-
-# ---------------------------------------------------------------- 5. the width both kernels have
+# ---------------------------------------------------------------- 4. the width both kernels have
 def test_fp32_s1_32_s2_16_agrees_with_the_wide_call():
     size = (192, 32, 16)
     w = make(size)._pack(torch.device(DEV))
     assert N.lib().hipt_clam_bags_supported(C.byref(w)) == 1 and N.lib().hipt_clam_narrow_bags_supported(C.byref(w)) == 1
     bags = bags_of(192, 5)
-    a, _, _ = direct(w, bags, ROWS, narrow=True)
-    b, _, _ = direct(w, bags, ROWS, narrow=False)
+    a, _, _ = U.direct("narrow", w, bags, ROWS)
+    b, _, _ = U.direct("sb", w, bags, ROWS)
     torch.cuda.synchronize()
     for name, x, y in zip(OUTS, a[:4], b[:4]):
         assert md(x, y.cpu().numpy()) <= 1e-5, (name, md(x, y.cpu().numpy()))
@@ -167,96 +129,11 @@ def test_fp32_s1_32_s2_16_agrees_with_the_wide_call():
     assert bits(torch.cat(out["A_raw"], dim=1).reshape(-1)) == bits(b[0]) and bits(out["M"]) == bits(b[1])
 
 
-# ---------------------------------------------------------------- 6. attention_only
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size", [(192, 16, 8), (192, 8, 4)])
-def test_attention_only_writes_a_raw_alone(size, dtype):
-    m = make(size, dtype)
-    bags = bags_of(size[0], 9)
-    full = run_narrow(m, bags)
-    m.bags_narrow = True
-    try:
-        views = m.forward_bags(list(bags), attention_only=True)
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_narrow
-    assert [bits(v) for v in views] == [bits(a) for a in full["A_raw"]]
-    w = m._pack(torch.device(DEV))
-    B = len(ROWS)
-    sent = lambda *shape: torch.full(shape, -7.25, dtype=torch.float32, device=DEV)
-    out = (sent(sum(ROWS)), sent(B, size[1]), sent(B, 2), sent(B, 2), torch.full((B,), -7, dtype=torch.int64, device=DEV))
-    direct(w, bags, ROWS, attention_only=True, out=out)
-    torch.cuda.synchronize()
-    assert bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-    assert all(bool((t == -7.25).all()) for t in out[1:4]) and bool((out[4] == -7).all())
-
-
-# ---------------------------------------------------------------- 7. guard bytes
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size", [(192, 8, 4), (192, 16, 8), (512, 32, 8)])
-def test_outputs_and_workspace_stay_inside_their_buffers(size, dtype):
-    m = make(size, dtype)
-    w = m._pack(torch.device(DEV))
-    bags = bags_of(size[0], 9)
-    B, rows, S1 = len(ROWS), sum(ROWS), size[1]
-    need = N.lib().hipt_clam_narrow_bags_workspace_bytes(C.byref(w), B, rows)
-    assert need > 0 and need % 256 == 0
-    fenced = []
-
-    def buf(nbytes, dt=torch.uint8):
-        raw = torch.full((nbytes + 2 * FENCE,), FILL, dtype=torch.uint8, device=DEV)
-        assert raw.data_ptr() % 256 == 0
-        fenced.append((raw, nbytes))
-        return raw[FENCE:FENCE + nbytes].view(dt)
-
-    out = (buf(rows * 4, torch.float32), buf(B * S1 * 4, torch.float32).view(B, S1), buf(B * 2 * 4, torch.float32).view(B, 2),
-           buf(B * 2 * 4, torch.float32).view(B, 2), buf(B * 8, torch.int64))
-    direct(w, bags, ROWS, out=out, ws=buf(need))
-    torch.cuda.synchronize()
-    for raw, n in fenced:
-        assert bool((raw[:FENCE] == FILL).all()) and bool((raw[FENCE + n:] == FILL).all()), "a write outside a buffer"
-    full = run_narrow(m, bags)
-    assert bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-    assert bits(out[1]) == bits(full["M"]) and bits(out[2]) == bits(full["logits"]) and bits(out[3]) == bits(full["Y_prob"])
-    assert bits(out[4]) == bits(full["Y_hat"])
-
-
-# ---------------------------------------------------------------- 8. graph capture
-def test_one_call_is_captured_and_replayed():
-    size = (192, 16, 8)
-    m = make(size)
-    static = torch.cat(bags_of(192, 9), dim=0).clone()
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), static.shape[0], static.device)   # checked and uploaded BEFORE the capture
-    m.bags_narrow = True
-    try:
-        call = lambda: m.forward_bags((static, off), return_features=True)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            call()                                    # weight image, workspace and per-device kernel setup exist before the capture
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            logits, y_prob, y_hat, a_raw, res = call()
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_narrow
-    for seed in (31, 32):
-        static.copy_(torch.cat(bags_of(192, seed), dim=0))
-        g.replay()
-        torch.cuda.synchronize()
-        got = {"A_raw": torch.cat(a_raw, dim=1), "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
-        eager = run_narrow(m, bags_of(192, seed))
-        eager["A_raw"] = torch.cat(eager["A_raw"], dim=1)
-        assert_same_bits(got, eager, f"replay on seed {seed}")
-
-
-# ---------------------------------------------------------------- 9. the instance branch and the split functions
+# ---------------------------------------------------------------- 5. the instance branch and the split functions
 @pytest.mark.parametrize("subtyping", [False, True])
 def test_instance_branch_is_the_per_bag_chain(subtyping):
     size, k = (192, 16, 8), 8
-    m = make(size, "fp32", subtyping)
+    m = make(size, "fp32", subtyping=subtyping)
     bags = bags_of(192, 23, ROWS_I)
     labels = [b % 2 for b in range(len(ROWS_I))]
     run_narrow(m, bags[:1])   # the weight image exists
@@ -283,7 +160,7 @@ def test_instance_branch_is_the_per_bag_chain(subtyping):
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_split_functions_on_the_device(dtype):
-    m = make((192, 16, 8), dtype, True)
+    m = make((192, 16, 8), dtype, subtyping=True)
     bags = bags_of(192, 23, ROWS_I)
     labels = [b % 2 for b in range(len(ROWS_I))]
     e1 = evaluate_split(m, bags, labels, 2, max_rows_per_call=1 << 16)
@@ -308,19 +185,20 @@ def test_split_functions_on_the_device(dtype):
         assert np.array_equal(e1.all_preds, e0.all_preds)
 
 
-# ---------------------------------------------------------------- 10. default behaviour
+# ---------------------------------------------------------------- the checks every form shares (clam_bags_util), on this form's cases
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_default_forward_bags_still_loops_with_the_bits_of_forward(dtype):
-    m = CLAM_SB(size_arg="hipt_smaller")
-    m.load_state_dict(synth.make_state_dict(synth.clam_param_specs((192, 16, 8)), 192), strict=True)
-    m.relocate()
-    m.eval().set_compute_dtype(dtype)
-    assert m.bags_narrow is False
-    bags = bags_of(192, 13, (1, 129, 300))
-    logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True)
-    assert m.bags_route == "per_bag"
-    for b, bag in enumerate(bags):
-        with torch.no_grad():
-            l1, p1, h1, a1, r1 = m(bag, return_features=True)
-        assert bits(logits[b:b + 1]) == bits(l1) and bits(y_prob[b:b + 1]) == bits(p1) and bits(y_hat[b:b + 1]) == bits(h1)
-        assert bits(a_raw[b]) == bits(a1) and bits(res["features"][b]) == bits(r1["features"].reshape(res["features"][b].shape))
+@pytest.mark.parametrize("size", [(192, 16, 8), (192, 8, 4), (1024, 32, 8)])
+def test_a_bag_does_not_see_its_neighbours(size, dtype, monkeypatch):
+    U.check_neighbours("narrow", size, 2, dtype, monkeypatch)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("size", [(192, 16, 8), (192, 8, 4)])
+def test_attention_only_writes_a_raw_alone(size, dtype):
+    U.check_attention_only("narrow", size, 2, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("size", [(192, 8, 4), (192, 16, 8), (512, 32, 8)])
+def test_outputs_and_workspace_stay_inside_their_buffers(size, dtype):
+    U.check_fences("narrow", size, 2, dtype)

@@ -16,6 +16,9 @@ Wb, over the seven bags of ROWS (seed 21, K = 2), measured on an MI355X with ``m
 The smallest gap between the reference's two largest logits over the bags is 0.206 at [384,128,64] and 0.125 at [192,64,32], far above
 the logit bars, so equality of Y_hat is a statement about the kernels; every Y_hat agrees.  M: both per-bag paths pool a bf16 image
 of h1; the one-call path pools fp32 h1 (section 16's POOL32 path).
+
+What the K-branch form shares with the others is stated once in tests/clam_bags_util.py; graph capture, the two input forms and the
+default switch run from tests/test_gpu_clam_forms.py (form "mb").
 """
 import ctypes as C
 import functools
@@ -26,7 +29,7 @@ import torch
 
 import clam_bags_util as U
 import clam_mb_ref as R
-from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, md
+from clam_bags_util import DEV, OUTS, TOL, bits, md
 from hipt_abmil_atec23_amd import CLAM_MB, CLAM_SB, _native as N
 from hipt_abmil_atec23_amd import functional as Fn
 from hipt_abmil_atec23_amd import synth
@@ -47,8 +50,8 @@ INST_SEED = {CLAM_SB: 50, CLAM_MB: 50}   # seeds whose reference top-k gaps exce
 GAP = 1e-3           # ten times the A_raw bar
 
 
-def make(size, dtype="fp32", cls=CLAM_MB, n_classes=2, subtyping=False):
-    return U.make(size, dtype, cls, n_classes, subtyping, True)   # bags_one_call set
+def model_of(size, dtype="fp32", cls=CLAM_MB, n_classes=2, subtyping=False):
+    return U.make(size, dtype, cls, n_classes, subtyping)
 
 
 def params64(size, n_classes=2, multi=True, rounded=False):
@@ -68,31 +71,19 @@ errors = functools.partial(U.errors, multi=True)
 
 
 def run_bags(m, bags, **kw):
-    logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True, **kw)
-    assert m.bags_route == "bags"
-    torch.cuda.synchronize()
-    return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat, "res": res}
+    return U.run_form(m, "mb" if m._multi else "sb", bags, **kw)
 
 
-def run_per_bag(m, bags):
-    m.bags_one_call = False
-    try:
-        with torch.no_grad():
-            outs = [m(b, return_features=True) for b in bags]
-    finally:
-        m.bags_one_call = True
-    torch.cuda.synchronize()
-    return {"A_raw": [o[3] for o in outs], "M": torch.stack([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
-            "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
+run_per_bag = U.run_loop     # (forward does not read bags_one_call: the per-bag path needs no switch)
 
 
 # ---------------------------------------------------------------- 1. fp32 parity
 @pytest.mark.parametrize("size", SIZES)
 @pytest.mark.parametrize("K", [2, 3])
 def test_fp32_parity_per_bag(size, K):
-    m = make(size, "fp32", CLAM_MB, K)
+    m = model_of(size, "fp32", CLAM_MB, K)
     bags = bags_of(size[0], 3)
-    m.forward_bags(list(bags[:1]))   # the weight image exists
+    run_bags(m, bags[:1])   # the weight image exists
     before = N.calls
     out = run_bags(m, bags)
     assert N.calls == before + 1, "one native call for the whole set"
@@ -107,7 +98,7 @@ def test_fp32_parity_per_bag(size, K):
 
 # ---------------------------------------------------------------- 2. bf16 parity
 def measure_bf16(route, size):
-    m = make(size, "bf16")
+    m = model_of(size, "bf16")
     bags = bags_of(size[0], BF16_SEED)
     out = run_bags(m, bags) if route == "bags" else run_per_bag(m, bags)
     refs = reference(size, BF16_SEED, 2, True)
@@ -133,16 +124,14 @@ def test_bf16_parity_per_bag(size):
 @pytest.mark.parametrize("size", SIZES)
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_branch_k_is_the_single_branch_call(size, dtype):
-    m = make(size, dtype)
+    m = model_of(size, dtype)
     bags = bags_of(size[0], 5)
     out = run_bags(m, bags)
     ws, _ = m._pack_branches(torch.device(DEV))
-    cat = Fn.as_compute(torch.cat(bags, dim=0), ws[0].dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), cat.shape[0], cat.device)
     a_all = torch.cat(out["A_raw"], dim=1)
     same = True
     for k, w in enumerate(ws):
-        A_raw, M, logits, _, _ = Fn.clam_sb_forward_bags(w, cat, off)
+        (A_raw, M, logits, _, _), _, _ = U.direct("sb", w, bags, ROWS)
         torch.cuda.synchronize()
         d = (md(a_all[k], A_raw.cpu().numpy()), md(out["M"][:, k], M.cpu().numpy()), md(out["logits"][:, k], logits.cpu().numpy()))
         same = same and bits(a_all[k]) == bits(A_raw) and bits(out["M"][:, k]) == bits(M) and bits(out["logits"][:, k]) == bits(logits.reshape(-1))
@@ -150,97 +139,16 @@ def test_branch_k_is_the_single_branch_call(size, dtype):
     print(f"branch consistency {size} {dtype}: bit for bit equal = {same}")
 
 
-# ---------------------------------------------------------------- 4. independence, attention_only, guards, graph
+# ---------------------------------------------------------------- 4. the checks every form shares (clam_bags_util), on form "mb"
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_a_bag_does_not_see_its_neighbours(dtype, monkeypatch):
-    m = make((384, 128, 64), dtype)
-    bags = bags_of(384, 9)
-    full = run_bags(m, bags)
-    rev = run_bags(m, bags[::-1])
-    monkeypatch.setenv("HIPT_BAGS_MAX_WG", "3")     # 18 units over 3 workgroups instead of one each
-    few = run_bags(m, bags)
-    monkeypatch.delenv("HIPT_BAGS_MAX_WG")
-    B = len(bags)
-    for b in range(B):
-        assert_same_bits(per_bag(full, b), per_bag(run_bags(m, [bags[b]]), 0), f"bag {b} alone")
-        assert_same_bits(per_bag(full, b), per_bag(rev, B - 1 - b), f"bag {b} reversed order")
-        assert_same_bits(per_bag(full, b), per_bag(few, b), f"bag {b} small grid")
-
-
-def fenced_buffers():
-    fenced = []
-
-    def buf(nbytes, dt=torch.uint8):
-        raw = torch.full((nbytes + 2 * FENCE,), FILL, dtype=torch.uint8, device=DEV)
-        assert raw.data_ptr() % 256 == 0
-        fenced.append((raw, nbytes))
-        return raw[FENCE:FENCE + nbytes].view(dt)
-
-    def check(untouched=()):
-        for i, (raw, n) in enumerate(fenced):
-            assert bool((raw[:FENCE] == FILL).all()) and bool((raw[FENCE + n:] == FILL).all()), "a write outside a buffer"
-            if i in untouched:
-                assert bool((raw == FILL).all()), "attention_only wrote more than A_raw"
-    return buf, check
+    U.check_neighbours("mb", (384, 128, 64), 2, dtype, monkeypatch)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("attention_only", [False, True])
 def test_outputs_and_workspace_stay_inside_their_buffers(dtype, attention_only):
-    size, K = (384, 128, 64), 2
-    m = make(size, dtype)
-    w = m._pack_stacked(torch.device(DEV))
-    assert N.lib().hipt_clam_mb_bags_supported(C.byref(w)) == 1
-    bags = bags_of(384, 9)
-    cat = Fn.as_compute(torch.cat(bags, dim=0), w.dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), cat.shape[0], cat.device)
-    B, rows = len(ROWS), cat.shape[0]
-    need = N.lib().hipt_clam_mb_bags_workspace_bytes(C.byref(w), B, rows)
-    assert need > 0 and need % 256 == 0
-    buf, check = fenced_buffers()
-    f32 = torch.float32
-    out = (buf(K * rows * 4, f32).view(K, rows), buf(B * K * 128 * 4, f32).view(B, K, 128), buf(B * K * 4, f32).view(B, K),
-           buf(B * K * 4, f32).view(B, K), buf(B * 8, torch.int64))
-    ws = buf(need)
-    Fn.clam_mb_forward_bags(w, cat, off, attention_only=attention_only, out=out, ws=ws)
-    torch.cuda.synchronize()
-    check(untouched=(1, 2, 3, 4) if attention_only else ())
-    full = run_bags(m, bags)
-    assert bits(out[0]) == bits(torch.cat(full["A_raw"], dim=1))
-    if attention_only:
-        views = m.forward_bags(list(bags), attention_only=True)
-        assert [bits(v) for v in views] == [bits(a) for a in full["A_raw"]]
-    else:
-        assert bits(out[1]) == bits(full["M"]) and bits(out[2]) == bits(full["logits"]) and bits(out[3]) == bits(full["Y_prob"])
-        assert bits(out[4]) == bits(full["Y_hat"])
-    # a short or misaligned workspace is a bad argument, before anything is written
-    for bad in (ws[:need - 256], ws[16:]):
-        with pytest.raises(RuntimeError, match="code -?[0-9]+"):
-            Fn.clam_mb_forward_bags(w, cat, off, attention_only=attention_only, out=out, ws=bad)
-
-
-def test_one_call_is_captured_and_replayed():
-    m = make((384, 128, 64))
-    static = torch.cat(bags_of(384, 9), dim=0).clone()
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), static.shape[0], static.device)   # checked and uploaded BEFORE the capture
-    call = lambda: m.forward_bags((static, off), return_features=True)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        call()                                        # weight image, workspace and per-device kernel setup exist before the capture
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        logits, y_prob, y_hat, a_raw, res = call()
-    for seed in (31, 32):
-        static.copy_(torch.cat(bags_of(384, seed), dim=0))
-        g.replay()
-        torch.cuda.synchronize()
-        got = {"A_raw": torch.cat(a_raw, dim=1), "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
-        eager = run_bags(m, bags_of(384, seed))
-        eager["A_raw"] = torch.cat(eager["A_raw"], dim=1)
-        assert_same_bits(got, eager, f"replay on seed {seed}")
+    (U.check_attention_only if attention_only else U.check_fences)("mb", (384, 128, 64), 2, dtype)
 
 
 # ---------------------------------------------------------------- 5. segmented top-k
@@ -276,10 +184,10 @@ def inst_labels(cls, n_classes=2):
 @pytest.mark.parametrize("subtyping", [False, True])
 def test_instance_branch_is_the_per_bag_chain(cls, subtyping):
     size, k = (384, 128, 64), 8
-    m = make(size, "fp32", cls, 2, subtyping)
+    m = model_of(size, "fp32", cls, 2, subtyping)
     bags = bags_of(384, 23, ROWS_I)
     labels = inst_labels(cls)
-    m.forward_bags(list(bags[:1]))   # the weight image exists
+    run_bags(m, bags[:1])   # the weight image exists
     before = N.calls
     out = run_bags(m, bags, label=labels, instance_eval=True)
     assert N.calls == before + 3, "forward, segmented top-k, gather"
@@ -336,7 +244,7 @@ def test_instance_branch_against_the_reference(cls, subtyping):
     seed = INST_SEED[cls]
     refs, gap = inst_reference(cls, subtyping, seed)
     assert gap > GAP, f"seed {seed}: the reference's own top-k is decided by {gap:.2e} only"
-    m = make((384, 128, 64), "fp32", cls, 2, subtyping)
+    m = model_of((384, 128, 64), "fp32", cls, 2, subtyping)
     bags = bags_of(384, seed, ROWS_I)
     out = run_bags(m, bags, label=inst_labels(cls), instance_eval=True)
     ids, _ = Fn.topk_segments(torch.cat(out["A_raw"], dim=1).contiguous(), Fn.BagOffsets(np.cumsum([0, *ROWS_I]), sum(ROWS_I), torch.device(DEV)), 8)
@@ -363,7 +271,7 @@ def test_instance_branch_against_the_reference(cls, subtyping):
 @pytest.mark.parametrize("cls", [CLAM_SB, CLAM_MB])
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_validate_split_on_the_device(cls, dtype):
-    m = make((384, 128, 64), dtype, cls, 2, True)
+    m = model_of((384, 128, 64), dtype, cls, 2, True)
     bags = bags_of(384, 23, ROWS_I)
     labels = inst_labels(cls)
     a = validate_split(m, bags, labels, 2, max_rows_per_call=1 << 16)
@@ -373,11 +281,7 @@ def test_validate_split_on_the_device(cls, dtype):
         assert x.tobytes() == y.tobytes()
     assert (a.val_loss, a.val_error, a.val_inst_loss, a.inst_count, a.acc, a.inst) == (b.val_loss, b.val_error, b.val_inst_loss, b.inst_count, b.acc, b.inst)
     if dtype == "fp32":
-        m.bags_one_call = False
-        try:
-            loop = per_slide_loop(m, bags, labels, 2)
-        finally:
-            m.bags_one_call = True
+        loop = per_slide_loop(m, bags, labels, 2)
         assert md(a.prob, loop.prob) <= TOL and a.labels.tobytes() == loop.labels.tobytes()
         assert a.acc == loop.acc and a.inst == loop.inst and a.inst_count == loop.inst_count
         assert abs(a.val_loss - loop.val_loss) <= TOL and abs(a.val_inst_loss - loop.val_inst_loss) <= TOL

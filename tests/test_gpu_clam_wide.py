@@ -9,8 +9,12 @@ The bars.  fp32: the worst |error| against the fp64 oracle over the four shapes 
 one MI355X, was MEASURED_FP32_NEW for this kernel and MEASURED_FP32_LOOP for the loop of ``forward`` calls on the same bags (the
 parent commit's route); FP32_BAR is twice the larger, and stays below the project's fp32 bar of 1e-4.  bf16: the same two
 measurements against tests/clam_wide_ref.py (fp64; bag, W1, Wa, Wb rounded to bf16, h1 rounded to bf16 for the gate only), per
-output; BF16_BARS is twice the larger per output.  Each test prints its figures before it asserts."""
+output; BF16_BARS is twice the larger per output.  Each test prints its figures before it asserts.
+
+What this form shares with the others is stated once in tests/clam_bags_util.py; graph capture, the two input forms and the default
+switch run from tests/test_gpu_clam_forms.py."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -18,17 +22,15 @@ import torch
 
 import clam_bags_util as U
 import clam_wide_ref as WR
-from clam_bags_util import DEV, FENCE, FILL, OUTS, TOL, assert_same_bits, bits, errors, md, per_bag
-from hipt_abmil_atec23_amd import CLAM_SB, _native as N
-from hipt_abmil_atec23_amd import functional as Fn
+from clam_bags_util import DEV, OUTS, TOL, errors, md, run_loop
+from hipt_abmil_atec23_amd import _native as N
 from hipt_abmil_atec23_amd.evaluate import evaluate_split, validate_split
 
 pytestmark = pytest.mark.gpu
 ROWS = (1, 2, 31, 33, 63, 65, 127, 128, 129, 300, 1100)
+assert ROWS == U.FORMS["wide"].rows
 ROWS_I = (8, 31, 33, 63, 65, 127, 128, 129, 300, 1100)      # the instance branch needs k_sample = 8 rows per bag
-ROWS_PAST = (129, 64, 257)                                  # the call's last bag ends one row past a unit
 SHAPES = [(128, 256, 64), (128, 512, 256), (1024, 512, 384), (1024, 512, 256)]
-SMALL = [(128, 256, 64), (128, 512, 256)]
 # worst |error| over SHAPES and OUTS against the fp64 oracle, fp32 mode (seed 3), measured: (this kernel, the loop of forward calls)
 MEASURED_FP32_NEW, MEASURED_FP32_LOOP = 3.338e-6, 3.338e-6      # both at (1024, 512, 384), A_raw; bar 6.676e-6
 FP32_BAR = 2.0 * max(MEASURED_FP32_NEW, MEASURED_FP32_LOOP)
@@ -40,8 +42,7 @@ MEASURED_BF16 = {"A_raw": (1.421e-3, 1.421e-3), "M": (1.438e-4, 1.438e-4), "logi
 BF16_BARS = {k: 2.0 * max(v) for k, v in MEASURED_BF16.items()}
 
 
-def make(size, dtype="fp32", subtyping=False):
-    return U.make(size, dtype, CLAM_SB, 2, subtyping)
+make = functools.partial(U.model, "wide")
 
 
 def bags_of(s0, seed, rows=ROWS):
@@ -49,29 +50,7 @@ def bags_of(s0, seed, rows=ROWS):
 
 
 def run_wide(m, bags, **kw):
-    """forward_bags with the switch set, on the one-call route"""
-    m.bags_wide = True
-    try:
-        logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True, **kw)
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_wide
-    torch.cuda.synchronize()
-    return {"A_raw": a_raw, "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat, "res": res}
-
-
-def run_loop(m, bags):
-    with torch.no_grad():   # (with gradients enabled forward() takes the fp32 training kernels)
-        outs = [m(b, return_features=True) for b in bags]
-    torch.cuda.synchronize()
-    return {"A_raw": [o[3] for o in outs], "M": torch.cat([o[4]["features"] for o in outs]), "logits": torch.cat([o[0] for o in outs]),
-            "Y_prob": torch.cat([o[1] for o in outs]), "Y_hat": torch.cat([o[2] for o in outs])}
-
-
-def direct(w, bags, rows, **kw):
-    cat = Fn.as_compute(torch.cat(list(bags), dim=0), w.dtype)
-    off = Fn.BagOffsets(np.cumsum([0, *rows]), cat.shape[0], cat.device)
-    return Fn.clam_sb_forward_bags_wide(w, cat, off, **kw), cat, off
+    return U.run_form(m, "wide", bags, **kw)
 
 
 def decided(refs, bar):
@@ -119,122 +98,11 @@ def test_bf16_parity_per_bag(size):
     assert wrong == []
 
 
-# ---------------------------------------------------------------- 3. bitwise independence
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size", SMALL + [(1024, 512, 384)])
-def test_a_bag_does_not_see_its_neighbours(size, dtype, monkeypatch):
-    m = make(size, dtype)
-    bags = bags_of(size[0], 9)
-    full = run_wide(m, bags)
-    rev = run_wide(m, bags[::-1])
-    monkeypatch.setenv("HIPT_BAGS_MAX_WG", "3")     # 22 units over 3 workgroups instead of one each
-    few = run_wide(m, bags)
-    monkeypatch.delenv("HIPT_BAGS_MAX_WG")
-    B = len(bags)
-    mid = run_wide(m, [bags[(b + 1) % B] for b in range(B)])      # every bag one place earlier: the first goes last
-    for b in range(B):
-        assert_same_bits(per_bag(full, b), per_bag(run_wide(m, [bags[b]]), 0), f"bag {b} alone")
-        assert_same_bits(per_bag(full, b), per_bag(rev, B - 1 - b), f"bag {b} reversed order")
-        assert_same_bits(per_bag(full, b), per_bag(mid, (b - 1) % B), f"bag {b} shifted")
-        assert_same_bits(per_bag(full, b), per_bag(few, b), f"bag {b} small grid")
-
-
-# ---------------------------------------------------------------- 4. attention_only
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size", SMALL)
-def test_attention_only_writes_a_raw_alone(size, dtype):
-    m = make(size, dtype)
-    bags = bags_of(size[0], 9)
-    full = run_wide(m, bags)
-    m.bags_wide = True
-    try:
-        views = m.forward_bags(list(bags), attention_only=True)
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_wide
-    assert [bits(v) for v in views] == [bits(a) for a in full["A_raw"]]
-    w = m._pack(torch.device(DEV))
-    B = len(ROWS)
-    sent = lambda *shape: torch.full(shape, -7.25, dtype=torch.float32, device=DEV)
-    out = (sent(sum(ROWS)), sent(B, size[1]), sent(B, 2), sent(B, 2), torch.full((B,), -7, dtype=torch.int64, device=DEV))
-    direct(w, bags, ROWS, attention_only=True, out=out)
-    torch.cuda.synchronize()
-    assert bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-    assert all(bool((t == -7.25).all()) for t in out[1:4]) and bool((out[4] == -7).all())
-
-
-# ---------------------------------------------------------------- 5. guard bytes
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("size,rows", [((128, 256, 64), ROWS), ((128, 512, 256), ROWS), ((128, 512, 384), ROWS_PAST)])
-def test_outputs_and_workspace_stay_inside_their_buffers(size, rows, dtype):
-    m = make(size, dtype)
-    w = m._pack(torch.device(DEV))
-    bags = bags_of(size[0], 9, rows)
-    B, total, S1 = len(rows), sum(rows), size[1]
-    need = N.lib().hipt_clam_wide_bags_workspace_bytes(C.byref(w), B, total)
-    assert need > 0 and need % 256 == 0
-    fenced = []
-
-    def buf(nbytes, dt=torch.uint8):
-        raw = torch.full((nbytes + 2 * FENCE,), FILL, dtype=torch.uint8, device=DEV)
-        assert raw.data_ptr() % 256 == 0
-        fenced.append((raw, nbytes))
-        return raw[FENCE:FENCE + nbytes].view(dt)
-
-    out = (buf(total * 4, torch.float32), buf(B * S1 * 4, torch.float32).view(B, S1), buf(B * 2 * 4, torch.float32).view(B, 2),
-           buf(B * 2 * 4, torch.float32).view(B, 2), buf(B * 8, torch.int64))
-    ws = buf(need)
-    direct(w, bags, rows, out=out, ws=ws)
-    torch.cuda.synchronize()
-    for raw, n in fenced:
-        assert bool((raw[:FENCE] == FILL).all()) and bool((raw[FENCE + n:] == FILL).all()), "a write outside a buffer"
-    full = run_wide(m, bags)
-    assert bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-    assert bits(out[1]) == bits(full["M"]) and bits(out[2]) == bits(full["logits"]) and bits(out[3]) == bits(full["Y_prob"])
-    assert bits(out[4]) == bits(full["Y_hat"])
-    # the workspace carries no state: a second call on the used workspace gives the same bits
-    direct(w, bags, rows, out=out, ws=ws)
-    torch.cuda.synchronize()
-    assert bits(out[1]) == bits(full["M"]) and bits(out[0]) == b"".join(bits(a) for a in full["A_raw"])
-
-
-# ---------------------------------------------------------------- 6. graph capture
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_one_call_is_captured_and_replayed(dtype):
-    size = (128, 512, 256)
-    m = make(size, dtype)
-    static = torch.cat(bags_of(128, 9), dim=0).clone()
-    off = Fn.BagOffsets(np.cumsum([0, *ROWS]), static.shape[0], static.device)   # checked and uploaded BEFORE the capture
-    m.bags_wide = True
-    try:
-        call = lambda: m.forward_bags((static, off), return_features=True)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            call()                                    # weight image, workspace and per-device kernel setup exist before the capture
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            logits, y_prob, y_hat, a_raw, res = call()
-        assert m.bags_route == "bags"
-    finally:
-        del m.bags_wide
-    for seed in (31, 32):
-        static.copy_(torch.cat(bags_of(128, seed), dim=0))
-        g.replay()
-        torch.cuda.synchronize()
-        got = {"A_raw": torch.cat(a_raw, dim=1), "M": res["features"], "logits": logits, "Y_prob": y_prob, "Y_hat": y_hat}
-        eager = run_wide(m, bags_of(128, seed))
-        eager["A_raw"] = torch.cat(eager["A_raw"], dim=1)
-        assert_same_bits(got, eager, f"replay on seed {seed}")
-
-
-# ---------------------------------------------------------------- 7. the instance branch
+# ---------------------------------------------------------------- 3. the instance branch
 @pytest.mark.parametrize("subtyping", [False, True])
 def test_instance_branch_is_the_per_bag_chain(subtyping):
     size, k = (128, 256, 64), 8
-    m = make(size, "fp32", subtyping)
+    m = make(size, "fp32", subtyping=subtyping)
     bags = bags_of(128, 23, ROWS_I)
     labels = [b % 2 for b in range(len(ROWS_I))]
     run_wide(m, bags[:1])   # the weight image exists
@@ -259,9 +127,9 @@ def test_instance_branch_is_the_per_bag_chain(subtyping):
         assert abs(float(res["instance_loss"][b]) - want) <= 1e-6 * abs(want), (b, float(res["instance_loss"][b]), want)
 
 
-# ---------------------------------------------------------------- 8. the split functions
+# ---------------------------------------------------------------- 4. the split functions
 def test_split_functions_on_the_device():
-    m = make((128, 256, 64), "fp32", True)
+    m = make((128, 256, 64), "fp32", subtyping=True)
     bags = bags_of(128, 23, ROWS_I)
     labels = [b % 2 for b in range(len(ROWS_I))]
     e1 = evaluate_split(m, bags, labels, 2, max_rows_per_call=1 << 16, wide_one_call=True)
@@ -287,15 +155,24 @@ def test_split_functions_on_the_device():
     assert np.array_equal(e1.all_preds, e0.all_preds)
 
 
-# ---------------------------------------------------------------- 9. default behaviour
-def test_default_forward_bags_still_loops_with_the_bits_of_forward():
-    m = make((128, 256, 64))
-    assert CLAM_SB.bags_wide is False and "bags_wide" not in m.__dict__
-    bags = bags_of(128, 13, (1, 129, 300))
-    logits, y_prob, y_hat, a_raw, res = m.forward_bags(list(bags), return_features=True)
-    assert m.bags_route == "per_bag"
-    for b, bag in enumerate(bags):
-        with torch.no_grad():
-            l1, p1, h1, a1, r1 = m(bag, return_features=True)
-        assert bits(logits[b:b + 1]) == bits(l1) and bits(y_prob[b:b + 1]) == bits(p1) and bits(y_hat[b:b + 1]) == bits(h1)
-        assert bits(a_raw[b]) == bits(a1) and bits(res["features"][b]) == bits(r1["features"].reshape(res["features"][b].shape))
+# ---------------------------------------------------------------- the checks every form shares (clam_bags_util), on this form's cases
+ROWS_PAST = (129, 64, 257)                                  # the call's last bag ends one row past a unit
+SMALL = [(128, 256, 64), (128, 512, 256)]
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("size", SMALL + [(1024, 512, 384)])
+def test_a_bag_does_not_see_its_neighbours(size, dtype, monkeypatch):
+    U.check_neighbours("wide", size, 2, dtype, monkeypatch)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("size", SMALL)
+def test_attention_only_writes_a_raw_alone(size, dtype):
+    U.check_attention_only("wide", size, 2, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("size,rows", [((128, 256, 64), ROWS), ((128, 512, 256), ROWS), ((128, 512, 384), ROWS_PAST)])
+def test_outputs_and_workspace_stay_inside_their_buffers(size, rows, dtype):
+    U.check_fences("wide", size, 2, dtype, rows)
