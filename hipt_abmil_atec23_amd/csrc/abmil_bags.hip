@@ -655,14 +655,9 @@ int launch_bags(const hipt_clam_weights* w, const void* bags, const void* units,
                 float* partials, hipStream_t st) {
     using G = AG<T, S1, S2>;
     constexpr int LDS = G::LDS + (sizeof(T) == 2 ? TM * S1 * 4 : 0);  // bf16: + the fp32 h1 image of the pooling (<= 130 KiB of the CU's 160)
-    const int grid = tile_pass_grid(max_units);
-    auto k = abmil_bags_kernel<T, S1, S2>;
-    static DeviceSetup setup;
-    if (int rc = setup({(const void*)k}, LDS, "abmil_bags")) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, st, (const T*)bags, (const BagUnit*)units, max_units, w->s0,
-                       (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc, w->bc, A_raw, partials, attention_only);
-    HIPT_CHECK_LAUNCH();
-    return HIPT_OK;
+    return launch_tile_pass<abmil_bags_kernel<T, S1, S2>>(LDS, "abmil_bags", max_units, st, (const T*)bags, (const BagUnit*)units,
+                                                          max_units, w->s0, (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc,
+                                                          w->bc, A_raw, partials, attention_only);
 }
 
 template <typename T, int S1, int S2>
@@ -670,15 +665,9 @@ int launch_bags_mb(const hipt_clam_weights* w, const void* bags, const void* uni
                    int64_t a_stride, float* A_raw, float* partials, hipStream_t st) {
     using G = AG<T, S1, S2>;
     constexpr int LDS = G::LDS_MB + (sizeof(T) == 2 ? TM * S1 * 4 : 0);  // bf16: + the fp32 h1 image of the pooling (<= 135 KiB of the CU's 160)
-    const int grid = tile_pass_grid(max_units);
-    auto k = abmil_bags_mb_kernel<T, S1, S2>;
-    static DeviceSetup setup;
-    if (int rc = setup({(const void*)k}, LDS, "abmil_bags_mb")) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, st, (const T*)bags, (const BagUnit*)units, max_units, w->s0,
-                       (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc, w->bc, w->n_att, a_stride, A_raw, partials,
-                       attention_only);
-    HIPT_CHECK_LAUNCH();
-    return HIPT_OK;
+    return launch_tile_pass<abmil_bags_mb_kernel<T, S1, S2>>(LDS, "abmil_bags_mb", max_units, st, (const T*)bags, (const BagUnit*)units,
+                                                             max_units, w->s0, (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc,
+                                                             w->bc, w->n_att, a_stride, A_raw, partials, attention_only);
 }
 
 }  // namespace

@@ -12,6 +12,9 @@
 // Ps[k][0] + Ps[k][1] + bc[k], the mb / cf order of the pooling MFMAs.  Hence branch k of a K-branch call has the bits of the same branch
 // in a call of the K <= 4 kernel on a model made of a subset of the branches (tests/test_gpu_clam_mb_many.py holds this).
 // No atomics, no tickets, no state between calls: the call can be captured in a graph.
+// Shared with abmil_bags.hip as code (abmil_tile.h): AG, Lanes, h1_off, store_partial and the launcher.  Still a written-out copy of
+// abmil_bags_mb_kernel's text: everything "once per unit" above and the pooling.  Either kernel's text behind a function boundary
+// compiles to other device code, so one body for the pair was not kept (DESIGN.md sections 16 item 2 and 34).
 #include "abmil_tile.h"
 #include "common.h"
 #include "kernels.h"
@@ -275,15 +278,9 @@ template <typename T, int S1, int S2>
 int launch_bags_mb8(const hipt_clam_weights* w, const void* bags, const void* units, int max_units, int attention_only,
                     int64_t a_stride, float* A_raw, float* partials, hipStream_t st) {
     constexpr int LDS = AG8<T, S1, S2>::LDS_ALL;  // bf16: with the fp32 h1 image of the pooling (<= 143 424 B of the CU's 163 840)
-    const int grid = tile_pass_grid(max_units);
-    auto k = abmil_bags_mb8_kernel<T, S1, S2>;
-    static DeviceSetup setup;
-    if (int rc = setup({(const void*)k}, LDS, "abmil_bags_mb8")) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, st, (const T*)bags, (const BagUnit*)units, max_units, w->s0,
-                       (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc, w->bc, w->n_att, a_stride, A_raw, partials,
-                       attention_only);
-    HIPT_CHECK_LAUNCH();
-    return HIPT_OK;
+    return launch_tile_pass<abmil_bags_mb8_kernel<T, S1, S2>>(LDS, "abmil_bags_mb8", max_units, st, (const T*)bags, (const BagUnit*)units,
+                                                              max_units, w->s0, (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc,
+                                                              w->bc, w->n_att, a_stride, A_raw, partials, attention_only);
 }
 
 }  // namespace

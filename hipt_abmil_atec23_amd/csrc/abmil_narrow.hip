@@ -208,15 +208,9 @@ __global__ __launch_bounds__(256, 2) void abmil_narrow_kernel(const T* __restric
 template <typename T, int S1, int S2>
 int launch_narrow(const hipt_clam_weights* w, const void* bags, const void* units, int max_units, int attention_only, float* A_raw,
                   float* partials, hipStream_t st) {
-    using G = NG<T, S1, S2>;
-    const int grid = tile_pass_grid(max_units);
-    auto k = abmil_narrow_kernel<T, S1, S2>;
-    static DeviceSetup setup;
-    if (int rc = setup({(const void*)k}, G::LDS, "abmil_narrow")) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), G::LDS, st, (const T*)bags, (const BagUnit*)units, max_units, w->s0,
-                       (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc, w->bc, A_raw, partials, attention_only);
-    HIPT_CHECK_LAUNCH();
-    return HIPT_OK;
+    return launch_tile_pass<abmil_narrow_kernel<T, S1, S2>>(NG<T, S1, S2>::LDS, "abmil_narrow", max_units, st, (const T*)bags,
+                                                            (const BagUnit*)units, max_units, w->s0, (const T*)w->w1, w->b1,
+                                                            (const T*)w->wab, w->bab, w->wc, w->bc, A_raw, partials, attention_only);
 }
 
 }  // namespace

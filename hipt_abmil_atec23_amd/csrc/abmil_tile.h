@@ -1,13 +1,17 @@
 // What the single-bag kernel (abmil.hip) and the ragged multi-bag kernel (abmil_bags.hip) of the fused CLAM_SB / ABMIL row tile share:
 // tile height, LDS budget and carve of one [T, S1, S2] instantiation, lane geometry, the swizzled h1 image,
 // tile_max and store_partial, bag_head (the tail of both combine kernels) and the one table of supported
-// widths (visit_width); and, of the multi-bag tile passes (abmil_bags.hip, abmil_narrow.hip), the unit record and the grid.  The GEMM phases and the fp32 pooling are still written out in both kernels: lifted into functions here they
-// compiled to different, slower code.  The gate's sigmoid_f / tanh_f and the shuffle reductions (wave_*, quad_sum)
+// widths (visit_width); and, of the multi-bag tile passes (abmil_bags.hip, abmil_bags_mb8.hip, abmil_narrow.hip, abmil_wide.hip,
+// abmil_wide_mb.hip), the unit record, the grid, the one launcher (launch_tile_pass) and the wide pair's geometry (WG).  The GEMM
+// phases, the gate and the pooling are still written out in every tile kernel, the sibling pairs abmil_wide / abmil_wide_mb and
+// abmil_bags_mb / abmil_bags_mb8 included: a tile's statements behind a function boundary -- lifted phase by phase, or the whole unit
+// loop as one body that each kernel calls -- compile to other device code.  The gate's sigmoid_f / tanh_f and the shuffle reductions (wave_*, quad_sum)
 // are common.h's: the training step (clam_train.hip) recomputes the gate with the same two functions.
 #pragma once
 #include <cstdlib>
 
 #include "common.h"
+#include "launch.h"
 
 namespace abmil_tile {
 
@@ -43,6 +47,29 @@ template <typename T, int S1, int S2> struct AG {
     static __device__ __forceinline__ char* h32_mb(char* s) { return s + LDS_MB; }
 };
 
+// Geometry of the WIDE tile passes (abmil_wide.hip, abmil_wide_mb.hip): a 128-row unit walked as sub-tiles of R rows, the phase-1 ring,
+// the h1 image and the ring of the gate passes.  Each kernel's geometry derives from it and adds its own LDS carve behind AREA.
+template <typename T, int S1, int S2> struct WG {
+    static constexpr int KB = Tr<T>::KB;
+    static constexpr int R = 128 / (int)sizeof(T);     // rows of a sub-tile
+    static constexpr int NSUB = TM / R;                // sub-tiles of a unit
+    static constexpr int NI = R / 16;                  // row fragments, all in every wave
+    static constexpr int NJ1 = S1 / 64;                // column fragments per wave, phase 1
+    static constexpr int NSLAB = S1 / KB;              // 128-byte slabs of the h1 image
+    static constexpr int NXQ = R / 32;                 // LDS-DMA instructions per wave for the X rows of one K-slab
+    static constexpr int NWQ = S1 / 32;                // ... for the W1 rows
+    static constexpr int STAGE = (R + S1) * 128;
+    static constexpr int H1_BYTES = NSLAB * R * 128;   // = S1 * 128
+    static constexpr int NP = 2 * S2 < 256 ? 2 * S2 : 256;  // packed gate rows per pass
+    static constexpr int NPASS = (2 * S2) / NP;
+    static constexpr int NJ2 = NP / 64;                // gate column fragments per wave
+    static constexpr int NGQ = NP / 32;                // LDS-DMA instructions per wave for one [Wa; Wb] slab of a pass
+    static constexpr int GSTAGE = NP * 128;
+    static constexpr int AREA = 2 * STAGE > H1_BYTES + 2 * GSTAGE ? 2 * STAGE : H1_BYTES + 2 * GSTAGE;
+    static_assert(S1 % 64 == 0 && S1 % KB == 0, "wide ABMIL: S1 a multiple of 64");
+    static_assert((2 * S2) % NP == 0 && NP % 64 == 0, "wide ABMIL: 2 * S2 a multiple of the pass width");
+};
+
 // lane geometry of the 256-thread tile kernels, built once per kernel
 struct Lanes {
     int tid, lane, wave, wm, wn, g, li;
@@ -59,11 +86,11 @@ struct Lanes {
     }
 };
 
-// byte offset of element (row, col) inside the slab-major, swizzled A-operand image of h1
-template <typename T> __device__ __forceinline__ int h1_off(int row, int col) {
+// byte offset of element (row, col) inside the slab-major, swizzled A-operand image of a ROWS-row tile's h1 (the wide passes: a sub-tile)
+template <typename T, int ROWS = TM> __device__ __forceinline__ int h1_off(int row, int col) {
     constexpr int KB = Tr<T>::KB, EPC = Tr<T>::EPC;
     const int slab = col / KB, c = (col % KB) / EPC, sub = (col % EPC) * (int)sizeof(T);
-    return slab * (TM * 128) + row * 128 + ((c ^ ((row >> 1) & 7)) << 4) + sub;
+    return slab * (ROWS * 128) + row * 128 + ((c ^ ((row >> 1) & 7)) << 4) + sub;
 }
 
 // The tile's largest score, in every thread (finite: a tile has >= 1 valid row).  Its barrier also publishes As to the pooling.
@@ -177,6 +204,17 @@ inline int tile_pass_grid(int max_units) {
         if (v >= 1 && v < cap) cap = v;
     }
     return max_units < cap ? max_units : cap;
+}
+
+// The launch of every tile pass: the grid over max_units, this kernel instantiation's per-device setup (the dynamic-LDS opt-in, under
+// the family name the error texts carry), 256 threads.  `args` are the kernel's arguments.
+template <auto Kernel, typename... Args>
+int launch_tile_pass(int lds, const char* family, int max_units, hipStream_t st, Args... args) {
+    static DeviceSetup setup;  // one per kernel instantiation
+    if (int rc = setup({(const void*)Kernel}, lds, family)) return rc;
+    hipLaunchKernelGGL(Kernel, dim3(tile_pass_grid(max_units)), dim3(256), lds, st, args...);
+    HIPT_CHECK_LAUNCH();
+    return HIPT_OK;
 }
 
 }  // namespace abmil_tile

@@ -26,35 +26,12 @@
 namespace {
 using namespace abmil_tile;
 
-template <typename T, int S1, int S2> struct WGm {
-    static constexpr int KB = Tr<T>::KB;
-    static constexpr int R = 128 / (int)sizeof(T);     // rows of a sub-tile
-    static constexpr int NSUB = TM / R;                // sub-tiles of a unit
-    static constexpr int NI = R / 16;                  // row fragments, all in every wave
-    static constexpr int NJ1 = S1 / 64;                // column fragments per wave, phase 1
-    static constexpr int NSLAB = S1 / KB;              // 128-byte slabs of the h1 image
-    static constexpr int NXQ = R / 32;                 // LDS-DMA instructions per wave for the X rows of one K-slab
-    static constexpr int NWQ = S1 / 32;                // ... for the W1 rows
-    static constexpr int STAGE = (R + S1) * 128;
-    static constexpr int H1_BYTES = NSLAB * R * 128;   // = S1 * 128
-    static constexpr int NP = 2 * S2 < 256 ? 2 * S2 : 256;  // packed gate rows per pass
-    static constexpr int NPASS = (2 * S2) / NP;
-    static constexpr int NJ2 = NP / 64;                // gate column fragments per wave
-    static constexpr int NGQ = NP / 32;                // LDS-DMA instructions per wave for one [Wa; Wb] slab of a pass
-    static constexpr int GSTAGE = NP * 128;
-    static constexpr int AREA = 2 * STAGE > H1_BYTES + 2 * GSTAGE ? 2 * STAGE : H1_BYTES + 2 * GSTAGE;
-    static constexpr int LDS = AREA + (R + 4 * R) * 4;  // + A_raw[R], gate sums [4][R]
-    static_assert(S1 % 64 == 0 && S1 % KB == 0, "wide ABMIL: S1 a multiple of 64");
-    static_assert((2 * S2) % NP == 0 && NP % 64 == 0, "wide ABMIL: 2 * S2 a multiple of the pass width");
+// abmil_tile.h's wide geometry, and behind its AREA this kernel's carve: A_raw[R], gate sums [4][R]
+template <typename T, int S1, int S2> struct WGm : WG<T, S1, S2> {
+    using G = WG<T, S1, S2>;
+    static constexpr int LDS = G::AREA + (G::R + 4 * G::R) * 4;
     static_assert(LDS <= 160 * 1024, "wide ABMIL: LDS");
 };
-
-// byte offset of element (row, col) inside the slab-major, swizzled operand image of an R-row sub-tile's h1
-template <typename T, int R> __device__ __forceinline__ int h1w_off(int row, int col) {
-    constexpr int KB = Tr<T>::KB, EPC = Tr<T>::EPC;
-    const int slab = col / KB, c = (col % KB) / EPC, sub = (col % EPC) * (int)sizeof(T);
-    return slab * (R * 128) + row * 128 + ((c ^ ((row >> 1) & 7)) << 4) + sub;
-}
 
 template <typename T, int S1, int S2>
 __global__ __launch_bounds__(256) void abmil_wide_kernel(const T* __restrict__ bag, const BagUnit* __restrict__ units, int max_units,
@@ -166,7 +143,7 @@ __global__ __launch_bounds__(256) void abmil_wide_kernel(const T* __restrict__ b
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                     acc1[i][j] = v;
-                    store4<T>((T*)(H1s + h1w_off<T, R>(row, col)), v);
+                    store4<T>((T*)(H1s + h1_off<T, R>(row, col)), v);
                 }
             }
             wait_vm0();
@@ -282,15 +259,9 @@ __global__ __launch_bounds__(256) void abmil_wide_kernel(const T* __restrict__ b
 template <typename T, int S1, int S2>
 int launch_wide(const hipt_clam_weights* w, const void* bags, const void* units, int max_units, int attention_only, float* A_raw,
                 float* partials, hipStream_t st) {
-    using G = WGm<T, S1, S2>;
-    const int grid = tile_pass_grid(max_units);
-    auto k = abmil_wide_kernel<T, S1, S2>;
-    static DeviceSetup setup;
-    if (int rc = setup({(const void*)k}, G::LDS, "abmil_wide")) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), G::LDS, st, (const T*)bags, (const BagUnit*)units, max_units, w->s0,
-                       (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc, w->bc, A_raw, partials, attention_only);
-    HIPT_CHECK_LAUNCH();
-    return HIPT_OK;
+    return launch_tile_pass<abmil_wide_kernel<T, S1, S2>>(WGm<T, S1, S2>::LDS, "abmil_wide", max_units, st, (const T*)bags,
+                                                          (const BagUnit*)units, max_units, w->s0, (const T*)w->w1, w->b1,
+                                                          (const T*)w->wab, w->bab, w->wc, w->bc, A_raw, partials, attention_only);
 }
 
 }  // namespace

@@ -16,6 +16,9 @@
 // Rounding model, per branch that of abmil_wide.hip: bf16 bag, W1, Wa, Wb; h1 rounded to bf16 as the gate GEMM's operand only; the gate,
 // the K scores and the K poolings fp32 on unrounded h1.  fp32: nothing is rounded.
 // A unit's result does not depend on the workgroup that ran it: no atomics, no tickets, nothing kept in the workspace.
+// Shared with abmil_wide.hip as code (abmil_tile.h): the geometry WG, h1_off<T, R> and the launcher.  Still a written-out copy of that
+// file's text: the unit loop up to acc2 (row addresses and stage, the phase-1 ring, stage_g, the ReLU / h1 image, the gate GEMM passes).
+// One body for both kernels changed the device code of all 12 instantiations and was put back (DESIGN.md sections 16 item 2 and 33).
 #include "abmil_tile.h"
 #include "common.h"
 #include "kernels.h"
@@ -26,38 +29,14 @@ using namespace abmil_tile;
 
 constexpr int KMAX = 4;  // attention branches a workgroup's LDS holds running records for
 
-// abmil_wide.hip's geometry (a copy: that file's instantiations keep their code), and behind its AREA the K-fold carve
-template <typename T, int S1, int S2> struct WGk {
-    static constexpr int KB = Tr<T>::KB;
-    static constexpr int R = 128 / (int)sizeof(T);     // rows of a sub-tile
-    static constexpr int NSUB = TM / R;                // sub-tiles of a unit
-    static constexpr int NI = R / 16;                  // row fragments, all in every wave
-    static constexpr int NJ1 = S1 / 64;                // column fragments per wave, phase 1
-    static constexpr int NSLAB = S1 / KB;              // 128-byte slabs of the h1 image
-    static constexpr int NXQ = R / 32;                 // LDS-DMA instructions per wave for the X rows of one K-slab
-    static constexpr int NWQ = S1 / 32;                // ... for the W1 rows
-    static constexpr int STAGE = (R + S1) * 128;
-    static constexpr int H1_BYTES = NSLAB * R * 128;   // = S1 * 128
-    static constexpr int NP = 2 * S2 < 256 ? 2 * S2 : 256;  // packed gate rows per pass
-    static constexpr int NPASS = (2 * S2) / NP;
-    static constexpr int NJ2 = NP / 64;                // gate column fragments per wave
-    static constexpr int NGQ = NP / 32;                // LDS-DMA instructions per wave for one [Wa; Wb] slab of a pass
-    static constexpr int GSTAGE = NP * 128;
-    static constexpr int AREA = 2 * STAGE > H1_BYTES + 2 * GSTAGE ? 2 * STAGE : H1_BYTES + 2 * GSTAGE;
-    // + A_raw[KMAX][R], gate sums [KMAX][4][R], running acc [KMAX][S1], running (m, l) [4 waves][KMAX][2]
-    static constexpr int LDS = AREA + KMAX * (R + 4 * R) * 4 + KMAX * S1 * 4 + 4 * KMAX * 2 * 4;
-    static_assert(S1 % 64 == 0 && S1 % KB == 0, "wide ABMIL: S1 a multiple of 64");
-    static_assert((2 * S2) % NP == 0 && NP % 64 == 0, "wide ABMIL: 2 * S2 a multiple of the pass width");
-    static_assert(KMAX * R <= 256, "wide ABMIL MB: one thread per (branch, row)");
+// abmil_tile.h's wide geometry, and behind its AREA the K-fold carve: A_raw[KMAX][R], gate sums [KMAX][4][R], running acc [KMAX][S1],
+// running (m, l) [4 waves][KMAX][2]
+template <typename T, int S1, int S2> struct WGk : WG<T, S1, S2> {
+    using G = WG<T, S1, S2>;
+    static constexpr int LDS = G::AREA + KMAX * (G::R + 4 * G::R) * 4 + KMAX * S1 * 4 + 4 * KMAX * 2 * 4;
+    static_assert(KMAX * G::R <= 256, "wide ABMIL MB: one thread per (branch, row)");
     static_assert(LDS <= 160 * 1024, "wide ABMIL MB: LDS");
 };
-
-// byte offset of element (row, col) inside the slab-major, swizzled operand image of an R-row sub-tile's h1
-template <typename T, int R> __device__ __forceinline__ int h1k_off(int row, int col) {
-    constexpr int KB = Tr<T>::KB, EPC = Tr<T>::EPC;
-    const int slab = col / KB, c = (col % KB) / EPC, sub = (col % EPC) * (int)sizeof(T);
-    return slab * (R * 128) + row * 128 + ((c ^ ((row >> 1) & 7)) << 4) + sub;
-}
 
 template <typename T, int S1, int S2>
 __global__ __launch_bounds__(256) void abmil_wide_mb_kernel(const T* __restrict__ bag, const BagUnit* __restrict__ units, int max_units,
@@ -185,7 +164,7 @@ __global__ __launch_bounds__(256) void abmil_wide_mb_kernel(const T* __restrict_
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                     acc1[i][j] = v;
-                    store4<T>((T*)(H1s + h1k_off<T, R>(row, col)), v);
+                    store4<T>((T*)(H1s + h1_off<T, R>(row, col)), v);
                 }
             }
             wait_vm0();
@@ -337,16 +316,10 @@ __global__ __launch_bounds__(256) void abmil_wide_mb_kernel(const T* __restrict_
 template <typename T, int S1, int S2>
 int launch_wide_mb(const hipt_clam_weights* w, const void* bags, const void* units, int max_units, int attention_only, int64_t a_stride,
                    float* A_raw, float* partials, hipStream_t st) {
-    using G = WGk<T, S1, S2>;
-    const int grid = tile_pass_grid(max_units);
-    auto k = abmil_wide_mb_kernel<T, S1, S2>;
-    static DeviceSetup setup;
-    if (int rc = setup({(const void*)k}, G::LDS, "abmil_wide_mb")) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), G::LDS, st, (const T*)bags, (const BagUnit*)units, max_units, w->s0,
-                       (const T*)w->w1, w->b1, (const T*)w->wab, w->bab, w->wc, w->bc, w->n_att, a_stride, A_raw, partials,
-                       attention_only);
-    HIPT_CHECK_LAUNCH();
-    return HIPT_OK;
+    return launch_tile_pass<abmil_wide_mb_kernel<T, S1, S2>>(WGk<T, S1, S2>::LDS, "abmil_wide_mb", max_units, st, (const T*)bags,
+                                                             (const BagUnit*)units, max_units, w->s0, (const T*)w->w1, w->b1,
+                                                             (const T*)w->wab, w->bab, w->wc, w->bc, w->n_att, a_stride, A_raw,
+                                                             partials, attention_only);
 }
 
 }  // namespace
