@@ -122,22 +122,8 @@ class _HostFeed:
         self.stage = [None] * self.SLOTS     # pinned staging twins (allocated only when a pageable batch arrives)
         self.free = [None] * self.SLOTS      # event: the call that read buf[s] has finished
         self.staged = [None] * self.SLOTS    # event: the last copy out of stage[s] has completed
-        self.slot = 0
-        self.fill = 0
-        self.read_stream = torch.cuda.Stream(device=device, priority=-1)  # features come back on their own stream, behind THEIR call only
-        self._hbuf = None
-
-    def read_back(self, feats: torch.Tensor, done: "torch.cuda.Event") -> torch.Tensor:
-        """features of a finished call as a host tensor, without waiting for anything enqueued after that call (a `.cpu()` on the compute
-        stream would wait for the NEXT call too, and the host could not feed the one after it meanwhile)"""
-        if self._hbuf is None or self._hbuf.shape[1:] != feats.shape[1:] or self._hbuf.shape[0] < feats.shape[0] or self._hbuf.dtype != feats.dtype:
-            self._hbuf = torch.empty((max(feats.shape[0], 8),) + tuple(feats.shape[1:]), dtype=feats.dtype, pin_memory=True)
-        self.read_stream.wait_event(done)
-        with torch.cuda.stream(self.read_stream):
-            self._hbuf[:feats.shape[0]].copy_(feats, non_blocking=True)
-        feats.record_stream(self.read_stream)
-        self.read_stream.synchronize()
-        return self._hbuf[:feats.shape[0]].clone()
+        self.slot = self.fill = 0
+        self.stage_waited = False            # the open gather has waited for staged[slot]
 
     def begin(self, cap: int, like: torch.Tensor):
         """start gathering up to `cap` regions shaped like `like` ([r, ...]) into the current slot"""
@@ -151,7 +137,7 @@ class _HostFeed:
             self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))
         if self.free[s] is not None:
             self.copy_stream.wait_event(self.free[s])  # the compute that read this buffer two calls ago
-        self.fill = 0
+        self.fill, self.stage_waited = 0, False
 
     def add(self, r: torch.Tensor):
         s, o, n = self.slot, self.fill, r.shape[0]
@@ -160,33 +146,113 @@ class _HostFeed:
         if not r.is_pinned():
             if self.stage[s] is None:
                 self.stage[s] = torch.empty(self.buf[s].shape, dtype=self.buf[s].dtype, pin_memory=True)
-            if self.staged[s] is not None and o == 0:
+            if self.staged[s] is not None and not self.stage_waited:  # the FIRST pageable batch of this gather, at whatever offset
                 self.staged[s].synchronize()  # (long complete: its call has been launched and usually finished)
+            self.stage_waited = True
             src = self.stage[s][o:o + n]
             src.copy_(r)  # host memcpy: pageable -> pinned
         with torch.cuda.stream(self.copy_stream):
             dst.copy_(src, non_blocking=True)
         self.fill = o + n
 
-    def capacity(self) -> int:
-        return 0 if self.buf[self.slot] is None else self.buf[self.slot].shape[0]
-
-    def finish(self):
-        """(the gathered regions as a device tensor the CURRENT stream may read, its slot); switches to the other slot"""
-        s = self.slot
-        ev = torch.cuda.Event()
+    def finish(self) -> torch.Tensor:
+        """the gathered regions as a device tensor the CURRENT stream may read"""
+        self.staged[self.slot] = ev = torch.cuda.Event()
         ev.record(self.copy_stream)
-        self.staged[s] = ev
         torch.cuda.current_stream(self.device).wait_event(ev)
-        out = self.buf[s][:self.fill]
-        self.slot = (s + 1) % self.SLOTS
-        return out, s
+        return self.buf[self.slot][:self.fill]
 
-    def release(self, s: int):
-        """the call that read slot s has been enqueued on the current stream"""
-        ev = torch.cuda.Event()
+    def release(self):
+        """the call that read the finished gather has been enqueued on the current stream; the next gather takes the other slot"""
+        self.free[self.slot] = ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
-        self.free[s] = ev
+        self.slot = (self.slot + 1) % self.SLOTS
+
+
+class _ResidentFeed:
+    """The same four calls for loader batches that already lie where ``model`` reads them (and for any model that is not on a HIP device): a
+    lone batch passes through as the tensor it is; several are gathered in ONE buffer, each loader batch dropped as soon as it is copied --
+    the peak is the gathered batch plus one loader batch (8 fp32 4096 x 4096 regions: 1.6 GB + 0.2 GB), not two copies of everything."""
+
+    def begin(self, cap: int, like: torch.Tensor):
+        self.parts = []
+
+    def add(self, r: torch.Tensor):
+        self.parts.append(r)
+
+    def finish(self) -> torch.Tensor:
+        parts, self.parts = self.parts, None
+        if len(parts) == 1:
+            return parts.pop()
+        out = torch.empty((sum(r.shape[0] for r in parts),) + tuple(parts[0].shape[1:]), dtype=parts[0].dtype, device=parts[0].device)
+        o = 0
+        while parts:
+            r = parts.pop(0)
+            out[o:o + r.shape[0]].copy_(r)
+            o += r.shape[0]
+        return out
+
+    def release(self):
+        pass
+
+
+class _ReadBack:
+    """Features of a finished call as a host tensor, without waiting for anything enqueued after that call (a `.cpu()` on the compute stream
+    would wait for the NEXT call too, and the host could not feed the one after it meanwhile).  Everything is taken from the tensor it is
+    given: the copy runs on a high-priority read stream of ``feats.device`` (one per device seen), behind ``done`` -- an event the caller
+    recorded on THAT device's current stream once the call was enqueued -- so a model whose two ViTs sit on two devices needs no special case."""
+
+    def __init__(self):
+        self.streams = {}
+        self.hbuf = None
+
+    def __call__(self, outs: list, done: "torch.cuda.Event") -> list:
+        return [self.one(feats, done) for feats in outs]
+
+    def one(self, feats: torch.Tensor, done: "torch.cuda.Event") -> torch.Tensor:
+        n = feats.shape[0]
+        if self.hbuf is None or self.hbuf.shape[1:] != feats.shape[1:] or self.hbuf.shape[0] < n or self.hbuf.dtype != feats.dtype:
+            self.hbuf = torch.empty((max(n, 8),) + tuple(feats.shape[1:]), dtype=feats.dtype, pin_memory=True)
+        if feats.device not in self.streams:
+            self.streams[feats.device] = torch.cuda.Stream(device=feats.device, priority=-1)
+        rs = self.streams[feats.device]
+        rs.wait_event(done)
+        with torch.cuda.stream(rs):
+            self.hbuf[:n].copy_(feats, non_blocking=True)
+        feats.record_stream(rs)
+        rs.synchronize()
+        return self.hbuf[:n].clone()
+
+
+class _CallPlan:
+    """Which loader batches share a model call -- by their facts alone (no tensor, no device): ``add`` takes a batch's key
+    ``(shape[1:], dtype, device)``, its region count, whether its shape is gathered (``gathers_bit_exactly``) and whether it is fed from the
+    host to a HIP device, and answers (close the open call BEFORE this batch?, close it AFTER?).  Loader batches are never split."""
+
+    def __init__(self, coalesce: int):
+        self.coalesce = coalesce
+        self.calls = 0   # closed so far
+        self.n = 0       # regions in the open call (0: none open)
+        self.key = None
+        self.cap = 0     # what the open call's gather may hold
+
+    def add(self, key, n: int, gatherable: bool, host_fed: bool):
+        # a different shape / type / device cannot share a call, nor a host-fed batch that would overrun the open gather (a large one behind small ones)
+        before = self.n > 0 and (key != self.key or (host_fed and self.n + n > self.cap))
+        if before:
+            self.calls, self.n = self.calls + 1, 0
+        gathers = self.coalesce > 1 and gatherable
+        if self.n == 0:
+            # capacity: what a gathered call reaches with loader batches of this size, so that ragged tails re-use the host feed's buffer
+            self.key, self.cap = key, (self.coalesce + n - 1 if gathers else n)
+        self.n += n
+        # host-fed: the FIRST call of a slide is a short one -- a quarter of `coalesce` -- so that the GPU starts behind 2 regions' copies instead
+        # of 8; nothing hides the first call's copy, every later one lands under the call before it
+        want = max(1, self.coalesce // 4) if (host_fed and self.calls == 0) else self.coalesce
+        after = not gathers or self.n >= want
+        if after:
+            self.calls, self.n = self.calls + 1, 0
+        return before, after
 
 
 def extract_slide(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], feat_dir: str, slide_id: str, coalesce: int = 8) -> str:
@@ -299,115 +365,79 @@ def _is_resnet(model) -> bool:
     return isinstance(model, (ResNet_Baseline, ResNet18_Baseline))
 
 
+def gathers_bit_exactly(regions: torch.Tensor, is_resnet: bool) -> bool:
+    """whole 16-row fragments in every call (patch count a multiple of 16): the gathered call and the one-by-one call take the same kernels
+    and write the same bits; other region sizes are NOT gathered (they would agree to the bf16 bar only)"""
+    if is_resnet:
+        return True  # every output row of hipt_resnet_forward depends on its own patch only, whatever the batch
+    if regions.dim() != 4:
+        return False
+    hw = regions.shape[2:] if regions.shape[1] == 3 else regions.shape[1:3]  # planar [R,3,W,H] or interleaved [R,W,H,3]
+    return ((hw[0] // 256) * (hw[1] // 256)) % 16 == 0
+
+
+def _fed_calls(batches, plan: _CallPlan, dev: Optional[torch.device], resnet: bool):
+    """Feeds the loader's batches to where the model reads them AS THEY ARRIVE and yields ``(feed, held)`` each time the plan closes a
+    call: the feed whose ``finish()`` is the call's regions, and the ``(coords, count)`` of its loader batches."""
+    resident, host = _ResidentFeed(), None  # (the _HostFeed is made when the first host batch for a HIP model arrives)
+    feed, held = None, []
+    for regions, coords in batches:
+        host_fed = dev is not None and dev.type == "cuda" and regions.device.type == "cpu"
+        before, after = plan.add((tuple(regions.shape[1:]), regions.dtype, regions.device), regions.shape[0],
+                                 gathers_bit_exactly(regions, resnet), host_fed)
+        if before:
+            yield feed, held
+            held = []
+        if not held:
+            if host_fed and host is None:
+                host = _HostFeed(dev)
+            feed = host if host_fed else resident
+            feed.begin(plan.cap, regions)
+        feed.add(regions)  # (a host batch's copy starts NOW)
+        held.append((coords, regions.shape[0]))
+        if after:
+            yield feed, held
+            held = []
+    if held:
+        yield feed, held
+
+
+def _append_call(writers, held, outs) -> None:
+    for w, feats in zip(writers, outs):
+        o = 0
+        for coords, n in held:  # one append per loader batch, as the reference's loop does
+            w.append(feats[o:o + n], coords)
+            o += n
+
+
 def _extract(model, batches, writers, run, coalesce: int) -> list:
     """the loop of ``extract_slide``; ``run(regions, first)`` -> one feature tensor per writer for a call whose regions are
-    regions ``first, first+1, ...`` of the slide (in loader order)"""
-    done_regions = [0]
-    held: list = []  # (regions or None when already staged into the host feed's gather buffer, coords, count) waiting for company
-    shape_key = [None]
-    ncalls = [0]
-    m256 = getattr(model, "model256", None)  # HIPT_4K: where its first-level ViT's weights live NOW (.to() may have moved it since construction)
-    dev = getattr(m256, "weight_device", None) if m256 is not None else None
+    regions ``first, first+1, ...`` of the slide (in loader order).  Three owners: ``_CallPlan`` says which loader batches share a call,
+    a feed (``_ResidentFeed`` / ``_HostFeed``) brings them to the device, ``_ReadBack`` brings a host-fed call's features home one call late."""
     resnet = _is_resnet(model)
-    if resnet:
-        dev = model.weight_device
-    dev = torch.device(dev) if dev is not None else None
-    feed = [None]        # _HostFeed, made when the first host batch for a HIP model arrives
-    pending: list = []   # [(features on the device, counts, coords)]: read back one call late
-
-    def append_call(outs, counts, coords, done=None):
-        for w, feats in zip(writers, outs):
-            if done is not None:
-                feats = feed[0].read_back(feats, done)
-            o = 0
-            for n, c in zip(counts, coords):  # one append per loader batch, as the reference's loop does
-                w.append(feats[o:o + n], c)
-                o += n
-
-    def drain():
-        while pending:
-            append_call(*pending.pop(0))
-
-    def flush():
-        if not held:
-            return
-        counts, coords = [n for _, _, n in held], [c for _, c, _ in held]
-        staged = held[0][0] is None  # host batches: already on their way into the open gather buffer (stage())
-        slot = None
-        if staged:
-            regions, slot = feed[0].finish()
-        elif len(held) == 1:
-            regions = held[0][0]
-        else:
-            # gathered in ONE buffer, each loader batch released as soon as it is copied: the peak is the gathered batch plus one
-            # loader batch (8 fp32 4096 x 4096 regions: 1.6 GB + 0.2 GB), not two copies of everything
-            regions = torch.empty((sum(counts),) + tuple(held[0][0].shape[1:]), dtype=held[0][0].dtype, device=held[0][0].device)
-            o = 0
-            for i in range(len(held)):
-                r = held[i][0]
-                regions[o:o + r.shape[0]].copy_(r)
-                o += r.shape[0]
-                held[i] = None
-                del r
-        held.clear()
-        shape_key[0] = None
-        ncalls[0] += 1
-        feats = run(regions, done_regions[0])
-        done_regions[0] += sum(counts)
-        if slot is not None:
-            feed[0].release(slot)
-        del regions
-        if staged:
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(dev))
-            pending.append((feats, counts, coords, done))  # read back after the NEXT call is enqueued: the GPU never waits for the host
-            while len(pending) > 1:
-                append_call(*pending.pop(0))
-        else:
-            drain()
-            append_call(feats, counts, coords)
-
-    def stage(regions) -> bool:
-        """a HOST batch for a model on a HIP device: its copy starts NOW, into the open gather buffer (opened here if none is)"""
-        if not (dev is not None and dev.type == "cuda" and regions.device.type == "cpu"):
-            return False
-        if feed[0] is None:
-            feed[0] = _HostFeed(dev)
-        f, n = feed[0], regions.shape[0]
-        if not held:
-            # capacity: what a gathered call reaches with loader batches of this size (the batch that crosses `coalesce` is not split), so that
-            # ragged tails re-use the buffer (a later, larger batch that would overrun it starts a new call); a shape that is not gathered: this batch alone
-            f.begin(coalesce + n - 1 if (coalesce > 1 and gathers_bit_exactly(regions)) else n, regions)
-        f.add(regions)
-        return True
-
-    def gathers_bit_exactly(regions) -> bool:
-        # whole 16-row fragments in every call (patch count a multiple of 16): the gathered call and the one-by-one call take the
-        # same kernels and write the same bits; other region sizes are NOT gathered (they would agree to the bf16 bar only)
-        if resnet:
-            return True  # every output row of hipt_resnet_forward depends on its own patch only, whatever the batch
-        if regions.dim() != 4:
-            return False
-        hw = regions.shape[2:] if regions.shape[1] == 3 else regions.shape[1:3]  # planar [R,3,W,H] or interleaved [R,W,H,3]
-        return ((hw[0] // 256) * (hw[1] // 256)) % 16 == 0
-
+    # HIPT_4K: where its first-level ViT's weights live NOW (.to() may have moved it since construction)
+    dev = model.weight_device if resnet else getattr(getattr(model, "model256", None), "weight_device", None)
+    read_back = _ReadBack()
+    pending = None  # (held, features on their device, done) of a host-fed call: read back after the NEXT call is enqueued
+    first = 0
     with torch.no_grad():
-        for regions, coords in batches:
-            key = (tuple(regions.shape[1:]), regions.dtype, regions.device)
-            if held and key != shape_key[0]:
-                flush()  # a different shape / type cannot share a call
-            if held and held[0][0] is None and feed[0].fill + regions.shape[0] > feed[0].capacity():
-                flush()  # (a host batch that would overrun the open gather buffer: a loader batch larger than `coalesce` behind smaller ones)
-            shape_key[0] = key
-            held.append((None if stage(regions) else regions, coords, regions.shape[0]))
-            # (host batches: the FIRST call of a slide is a short one -- a quarter of `coalesce` -- so that the GPU starts behind 2 regions' copies
-            #  instead of 8; nothing hides the first call's copy, every later one lands under the call before it.  A region's bits do not depend
-            #  on the call it shares.)
-            want = max(1, coalesce // 4) if (held[0][0] is None and ncalls[0] == 0) else coalesce
-            if coalesce <= 1 or not gathers_bit_exactly(regions) or sum(n for _, _, n in held) >= want:
-                flush()
-        flush()
-        drain()
+        for feed, held in _fed_calls(batches, _CallPlan(coalesce), torch.device(dev) if dev is not None else None, resnet):
+            regions = feed.finish()
+            outs = run(regions, first)
+            feed.release()
+            del regions
+            first += sum(n for _, n in held)
+            late, pending = pending, None
+            if isinstance(feed, _HostFeed):  # the GPU never waits for the host
+                # `done` goes where the FEATURES are, which need not be where the regions went (every output of `run` is on ONE device)
+                pending = (held, outs, torch.cuda.Event())
+                pending[2].record(torch.cuda.current_stream(outs[0].device))
+            if late is not None:
+                _append_call(writers, late[0], read_back(*late[1:]))
+            if pending is None:
+                _append_call(writers, held, outs)
+        if pending is not None:
+            _append_call(writers, pending[0], read_back(*pending[1:]))
     return [w.close() for w in writers]
 
 

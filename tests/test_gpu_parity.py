@@ -1398,7 +1398,7 @@ def test_extract_slide_host_batches_pipelined_same_bits(hipt, tmp_path):
     from hipt_abmil_atec23_amd.feature_store import extract_slide, load_coords
     hipt.set_compute_dtype("bf16")
     try:
-        n = 11  # coalesce 4: calls of 4, 4, 3 -> both gather buffers re-used
+        n = 11  # coalesce 4: resident calls of 4, 4, 3; host-fed 1 (the short first call), 4, 4, 2 -> both gather buffers re-used
         f32 = [synth.hash_uniform_torch((1, 3, 1024, 1024), 300 + i, device=DEV) for i in range(n)]
         u8 = [((r * 0.5 + 0.5) * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous() for r in f32]
         coords = [torch.tensor([[1024 * i, 7 * i]], dtype=torch.int64) for i in range(n)]
@@ -1413,6 +1413,16 @@ def test_extract_slide_host_batches_pipelined_same_bits(hipt, tmp_path):
                 assert np.array_equal(load_coords(str(tmp_path), f"{mem}_{kind}"), torch.cat(coords).numpy())
             one = torch.load(extract_slide(hipt, list(zip([r.cpu() for r in regs], coords)), str(tmp_path), f"one_{kind}", coalesce=1))
             assert torch.equal(one, ref), kind
+        # pinned and pageable batches alternating (ref: the resident uint8 loop above).  The host-fed calls are [0], [1..4], [5..8], [9, 10]: with
+        # batch 0 pinned every gather opens on a pageable batch (offset 0); with batch 0 PAGEABLE the gathers [1..4] and [5..8] open on a pinned
+        # one and meet their first pageable batch at offset 1 -- where the staging twin of the slot ([5..8]: slot 0 again, staged by call [0])
+        # must still wait for the copies that last read it, which a wait at offset 0 alone never did
+        for first in ("pinned", "pageable"):
+            alt = [r.cpu().pin_memory() if (i % 2 == 0) == (first == "pinned") else r.cpu() for i, r in enumerate(u8)]
+            assert alt[0].is_pinned() == (first == "pinned") and alt[1].is_pinned() != alt[0].is_pinned()
+            got = torch.load(extract_slide(hipt, list(zip(alt, coords)), str(tmp_path), f"alt_{first}", coalesce=4))
+            assert torch.equal(got, ref), first
+            assert np.array_equal(load_coords(str(tmp_path), f"alt_{first}"), torch.cat(coords).numpy())
         # shapes that are not gathered (6 patches: no whole 16-row fragments) go one loader batch per call, from host memory too; and a slide
         # whose batches change shape mid-way (a staged gather is closed, the new shape starts its own)
         small = [synth.hash_uniform_torch((1, 3, 512, 768), 340 + i, device=DEV) for i in range(3)]
@@ -1424,6 +1434,31 @@ def test_extract_slide_host_batches_pipelined_same_bits(hipt, tmp_path):
         assert load_coords(str(tmp_path), "mixed_host").dtype == np.int32
     finally:
         hipt.set_compute_dtype("fp32")
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="the two-device placement needs two GPUs")
+def test_extract_slide_host_batches_two_device_placement_same_bits(tmp_path):
+    """The constructor-default placement (ViT-256 on cuda:0, ViT-4K on cuda:1): host batches are fed to cuda:0, the features come out on
+    cuda:1 and are read back one call late on a stream of THAT device, behind an event recorded there.  Pinned host batches give the file
+    of the same model fed resident batches, bit for bit."""
+    from hipt_abmil_atec23_amd import HIPT_4K
+    from hipt_abmil_atec23_amd.feature_store import extract_slide, load_coords
+    m = HIPT_4K(None, None, "cuda:0", "cuda:1")
+    m.model256.load_state_dict(synth.make_state_dict(synth.vit_param_specs("vit256"), 256))
+    m.model4k.load_state_dict(synth.make_state_dict(synth.vit_param_specs("vit4k", embed_dim=192, depth=6), 4096))
+    m = m.eval().set_compute_dtype("bf16")
+    assert m.model256.weight_device != m.model4k.weight_device
+    n = 11
+    regs = [synth.hash_uniform_torch((1, 3, 1024, 1024), 300 + i, device="cuda:0") for i in range(n)]
+    coords = [torch.tensor([[1024 * i, 7 * i]], dtype=torch.int64) for i in range(n)]
+    ref = torch.load(extract_slide(m, list(zip(regs, coords)), str(tmp_path), "resident", coalesce=4))
+    # (resident calls are 4, 4, 3 and host-fed ones 1, 4, 4, 2: were this placement's bits to depend on the call a region shares, the
+    #  one-by-one resident loop would differ from `ref` too, and the failure below would not be the read-back's)
+    one = torch.load(extract_slide(m, list(zip(regs, coords)), str(tmp_path), "one_by_one", coalesce=1))
+    assert torch.equal(one, ref), "the two-device path's bits depend on how regions are grouped into calls"
+    got = torch.load(extract_slide(m, list(zip([r.cpu().pin_memory() for r in regs], coords)), str(tmp_path), "pinned", coalesce=4))
+    assert got.shape == (n, 192) and torch.equal(got, ref)
+    assert np.array_equal(load_coords(str(tmp_path), "pinned"), torch.cat(coords).numpy())
 
 
 def test_step_bits_do_not_depend_on_stream_concurrency_or_the_run(hipt):

@@ -44,8 +44,8 @@ def finish(self):
 orig_release = FS._HostFeed.release
 
 
-def release(self, s):
-    orig_release(self, s)
+def release(self):
+    orig_release(self)
     e = E()
     e.record(torch.cuda.current_stream(self.device))
     rec[-1]["comp1"] = e
