@@ -18,6 +18,8 @@ _LAZY = {
     "HIPT_4K": ("hipt_4k", "HIPT_4K"),
     "CLAM_SB": ("model_clam", "CLAM_SB"), "CLAM_MB": ("model_clam", "CLAM_MB"),
     "Attn_Net": ("model_clam", "Attn_Net"), "Attn_Net_Gated": ("model_clam", "Attn_Net_Gated"),
+    # max-pooling MIL baselines (main.py --model_type mil)
+    "MIL_fc": ("model_mil", "MIL_fc"), "MIL_fc_mc": ("model_mil", "MIL_fc_mc"),
     "VisionTransformer": ("vision_transformer", "VisionTransformer"), "vit_small": ("vision_transformer", "vit_small"),
     "VisionTransformer4K": ("vision_transformer4k", "VisionTransformer4K"), "vit4k_xs": ("vision_transformer4k", "vit4k_xs"),
     "ResNet_Baseline": ("resnet_custom", "ResNet_Baseline"), "Bottleneck_Baseline": ("resnet_custom", "Bottleneck_Baseline"),

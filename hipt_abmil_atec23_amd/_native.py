@@ -53,6 +53,11 @@ class ClamWeights(C.Structure):
                 ("logit_bound", C.c_float), ("reserved2", C.c_int32), ("stream_pk", C.c_void_p)]
 
 
+class MilWeights(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("s0", C.c_int32), ("s1", C.c_int32), ("n_classes", C.c_int32), ("multi_class", C.c_int32),
+                ("reserved", C.c_int32), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
+
+
 class ClamTrainWeights(C.Structure):
     _fields_ = [("s0", C.c_int32), ("s1", C.c_int32), ("s2", C.c_int32), ("n_att", C.c_int32), ("n_classes", C.c_int32),
                 ("multi_branch", C.c_int32)] + [(n, C.c_void_p) for n in ("w1", "b1", "wa", "ba", "wb", "bb", "wc", "bc", "wcls", "bcls")]
@@ -95,6 +100,7 @@ CONTOURS_MAX_PLANE, CONTOURS_MAX_BORDER_PIXELS, CONTOURS_MAX_BORDERS = 1 << 27, 
 FILL_MAX_DIM, FILL_MAX_POINTS, FILL_COORD_BOUND, FILL_MAX_COLS, FILL_COLLECTION_INTS = 65535, 1 << 27, 1 << 20, 3072, 5   # HIPT_FILL_*
 
 _VW, _IL, _CW = C.POINTER(VitWeights), C.POINTER(ImageLayout), C.POINTER(ClamWeights)
+_MW = C.POINTER(MilWeights)
 _TW, _TG = C.POINTER(ClamTrainWeights), C.POINTER(ClamTrainGrads)
 _CB, _RW, _RBW = C.POINTER(ConvBN), C.POINTER(ResnetWeights), C.POINTER(ResnetBasicWeights)
 _i, _i64, _p, _sz, _f = C.c_int, C.c_int64, C.c_void_p, C.c_size_t, C.c_float
@@ -166,6 +172,9 @@ SIGNATURES = {
     "hipt_clam_mb_forward": (_i, [_CW, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "hipt_attn_net_gated": (_i, [_CW, _p, _i, _p, _p, _sz, _p]),
     "hipt_clam_gather_h1": (_i, [_CW, _p, _p, _i, _p, _p]),
+    "hipt_mil_bags_supported": (_i, [_MW]),
+    "hipt_mil_bags_workspace_bytes": (_sz, [_MW, _i, _i64]),
+    "hipt_mil_forward_bags": (_i, [_MW, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hipt_clam_train_workspace_bytes": (_sz, [_TW, _i]),
     "hipt_clam_train_shape_supported": (_i, [_i, _i, _i, _i, _i, _i]),
     "hipt_clam_train_forward": (_i, [_TW, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),

@@ -1296,6 +1296,55 @@ HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags_wide, hipt_clam_mb_wide_bags_work
 HIPT_CLAM_BAGS_ENTRY(hipt_clam_mb_forward_bags_many, hipt_clam_mb_many_bags_workspace_bytes, BAGS_MB_MANY)
 #undef HIPT_CLAM_BAGS_ENTRY
 
+// ---- max-pooling MIL over B bags (mil.hip): the unit table of the calls above | tile_start | one record per unit; no state ----
+int hipt_mil_bags_supported(const hipt_mil_weights* w) {
+    return w && (w->dtype == HIPT_F32 || w->dtype == HIPT_BF16) && hipt_mil_supported(w) ? 1 : 0;
+}
+struct MilBagsWs { void* units; int* tile_start; void* records; };
+static MilBagsWs carve_mil_bags(Carver& c, int B, int64_t total_rows) {
+    const size_t nu = (size_t)clam_bags_max_units(B, total_rows);
+    MilBagsWs k;
+    k.units = c.take(nu * hipt_clam_bags_unit_bytes());
+    k.tile_start = c.take<int>((size_t)B + 1);
+    k.records = c.take(nu * hipt_mil_record_bytes());
+    return k;
+}
+
+size_t hipt_mil_bags_workspace_bytes(const hipt_mil_weights* w, int B, int64_t total_rows) {
+    if (!hipt_mil_bags_supported(w) || B < 1 || total_rows < B || clam_bags_max_units(B, total_rows) > INT32_MAX) return 0;
+    return dry_run([&](Carver& c) { carve_mil_bags(c, B, total_rows); });
+}
+
+int hipt_mil_forward_bags(const hipt_mil_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                          float* y_probs, int64_t* top_idx, float* top_logits, float* top_prob, int64_t* y_hat, float* top_features,
+                          void* workspace, size_t ws_bytes, void* stream) {
+    const char* name = "mil_forward_bags";
+    HIPT_CHECK_ARG(w != nullptr, "%s: null weights", name);
+    HIPT_CHECK_ARG(w->dtype == HIPT_F32 || w->dtype == HIPT_BF16, "%s: bad dtype %d", name, w->dtype);
+    HIPT_CHECK_ARG(w->w1 && w->b1 && w->w2 && w->b2, "%s: null weight pointer", name);
+    HIPT_CHECK_ARG(bags && offsets_dev && y_probs && top_idx && top_logits && top_prob && y_hat && workspace, "%s: null argument", name);
+    HIPT_CHECK_ARG(((uintptr_t)bags & 15) == 0 && ((uintptr_t)w->w1 & 15) == 0 && ((uintptr_t)w->w2 & 15) == 0 && ((uintptr_t)w->b1 & 15) == 0 &&
+                       (top_features == nullptr || ((uintptr_t)top_features & 15) == 0),
+                   "%s: bags, w1, b1, w2 and top_features must be 16-byte aligned", name);
+    HIPT_CHECK_ARG(B >= 1 && total_rows >= B, "%s: B = %d bags need at least one row each (total_rows = %lld)", name, B, (long long)total_rows);
+    HIPT_CHECK_ARG(clam_bags_max_units(B, total_rows) <= INT32_MAX, "%s: %lld rows in %d bags exceed 2^31 tiles", name, (long long)total_rows, B);
+    if (!hipt_mil_bags_supported(w)) {
+        hipt_set_error("%s: [%d,%d] with %d classes (multi_class = %d) is outside the envelope: S1 in {256, 512}, S0 a multiple of 32 (fp32) / "
+                       "64 (bf16), 2 <= classes <= 8, two classes unless multi_class", name, w->s0, w->s1, w->n_classes, w->multi_class);
+        return HIPT_E_UNSUPPORTED;
+    }
+    Carver c(workspace, ws_bytes);
+    const MilBagsWs k = carve_mil_bags(c, B, total_rows);
+    if (check_workspace(c, name)) return HIPT_E_BADARG;  // as the CLAM multi-bag calls: a short buffer is a bad argument
+    hipStream_t st = S(stream);
+    const int nu = (int)clam_bags_max_units(B, total_rows);
+    int rc;
+    PROF(PC_OTHER, hipt_clam_bags_units_launch(offsets_dev, B, total_rows, nu, k.tile_start, k.units, st));
+    PROF(PC_ABMIL, hipt_mil_tiles_combine_launch(w, bags, offsets_dev, B, k.units, k.tile_start, nu, y_probs, k.records, top_idx, top_logits,
+                                                 top_prob, y_hat, top_features, st));
+    return HIPT_OK;
+}
+
 int hipt_clam_mb_supported(const hipt_clam_weights* w) { return w && check_clam(w) == HIPT_OK && hipt_clam_mb_stream_supported(w) ? 1 : 0; }
 
 // ticket | partials of <= 128 workgroups x 4 branches | h1 as a bf16 image

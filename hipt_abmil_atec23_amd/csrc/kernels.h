@@ -253,6 +253,13 @@ int hipt_clam_wide_mb_tiles_launch(const hipt_clam_weights* w, const void* bags,
 // four behind one gate GEMM, each branch in that kernel's order of operations; the same partials, for hipt_clam_bags_mb_combine_launch
 int hipt_clam_bags_mb8_tiles_launch(const hipt_clam_weights* w, const void* bags, const void* units, int max_units,
                                     int attention_only, int64_t a_stride, float* A_raw, float* partials, hipStream_t st);
+// max-pooling MIL (mil.hip) on the unit table above: the tile pass (y_probs, one record per unit of hipt_mil_record_bytes()) and the per-bag
+// combine, which recomputes the selected row.  Widths: S1 in {256, 512}, S0 a multiple of 32 (fp32) / 64 (bf16), 2..8 classes
+bool hipt_mil_supported(const hipt_mil_weights* w);
+size_t hipt_mil_record_bytes();
+int hipt_mil_tiles_combine_launch(const hipt_mil_weights* w, const void* bags, const int64_t* offsets, int B, const void* units,
+                                  const int* tile_start, int max_units, float* y_probs, void* records, int64_t* top_idx,
+                                  float* top_logits, float* top_prob, int64_t* y_hat, float* top_features, hipStream_t st);
 
 // ---- bootstrapped evaluation metrics (bootstrap.hip) ----
 size_t hipt_bootstrap_lds_bytes(int n);

@@ -492,6 +492,42 @@ int hipt_clam_gather_h1(const hipt_clam_weights* w, const void* bag, const int64
                         float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Max-pooling MIL baseline (models/model_mil.py: MIL_fc, MIL_fc_mc; main.py --model_type mil)
+ * ---------------------------------------------------------------------------------- */
+typedef struct hipt_mil_weights {
+    int32_t dtype;            /* type of w1 (and of the bags)                                                    */
+    int32_t s0, s1;           /* size_dict entry [S0, S1] (model_mil.py:11)                                      */
+    int32_t n_classes;        /* C: 2 for MIL_fc, 3 .. 8 for MIL_fc_mc                                           */
+    int32_t multi_class;      /* 0: MIL_fc (the row with the largest y_probs[:, 1]); 1: MIL_fc_mc (the first maximum of y_probs
+                                 flattened to [N * C])                                                           */
+    int32_t reserved;
+    const void*  w1; const float* b1;   /* Linear(S0, S1) (+ReLU)  [S1, S0], [S1]                                */
+    const float* w2; const float* b2;   /* MIL_fc: the Linear(S1, 2); MIL_fc_mc: the C Linear(S1, 1) stacked.  [C, S1], [C], fp32 in
+                                           both dtypes, w2 16-byte aligned                                       */
+} hipt_mil_weights;
+
+/* MIL_fc.forward / MIL_fc_mc.forward (model_mil.py:26-43, :68-93; top_k = 1) over B ragged bags in ONE call; one bag is B = 1.
+ *   h1 = ReLU(x W1^T + b1); logits = h1 W2^T + b2; y_probs = softmax_C(logits), per row;
+ *   the selected row of a bag: MIL_fc -- the largest y_probs[:, 1]; MIL_fc_mc -- the first maximum of y_probs flattened to [N * C].
+ *   Equal keys: the LOWEST row wins, then the lowest class (torch.topk leaves the order of equal values open; argmax takes the first).
+ * bags, offsets_dev, B, total_rows: as hipt_clam_sb_forward_bags; every bag has at least one row.
+ * Outputs: y_probs fp32 [total_rows, C]; per bag top_idx int64 [B] (bag-local row), top_logits fp32 [B, C] = logits of that row, top_prob
+ * fp32 [B, C] = its row of y_probs, bit for bit; y_hat int64 [B] = the first maximum of top_logits; top_features fp32 [B, S1] = the row of
+ * h1 (NULL: not written).  Rows outside a bag are never written.
+ * Rounding: fp32 -- everything fp32.  bf16 -- the bags and W1 are bf16, the products accumulate in fp32, everything from + b1 on is fp32.
+ * Three plain launches on `stream` (abmil_bags' unit table, the tile pass, one combine workgroup per bag which recomputes the selected row):
+ * no atomics, no host synchronisation, graph-capturable, no state in the workspace.  A bag's outputs are bit for bit independent of the
+ * other bags of the call, of its position, of B and of the grid.
+ * hipt_mil_bags_supported(w) != 0: S1 in {256, 512}, S0 a positive multiple of 32 (fp32) / 64 (bf16), 2 <= C <= 8, C == 2 unless multi_class,
+ * fp32 or bf16; otherwise HIPT_E_UNSUPPORTED and hipt_mil_bags_workspace_bytes = 0.  HIPT_E_BADARG -- before anything is launched -- for
+ * a null pointer, misaligned bags or w2, B < 1, total_rows < B (an empty bag), a short or misaligned workspace. */
+int hipt_mil_bags_supported(const hipt_mil_weights* w);
+size_t hipt_mil_bags_workspace_bytes(const hipt_mil_weights* w, int B, int64_t total_rows);
+int hipt_mil_forward_bags(const hipt_mil_weights* w, const void* bags, const int64_t* offsets_dev, int B, int64_t total_rows,
+                          float* y_probs, int64_t* top_idx, float* top_logits, float* top_prob, int64_t* y_hat, float* top_features,
+                          void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * CLAM training step: differentiable forward + backward of CLAM_SB.forward / CLAM_MB.forward
  * (models/model_clam.py:147-191, 226-264) with the instance branch's top-k (inst_eval / inst_eval_out, :116-145), as
  * driven by utils/core_utils.py:300-348 (train_loop_clam) and :373-426 (train_loop; loss.backward() at :423).
