@@ -168,48 +168,61 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// k_sel largest entries of sign * a[0..N), descending, ties -> lowest index first (torch.topk on distinct values; the
-// order among equal values is index-ascending, what a stable sort gives).  ids: int64 [k_sel].  One workgroup.
+// The order of topk_block as an integer key, one total order on every fp32 value: -inf < finite < +inf < NaN (either sign bit, any
+// payload), -0.0 == +0.0.  Non-negative floats keep their bits, negative ones are mirrored below zero; no key is TOPK_KEY_NONE.
+constexpr int TOPK_KEY_NAN = 0x7fffffff, TOPK_KEY_NONE = -0x7fffffff - 1;
+__device__ __forceinline__ int topk_key(float v) {
+    const int b = __float_as_int(v), m = b & 0x7fffffff;
+    if (m > 0x7f800000) return TOPK_KEY_NAN;
+    return b < 0 ? -m : m;
+}
+
+// k_sel largest entries of sign * a[0..N), descending, NaN above +inf (torch.topk's place for it, under either sign), -0.0 == +0.0, ties
+// -- and NaNs among themselves -- lowest index first (torch.topk on distinct values; the order among equal values is index-ascending,
+// what a stable sort gives).  (key, index) is a strict total order, so each of the k_sel <= N iterations finds the successor of the
+// previous winner: every id written lies in [0, N), whatever the values.  ids: int64 [k_sel].  One workgroup; red carries the keys' bits.
 __device__ void topk_block(const float* __restrict__ a, int N, float sign, int k_sel, int64_t* __restrict__ ids, float* red, int* redi) {
-    float pv = INFINITY;
+    int pk = TOPK_KEY_NAN;
     int pi = -1;
     for (int it = 0; it < k_sel; ++it) {
-        float bv = -INFINITY;
+        int bk = TOPK_KEY_NONE;  // below every key
         int bi = 0x7fffffff;
         for (int i = threadIdx.x; i < N; i += 256) {
-            const float v = sign * a[i];
-            const bool eligible = v < pv || (v == pv && i > pi);
-            if (eligible && (v > bv || (v == bv && i < bi))) {
-                bv = v;
+            const int v = topk_key(sign * a[i]);
+            const bool eligible = v < pk || (v == pk && i > pi);
+            if (eligible && (v > bk || (v == bk && i < bi))) {
+                bk = v;
                 bi = i;
             }
         }
-        // wave argmax (value desc, index asc), then across the 4 waves
+        // wave argmax (key desc, index asc), then across the 4 waves
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
+            const int ok = __shfl_xor(bk, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
+            if (ok > bk || (ok == bk && oi < bi)) {
+                bk = ok;
                 bi = oi;
             }
         }
         __syncthreads();
         if ((threadIdx.x & 63) == 0) {
-            red[threadIdx.x >> 6] = bv;
+            red[threadIdx.x >> 6] = __int_as_float(bk);
             redi[threadIdx.x >> 6] = bi;
         }
         __syncthreads();
-        bv = red[0];
+        bk = __float_as_int(red[0]);
         bi = redi[0];
 #pragma unroll
-        for (int q = 1; q < 4; ++q)
-            if (red[q] > bv || (red[q] == bv && redi[q] < bi)) {
-                bv = red[q];
+        for (int q = 1; q < 4; ++q) {
+            const int qk = __float_as_int(red[q]);
+            if (qk > bk || (qk == bk && redi[q] < bi)) {
+                bk = qk;
                 bi = redi[q];
             }
+        }
         if (threadIdx.x == 0) ids[it] = bi;
-        pv = bv;
+        pk = bk;
         pi = bi;
     }
 }

@@ -583,7 +583,9 @@ int hipt_clam_train_backward(const hipt_clam_train_weights* w, const float* bag,
                              const hipt_clam_train_grads* g, void* workspace, size_t ws_bytes, void* stream);
 
 /* torch.topk(A, k) and torch.topk(-A, k) of every row of A [rows, N] on the device (inst_eval, :120-123):
- * ids int64 [rows, 2, k], descending / ascending by value, ties -> lowest index first. */
+ * ids int64 [rows, 2, k], descending / ascending by value, ties -> lowest index first.  One total order on fp32: -0.0 == +0.0, and a NaN
+ * (either sign bit) ranks above +inf in BOTH lists, as in torch.topk, NaNs among themselves lowest index first.  Every id lies in [0, N)
+ * whatever the values. */
 int hipt_topk_rows(const float* A, int rows, int N, int k, int64_t* ids, void* stream);
 
 /* hipt_topk_rows over the bags of a multi-bag call (the instance branch of validate_clam, one launch per call instead of one per slide).
